@@ -2,6 +2,14 @@
 """Headline benchmark: Prover::prove wall-clock on MI355X (BASELINE.json metric).
 
   python bench.py --gpus N --steps K --warmup W [--log-gates G] [--profile dense|bench-like|widgets]
+                  [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times exactly K steps and prints one JSON line whose `value` / `ms_per_step` is the
+milliseconds of one timed step.  --dump-outputs DIR: after the timed steps, the proof of the last step is written as
+DIR/proof.npy (its 1008 bytes as float64, 11 x 48-byte compressed G1 commitments then 15 x 32-byte evaluations); the
+inputs are seeded, so two builds given the same arguments can be compared proof for proof.  --full adds everything
+beyond the headline figure to the same line: the proof from pinned host wire columns, standalone NTT / seam / MSM
+micro timings, the other workloads and sizes (2^12, 2^16, 2^22), plonk_compile, and the CPU baseline.
 
 A step = one full prove() (V3) of a synthetic 2^G-gate circuit: 5 iNTT(n) (a, b, c, d, z; +1 for the
 public-input polynomial when the circuit has public inputs) + 5 coset-NTT(4n) (+1) + 1 coset-iNTT(4n)
@@ -634,16 +642,24 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--log-gates", type=int, default=20)
     ap.add_argument("--profile", default="dense", choices=["dense", "bench-like", "widgets"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-2p22", action="store_true", help="skip the 2^22-gate extra of the default line (about half a minute of setup)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the extra workloads / leaf costs of the N=1 line")
-    ap.add_argument("--host-wires-only", action="store_true", help="of the extras, only the proof from pinned host wire columns (A/B scripts)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's proof as DIR/proof.npy (float64 bytes)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the extras and the CPU baseline (host wire columns, NTT / MSM micro, leaf costs, other "
+                         "workloads and sizes, plonk_compile); a plain run measures the headline figure only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-2p22", action="store_true", help="with --full: skip the 2^22-gate extra (about half a minute of setup)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the extra workloads / leaf costs of the N=1 line")
+    ap.add_argument("--host-wires-only", action="store_true",
+                    help="with --full: of the extras, only the proof from pinned host wire columns (A/B scripts)")
     ap.add_argument("--from-circuit", action="store_true",
                     help="build the prover with plonk_compile from gate columns (Compiler::preprocess on the device) instead of "
                          "from coefficient forms, and check plonk_prover_prove_witnesses against the column entry point")
     ap.add_argument("--dry-launch", action="store_true",
                     help="launcher self-test: every rank joins the gloo group, all-reduces its rank and exits (no GPU needed)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    extras = args.full and not args.no_extras
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))       # `python bench.py --gpus N`: this process only launches and supervises the N ranks
@@ -831,7 +847,7 @@ def main():
             "scaling": "strong", "vs_baseline": None, "dtype": "u32 limbs (Fr 256-bit / Fp 384-bit Montgomery)",
             "data": "synthetic",
             # the contract's `value`: inputs resident in HBM when the timed region starts.  What a drop-in caller of Prover::prove
-            # pays on top is printed beside it: prove_ms_host_wires_pinned (2^20) / host_legs_2p22
+            # pays on top is printed beside it by --full: prove_ms_host_wires_pinned (2^20) / host_legs_2p22
             "value_excludes": "H2D of the 4 x 32 n wire bytes (%d MiB at this size)" % (4 * 32 * n >> 20),
             "config": {"workload": "Prover::prove V3, synthetic 2^%d-gate circuit, profile `%s` (%s), random SRS of n+7 points, "
                                    "wires/ProverKey/SRS tables resident in HBM" % (
@@ -875,8 +891,12 @@ def main():
                                     # wire / permutation polynomials of rounds 1-2: the part every rank of a multi-GPU run repeats
                                     "rounds_1_2_polynomials_replicated": round(rep_ms / args.steps, 3)},
         }
-        vk48 = prover.vk_commitments()
-        if world == 1 and not args.no_extras:
+        if args.dump_outputs:
+            import numpy as np
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            np.save(os.path.join(args.dump_outputs, "proof.npy"), np.frombuffer(proof, dtype=np.uint8).astype(np.float64))
+        vk48 = prover.vk_commitments() if args.full else None
+        if world == 1 and extras:
             try:   # the boundary handing over HOST wire columns (pinned): PCIe-inclusive prove(), never `value`
                 out["prove_ms_host_wires_pinned"] = host_wire_legs(ctx, prover, wbuf, n, blinders, proof, max(2, min(args.steps, 5)))
                 # what separates it from `value`: the first column's copy (measured, nothing can run under it) + three extra
@@ -887,7 +907,7 @@ def main():
                                      "wire_bytes_mib": 4 * 32 * n >> 20}
             except Exception as e:   # noqa: BLE001
                 out["host_wires_error"] = repr(e)
-        if world == 1 and not args.no_extras and not args.host_wires_only and args.profile == "dense":
+        if world == 1 and extras and not args.host_wires_only and args.profile == "dense":
             try:   # seam-level cost, measured while the prover is still alive: once a process has FREED tens of GB of device
                    # buffers the runtime stops overlapping the two copy directions of plonk_ntt_batch (33 -> 53 ms; bisected in
                    # profiles/r03b/ntt_batch_overlap_bisect.txt — variant C = prover.close() before the call)
@@ -900,7 +920,7 @@ def main():
                 out["leaf_error"] = repr(e)
         prover.close()
         wbuf.free()
-        if world == 1 and not args.no_extras and not args.host_wires_only and args.profile == "dense":
+        if world == 1 and extras and not args.host_wires_only and args.profile == "dense":
             try:   # the other workloads of SURVEY §8(d); never a reason to lose the line
                 k = max(2, min(args.steps, 5))
                 out["prove_ms_bench_like"] = time_profile(ctx, log_n, "bench-like", k, blinders)
@@ -922,7 +942,7 @@ def main():
                     out["compile"]["proof_matches_timed_run"] = bool(out["compile"]["proof_blake2b"] == out["proof_blake2b"])
             except Exception as e:   # noqa: BLE001
                 out["extras_error"] = repr(e)
-        if world == 1 and not args.no_extras and not args.host_wires_only and args.profile == "dense" and log_n == 20 and not args.no_2p22:
+        if world == 1 and extras and not args.host_wires_only and args.profile == "dense" and log_n == 20 and not args.no_2p22:
             try:   # BASELINE config 5's size on one GPU (commit key streamed from pinned host memory): after everything else, own guard
                 t22 = time.perf_counter()
                 dg = {}
@@ -943,12 +963,12 @@ def main():
                 ctx.srs_load([])
             except Exception:   # noqa: BLE001
                 pass
-        if world == 1 and not args.no_cpu_baseline and args.profile == "dense":
+        if world == 1 and args.full and not args.no_cpu_baseline and args.profile == "dense":
             try:
                 out["cpu_baseline"], cpu_proof = cpu_baseline(log_n, vk48)
                 if log_n <= 20:   # same SRS, circuit, witness and blinders: the CPU port must produce the same bytes
                     out["cpu_baseline"]["proof_matches_gpu"] = bool(cpu_proof == proof)
-                if not args.no_extras:   # north_star: "prove-time at 2^16 .. 2^22 ... next to the CPU path": the port at the small sizes too
+                if extras:   # north_star: "prove-time at 2^16 .. 2^22 ... next to the CPU path": the port at the small sizes too
                     for lg in (16, 12):
                         if lg != log_n:
                             out["cpu_baseline_2p%d" % lg] = cpu_baseline_small(ctx, lg, blinders)

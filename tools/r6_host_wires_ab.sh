@@ -8,7 +8,7 @@ mkdir -p $out
 export PLONK_CIRCUIT_CACHE=/tmp/plonk_circuits_r6
 for lg in 20 19; do
 for v in 0 2 1 0 1; do
-  PLONK_WIRE_BY_COLUMN=$v python bench.py --log-gates $lg --no-cpu-baseline --host-wires-only --steps 10 2>>$out/ab_err.txt | python -c "
+  PLONK_WIRE_BY_COLUMN=$v python bench.py --full --log-gates $lg --no-cpu-baseline --host-wires-only --steps 10 2>>$out/ab_err.txt | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print(json.dumps({'log_gates': $lg, 'PLONK_WIRE_BY_COLUMN': $v, 'value': d['value'], 'prove_ms_host_wires_pinned': d.get('prove_ms_host_wires_pinned'), 'gap_ms': round(d.get('prove_ms_host_wires_pinned', 0) - d['value'], 3), 'error': d.get('host_wires_error'), 'proof': d['proof_blake2b']}))"
