@@ -54,7 +54,8 @@ enum {
   PLONK_ERR_BYTES = -8,   /* serialized input too short (Error::NotEnoughBytes)         */
   PLONK_ERR_DATA = -9,    /* serialized input malformed (dusk_bytes::Error::InvalidData) */
   PLONK_ERR_POINT = -10,  /* commit-key point off curve / not in the subgroup (Error::PointMalformed) */
-  PLONK_ERR_NOMEM = -11   /* a host allocation failed inside the library (std::bad_alloc caught at the ABI)  */
+  PLONK_ERR_NOMEM = -11,  /* a host allocation failed inside the library (std::bad_alloc caught at the ABI)  */
+  PLONK_ERR_VERIFY = -12  /* a proof does not verify (Error::ProofVerificationError)    */
 };
 
 /* `devices`: HIP device ordinals; ndev must be 1 (one process per GPU — multi-GPU runs
@@ -419,7 +420,7 @@ int plonk_comm_destroy(plonk_ctx* ctx);
  * key and the VerifierKey — so a circuit compiled by plonk_compile can be loaded by the unmodified reference
  * (Prover::try_from_bytes) or by plonk_prover_from_bytes later.  plonk_verifier_to_bytes writes Verifier::to_bytes()
  * (src/compiler/verifier.rs:88-117) from the prover's label / sizes / VerifierKey, the caller's OpeningKey::to_bytes()
- * (opaque here: G2 never enters this library) and the public-input indexes.
+ * (copied as given; plonk_verifier_from_bytes below decodes it) and the public-input indexes.
  * Both: out == NULL reports the length in *len; otherwise cap >= *len bytes are written.  Single-GPU provers only.
  * Known differences from the reference's bytes (format parity is pinned only to the restated layout):
  * plonk_prover_from_bytes keeps the size + 8 commit-key points prove() can touch, so from_bytes -> to_bytes writes a
@@ -429,6 +430,46 @@ int plonk_comm_destroy(plonk_ctx* ctx);
 int plonk_prover_to_bytes(plonk_prover* p, uint8_t* out, uint64_t cap, uint64_t* len);
 int plonk_verifier_to_bytes(plonk_prover* p, const uint8_t* opening_key, uint64_t opening_key_len,
                             const uint64_t* pi_idx, uint64_t pi_count, uint8_t* out, uint64_t cap, uint64_t* len);
+/* Proof verification (Verifier::try_from_bytes / Verifier::verify, src/compiler/verifier.rs:121-253, src/proof_system/
+ * proof.rs:218-513), for a batch of proofs of one circuit.
+ * plonk_verifier_from_bytes takes the blob plonk_verifier_to_bytes (or the reference's Verifier::to_bytes) writes and
+ * validates it like the reference: the six big-endian lengths (PLONK_ERR_BYTES when the blob is shorter than they say or
+ * they overflow), the 15 VerifierKey commitments (PLONK_ERR_DATA), the OpeningKey's g, h and x_h (on their curves, in the
+ * subgroup, not the identity: PLONK_ERR_DATA), a power-of-two domain size, vk.n == constraints and public-input indexes
+ * inside the domain (PLONK_ERR_DATA).  The VK points and g are decoded on the device once; h and x_h are prepared for
+ * the Miller loop on the host.  A verifier holds device memory of its context and never touches the context's commit
+ * key, tables or provers; destroy it before its context.
+ * plonk_verifier_set_version: 3 (default) = PlonkVersion::V3 transcript, 2 = the legacy seeding (the rule of
+ * plonk_prover_set_version); anything else PLONK_ERR_ARG.
+ * plonk_verify checks `count` proofs (count x 1008 bytes, Proof::to_bytes).  pi: count x pi_count Fr (Montgomery limbs,
+ * like pi_val of plonk_prover_prove), dense, in the verifier's public-input index order.  verdicts (count entries; may be
+ * NULL when count == 1): PLONK_OK, PLONK_ERR_VERIFY, PLONK_ERR_DATA (non-canonical evaluation), PLONK_ERR_POINT (a
+ * commitment is not a valid compressed point of G1).  Returns PLONK_OK iff every proof is valid, PLONK_ERR_VERIFY when
+ * at least one is not, PLONK_ERR_ARG for pi_count != the verifier's count (Error::InconsistentPublicInputsLen), count == 0
+ * or count > 2^24.
+ * The K checks e(-L_k, x_h) e(R_k, h) == 1 are folded with the powers 1, rho, rho^2, ... of a challenge rho drawn from
+ * a transcript over the whole (sub-)batch ("plonk-batch-verify-v1": its length, every proof's bytes and public inputs):
+ * one MSM of 13 K + 16 terms for L and R on the device and ONE pairing check on the host, whatever K is.  With K = 1 the
+ * weight is 1 and the check is exactly the reference's.  A failing batch is bisected, a fresh rho per sub-batch, until
+ * every failing proof is found: b bad proofs cost O(b log K) further checks; the verdicts equal those of count == 1
+ * calls (up to the aggregation's soundness error, <= K / q per check; DESIGN.md, "Proof verification").  The call holds
+ * the context for its whole duration, bisection included: a batch of K proofs that are ALL bad costs 2K - 1 checks (each one
+ * MSM launch and one pairing, ~10 ms at small sizes), so a caller verifying untrusted batches on a context it also proves
+ * on should bound K.
+ * plonk_verifier_last reports the last plonk_verify: msm_terms counts the terms of both sums of its FIRST check,
+ * pairing_checks all checks (1 for a valid batch), the phase times are host wall-clock milliseconds. */
+typedef struct plonk_verifier plonk_verifier;
+typedef struct {
+  uint64_t proofs, msm_terms;
+  uint32_t pairing_checks, rejected;
+  double ms_decode, ms_scalars, ms_msm, ms_pairing;
+} plonk_verify_info;
+int plonk_verifier_from_bytes(plonk_ctx* ctx, const uint8_t* blob, uint64_t len, plonk_verifier** out);
+void plonk_verifier_destroy(plonk_verifier* v);
+int plonk_verifier_set_version(plonk_verifier* v, int version);
+int plonk_verify(plonk_verifier* v, const uint8_t* proofs, const uint64_t* pi, uint64_t pi_count, uint64_t count,
+                 int32_t* verdicts);
+int plonk_verifier_last(plonk_verifier* v, plonk_verify_info* out);
 typedef struct {
   uint64_t size, constraints;
   uint64_t label_off, label_len;

@@ -39,6 +39,7 @@ ERRORS = {
     -4: "PLONK_ERR_NO_SRS", -5: "PLONK_ERR_NO_GPU", -6: "PLONK_ERR_UNSAT (CircuitUnsatisfied)",
     -7: "PLONK_ERR_STATE", -8: "PLONK_ERR_BYTES (NotEnoughBytes)", -9: "PLONK_ERR_DATA (InvalidData)",
     -10: "PLONK_ERR_POINT (PointMalformed)", -11: "PLONK_ERR_NOMEM (host allocation failed inside the library)",
+    -12: "PLONK_ERR_VERIFY (ProofVerificationError)",
 }
 
 # every symbol include/plonk_hip.h declares (checked by tests/test_capi_symbols.py)
@@ -58,6 +59,7 @@ EXPORTS = [
     "plonk_host_alloc", "plonk_host_free", "plonk_lagrange_key",
     "plonk_compile", "plonk_prover_prove_witnesses", "plonk_prover_to_bytes", "plonk_verifier_to_bytes",
     "plonk_public_parameters_check", "plonk_srs_load_public_parameters",
+    "plonk_verifier_from_bytes", "plonk_verifier_destroy", "plonk_verifier_set_version", "plonk_verify", "plonk_verifier_last",
 ]
 
 POLY_ORDER = ["q_m", "q_l", "q_r", "q_o", "q_f", "q_c", "q_arith", "q_range", "q_logic",
@@ -124,6 +126,12 @@ class _BlobInfo(ctypes.Structure):
                 ("srs_off", ctypes.c_uint64), ("srs_points", ctypes.c_uint64), ("vk_off", ctypes.c_uint64)]
 
 
+class _VerifyInfo(ctypes.Structure):
+    _fields_ = [("proofs", ctypes.c_uint64), ("msm_terms", ctypes.c_uint64), ("pairing_checks", ctypes.c_uint32),
+                ("rejected", ctypes.c_uint32), ("ms_decode", ctypes.c_double), ("ms_scalars", ctypes.c_double),
+                ("ms_msm", ctypes.c_double), ("ms_pairing", ctypes.c_double)]
+
+
 class _PublicParametersInfo(ctypes.Structure):
     _fields_ = [("opening_key_off", ctypes.c_uint64), ("points_off", ctypes.c_uint64), ("point_stride", ctypes.c_uint64),
                 ("points_total", ctypes.c_uint64), ("points_kept", ctypes.c_uint64)]
@@ -165,6 +173,10 @@ class PointMalformed(PlonkError):
 
 
 _DECODE_ERRORS = {-8: NotEnoughBytes, -9: InvalidData, -10: PointMalformed}
+
+
+class ProofVerificationError(PlonkError):
+    """Mirrors Error::ProofVerificationError (reference proof.rs:502-512): plonk_verify's PLONK_ERR_VERIFY."""
 
 
 class PolynomialDegreeTooLarge(PlonkError):
@@ -227,6 +239,13 @@ def load_library() -> ctypes.CDLL:
     lib.plonk_prover_prove_witnesses.argtypes = [vp, vp, u64, vp, vp, u64, vp, vp]
     lib.plonk_prover_to_bytes.argtypes = [vp, vp, u64, ctypes.POINTER(u64)]
     lib.plonk_verifier_to_bytes.argtypes = [vp, vp, u64, vp, u64, vp, u64, ctypes.POINTER(u64)]
+    lib.plonk_verifier_from_bytes.argtypes = [vp, vp, u64, ctypes.POINTER(vp)]
+    lib.plonk_verifier_destroy.argtypes = [vp]
+    lib.plonk_verifier_destroy.restype = None
+    lib.plonk_verifier_set_version.argtypes = [vp, ci]
+    lib.plonk_verify.argtypes = [vp, vp, vp, u64, u64, vp]
+    lib.plonk_verifier_last.argtypes = [vp, vp]
+    lib.plonk_test_verify_msm.argtypes = [vp, vp, vp, u64, vp]   # test hook of verify.hip, not in the header
     lib.plonk_host_alloc.argtypes = [u64, ctypes.POINTER(vp)]
     lib.plonk_host_free.argtypes = [vp]
     lib.plonk_comm_unique_id.argtypes = [vp]
@@ -498,6 +517,16 @@ class Context:
         return self.msm(c)
 
     # ---- device-resident API ----------------------------------------------------
+    def _verify_msm(self, points, scalars):
+        """TEST HOOK: the device MSM of plonk_verify (verify.hip) on affine points (None = identity) and integer scalars;
+        returns the affine sum.  Not part of the C API."""
+        assert len(points) == len(scalars) and points
+        comp = b"".join(g1_compress(p) for p in points)
+        sc = b"".join((s % Q).to_bytes(32, "little") for s in scalars)
+        out = ctypes.create_string_buffer(97)
+        self._check(self.lib.plonk_test_verify_msm(self.handle, comp, sc, len(points), out))
+        return g1_from_raw97(out.raw)
+
     def alloc(self, nbytes: int) -> DeviceBuffer:
         return DeviceBuffer(self, nbytes)
 
@@ -835,6 +864,75 @@ class Prover:
         if getattr(self, "handle", None):
             if getattr(self.ctx, "handle", None):          # a closed context already destroyed its provers
                 self.ctx.lib.plonk_prover_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Verifier:
+    """The reference's `Verifier` (src/compiler/verifier.rs): built from Verifier::to_bytes() (plonk_verifier_from_bytes;
+    raises NotEnoughBytes / InvalidData like try_from_bytes).  `verify` checks one proof, `verify_batch` a batch of proofs
+    of this circuit in one aggregated pairing check (plonk_verify).  Destroyed before its context, like a prover."""
+
+    def __init__(self, ctx: Context, blob: bytes):
+        self.ctx = ctx
+        h = ctypes.c_void_p()
+        ctx._check(ctx.lib.plonk_verifier_from_bytes(ctx.handle, blob, len(blob), ctypes.byref(h)))
+        self.handle = h
+        ctx._provers.add(self)
+
+    def set_version(self, version: int):
+        """3 (default, PlonkVersion::V3) or the legacy 2 transcript seeding."""
+        self.ctx._check(self.ctx.lib.plonk_verifier_set_version(self.handle, version))
+
+    def _call(self, proofs, pis):
+        proofs = list(proofs)
+        pis = [list(p) for p in pis]
+        if len(proofs) != len(pis):
+            raise ValueError("one public-input list per proof")
+        count = len(proofs)
+        npi = len(pis[0]) if pis else 0
+        if any(len(p) != npi for p in pis):
+            raise ValueError("every proof needs the same number of public inputs")
+        blob = b"".join(bytes(p) for p in proofs)
+        if any(len(p) != 1008 for p in proofs):
+            raise ValueError("a proof is 1008 bytes")
+        pi = fr_to_bytes_mont([v for p in pis for v in p])
+        verdicts = (ctypes.c_int32 * max(count, 1))()
+        rc = self.ctx.lib.plonk_verify(self.handle, blob, pi if npi else None, npi, count, verdicts)
+        return rc, [int(v) for v in verdicts[:count]]
+
+    def verify(self, proof: bytes, public_inputs) -> bool:
+        """Verifier::verify: True for a valid proof, False for PLONK_ERR_VERIFY / _DATA / _POINT; public_inputs in the
+        verifier's index order.  Raises on argument errors (e.g. PLONK_ERR_ARG for the wrong number of inputs)."""
+        rc, verdicts = self._call([proof], [public_inputs])
+        if rc not in (PLONK_OK, -12):
+            self.ctx._check(rc)
+        return rc == PLONK_OK
+
+    def verify_batch(self, proofs, public_inputs) -> list:
+        """per-proof verdict codes (0 = valid, -12 PLONK_ERR_VERIFY, -9 PLONK_ERR_DATA, -10 PLONK_ERR_POINT)"""
+        if not proofs:
+            raise ValueError("empty batch")
+        rc, verdicts = self._call(proofs, public_inputs)
+        if rc not in (PLONK_OK, -12):
+            self.ctx._check(rc)
+        return verdicts
+
+    def last(self) -> dict:
+        """plonk_verifier_last: what the last verification ran (proofs, msm_terms, pairing_checks, rejected, phase times)"""
+        info = _VerifyInfo()
+        self.ctx._check(self.ctx.lib.plonk_verifier_last(self.handle, ctypes.byref(info)))
+        return {k: getattr(info, k) for k, _ in info._fields_}
+
+    def close(self):
+        if getattr(self, "handle", None):
+            if getattr(self.ctx, "handle", None):
+                self.ctx.lib.plonk_verifier_destroy(self.handle)
             self.handle = None
 
     def __del__(self):

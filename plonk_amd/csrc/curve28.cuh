@@ -247,6 +247,22 @@ HD G1R g1r_mul_glv(const G1R& p, const uint32_t* k /*8*/) {
   return acc;
 }
 
+// is_on_curve() & is_torsion_free() of an affine point (x, y < 2p): y^2 = x^3 + 4 and [q] P = O (254 doublings + one mixed
+// addition per set bit of q below the top one).  The commit-key check (msm.hip srs_validate_kernel) and the decoding of
+// proof commitments (verify.hip) share it.
+HD bool g1r_on_curve_in_subgroup(const Fp28& x, const Fp28& y) {
+  const Fp28 one = Fp28::one();
+  const Fp28 four = Fp28::add(Fp28::add(one, one), Fp28::add(one, one));
+  const Fp28 rhs = Fp28::add(Fp28::mul(x.sqr(), x), four);          // < 6p
+  if (!Fp28::sub<16>(y.sqr(), rhs).is_zero_mod()) return false;
+  G1R acc = G1R::from_affine(x, y);                                  // top bit of q (bit 254)
+  for (int b = 253; b >= 0; --b) {
+    acc = acc.dbl();
+    if ((FrP::MOD[b >> 5] >> (b & 31)) & 1) acc = acc.add_affine(x, y);
+  }
+  return acc.is_identity();
+}
+
 // affine coordinates (x, y) < 2p of a finite point (safegcd inverse: ~23 k instructions instead of ~300 k)
 HD void g1r_to_affine(const G1R& p, Fp28* x, Fp28* y) {
   const Fp28 inv = fp28_inv_gcd(Fp28::mul(p.ZZ, p.ZZZ));

@@ -165,26 +165,13 @@ __global__ void srs_table_kernel(const G1Affine* __restrict__ pts, G1AffineR* __
 }
 
 // CommitKey::from_raw_var_bytes (key.rs:263-300) validates every decoded point with
-// is_on_curve() & is_torsion_free(); here one lane per point: y^2 = x^3 + 4 and [q]P = O
-// (255 doublings + one mixed addition per set bit of q).  flag |= 1 on any failure.
+// is_on_curve() & is_torsion_free(); here one lane per point (curve28.cuh g1r_on_curve_in_subgroup).
+// flag |= 1 on any failure.
 __global__ void srs_validate_kernel(const G1Affine* __restrict__ pts, uint64_t n, int* __restrict__ flag) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const G1Affine a = ld_aff(pts + i);
-  const Fp28 x = Fp28::from_fp(a.x), y = Fp28::from_fp(a.y);
-  const Fp28 one = Fp28::one();
-  const Fp28 four = Fp28::add(Fp28::add(one, one), Fp28::add(one, one));
-  const Fp28 rhs = Fp28::add(Fp28::mul(x.sqr(), x), four);          // < 6p
-  bool ok = Fp28::sub<16>(y.sqr(), rhs).is_zero_mod();
-  if (ok) {
-    G1R acc = G1R::from_affine(x, y);                                // top bit of q (bit 254)
-    for (int b = 253; b >= 0; --b) {
-      acc = acc.dbl();
-      if ((FrP::MOD[b >> 5] >> (b & 31)) & 1) acc = acc.add_affine(x, y);
-    }
-    ok = acc.is_identity();
-  }
-  if (!ok) atomicOr(flag, 1);
+  if (!g1r_on_curve_in_subgroup(Fp28::from_fp(a.x), Fp28::from_fp(a.y))) atomicOr(flag, 1);
 }
 
 __device__ __forceinline__ G1Affine g1_generator() {

@@ -27,13 +27,6 @@ static_assert(plonk::WQS_RANGE == plonk::QS_RANGE && plonk::WQS_LOGIC == plonk::
 
 namespace plonk {
 
-// transcript labels in VerifierKey::seed_transcript order (widget.rs:229-254)
-static const int VK_ORDER[15] = {P_QM, P_QL, P_QR, P_QO, P_QC, P_QF, P_QARITH, P_QRANGE, P_QLOGIC,
-                                 P_QVAR, P_QFIXED, P_S1, P_S2, P_S3, P_S4};
-static const char* VK_LABEL[15] = {"q_m", "q_l", "q_r", "q_o", "q_c", "q_f", "q_arith", "q_range", "q_logic",
-                                   "q_variable_group_add", "q_fixed_group_add",
-                                   "s_sigma_1", "s_sigma_2", "s_sigma_3", "s_sigma_4"};
-
 struct Prover {
   Ctx* c = nullptr;
   int transcript_version = 3;      // PlonkVersion of the transcript seeding: 3 (Transcript::base_v3) or the legacy 2 (plonk_prover_set_version)
@@ -331,6 +324,7 @@ static FinishPool* finish_pool_of(Ctx* c) {
   if (!c->finish_pool && c->cfg.host_threads > 0) c->finish_pool = new FinishPool(c->cfg.host_threads);
   return (FinishPool*)c->finish_pool;
 }
+FinishPool* finish_pool_acquire(Ctx* c) { return finish_pool_of(c); }   // verify.hip: the transcript replays of a batch
 void finish_pool_release(Ctx* c) {
   delete (FinishPool*)c->finish_pool;
   c->finish_pool = nullptr;
@@ -777,11 +771,7 @@ static int prover_build(Ctx* c, const plonk_prover_desc* d, const CircuitSrc* ci
 // transcript_for_version(V3) = Transcript::base_v3 (transcript.rs:131-145) + VerifierKey::seed_transcript
 // (widget.rs:218-258) + the public inputs (prover.rs:440-442)
 static void seed_transcript(Transcript& tr, const Prover* p, const Fr* pi_val, uint64_t pi_count) {
-  tr.circuit_domain_sep(p->constraints);
-  // PlonkVersion::V2 (prove_with_version, prover.rs:365-413; feature `legacy-proving`): Transcript::base + seed_transcript_legacy
-  // (transcript.rs:110-129, widget.rs:224-228,260-265) bind the LABEL s_sigma_4 to the commitment of s_sigma_1; nothing else differs
-  for (int k = 0; k < 15; ++k) tr.append_commitment(VK_LABEL[k], p->vk[(p->transcript_version == 2 && k == 14) ? P_S1 : VK_ORDER[k]]);
-  tr.circuit_domain_sep(p->constraints);   // vk.n == constraints (compiler.rs:279)
+  seed_transcript_vk(tr, p->constraints, p->vk, p->transcript_version);   // widgets.hpp (V2: prove_with_version, prover.rs:365-413)
   for (uint64_t i = 0; i < pi_count; ++i) tr.append_scalar("pi", pi_val[i]);
 }
 // prover.rs:623-632,650-658

@@ -4,6 +4,7 @@
 // the CPU test harness (tests/csrc/host_arith.cpp).
 #pragma once
 #include "field.cuh"
+#include "transcript.hpp"
 
 namespace plonk {
 
@@ -17,6 +18,22 @@ enum PolyId {
 };
 
 static inline Fr fr_small(uint64_t v) { return Fr::from_u64(v); }
+
+// transcript labels in VerifierKey::seed_transcript order (widget.rs:229-254): the prover's seeding and the verifier's replay
+static const int VK_ORDER[15] = {P_QM, P_QL, P_QR, P_QO, P_QC, P_QF, P_QARITH, P_QRANGE, P_QLOGIC,
+                                 P_QVAR, P_QFIXED, P_S1, P_S2, P_S3, P_S4};
+static const char* VK_LABEL[15] = {"q_m", "q_l", "q_r", "q_o", "q_c", "q_f", "q_arith", "q_range", "q_logic",
+                                   "q_variable_group_add", "q_fixed_group_add",
+                                   "s_sigma_1", "s_sigma_2", "s_sigma_3", "s_sigma_4"};
+// transcript_for_version (transcript.rs:110-145) + VerifierKey::seed_transcript (widget.rs:218-258) for the 15 compressed
+// commitments in PolyId order.  PlonkVersion::V2 (Transcript::base + seed_transcript_legacy, feature `legacy-proving`) binds
+// the LABEL s_sigma_4 to the commitment of s_sigma_1; nothing else differs.  vk.n == constraints (compiler.rs:279).
+// The prover (prover.hip) and the verifier (verify_core.hpp) seed through this one function.
+static void seed_transcript_vk(Transcript& tr, uint64_t constraints, const uint8_t (*vk)[48], int version) {
+  tr.circuit_domain_sep(constraints);
+  for (int k = 0; k < 15; ++k) tr.append_commitment(VK_LABEL[k], vk[(version == 2 && k == 14) ? P_S1 : VK_ORDER[k]]);
+  tr.circuit_domain_sep(constraints);
+}
 
 // Truncated power series mod X^7 over Fr: the widget formulas below are evaluated in this ring
 // to obtain the 7 lowest coefficients of the quotient numerator (quotient_low()).

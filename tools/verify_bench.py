@@ -1,0 +1,95 @@
+"""Batch proof verification throughput (plonk_verify, plonk_amd/csrc/verify.hip): proofs of one 2^12-gate circuit with
+four public inputs, made once on the GPU with different blinders, verified in batches of K.  One JSON line per K: wall time of
+the call (it returns after its last device synchronisation), proofs per second, the plonk_verifier_last phase times,
+msm_terms and pairing_checks; then one run with one bad proof per 1024.
+
+    python tools/verify_bench.py [--log-n 12] [--ks 1,64,1024,8192] [--reps 3]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+
+def circuit(ngates, npi, seed=4242):
+    """random arithmetic gates with `npi` public inputs (append_public, composer.rs:377-389), ngates rows in all"""
+    import random
+    from oracle import plonk as O
+    from oracle.bls12_381 import Q
+    r = random.Random(seed)
+    c = O.Composer()
+    ws = [c.append_witness(r.randrange(Q)) for _ in range(4)]
+    for _ in range(npi):
+        v = r.randrange(Q)
+        c.append_gate(O.Gate(a=c.append_witness(v), q_l=Q - 1, pi=v))
+    while len(c.constraints) < ngates:
+        ws.append(c.gate_mul(r.choice(ws), r.choice(ws), r.choice(ws), q_m=r.randrange(1, Q), q_f=1, q_c=r.randrange(Q)))
+        ws = ws[-16:]
+    return c
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--log-n", type=int, default=12)
+    ap.add_argument("--ks", default="1,64,1024,8192")
+    ap.add_argument("--reps", type=int, default=3)
+    args = ap.parse_args()
+    ks = [int(k) for k in args.ks.split(",")]
+    import plonk_amd
+    from oracle import bls12_381 as E
+    from tests import circuits as C
+    import g2_ref as G2
+    tau, g = 0x5EED0000 * 0x9E3779B97F4A7C15 % E.Q, 0xA5A5A5A5DEADBEEF   # circuits.synthetic_srs's defaults
+    ctx = plonk_amd.Context(0)
+    comp = circuit(1 << args.log_n, 4)
+    case = C.compile_fast(comp, b"verify-bench")
+    srs = C.synthetic_srs(case["size"] + 7)
+    ctx.srs_load_bytes(srs, len(srs) // 96)
+    cols = C.circuit_columns(comp)
+    prover = plonk_amd.Prover.compile(ctx, b"verify-bench", cols["selectors"], cols["wires"], cols["witnesses"])
+    opening_key = E.g1_compress(E.g1_mul(E.G1_GEN, g)) + G2.g2_compress(G2.G2_GEN) + G2.g2_compress(G2.g2_mul(G2.G2_GEN, tau))
+    verifier = plonk_amd.Verifier(ctx, prover.verifier_to_bytes(opening_key, case["pi_idx"]))
+    pis = [case["pi"][i] for i in case["pi_idx"]]
+    kmax = max(ks)
+    t0 = time.perf_counter()
+    proofs = [prover.prove_witnesses(cols["values"], case["pi"], C.blinders(k)) for k in range(kmax)]
+    print(json.dumps({"setup": "proofs", "log_n": args.log_n, "public_inputs": len(pis), "count": kmax,
+                      "seconds": round(time.perf_counter() - t0, 2)}), flush=True)
+
+    def run(batch, label):
+        best = None
+        for _ in range(args.reps):
+            t = time.perf_counter()
+            verdicts = verifier.verify_batch(batch, [pis] * len(batch))
+            ms = (time.perf_counter() - t) * 1e3
+            info = verifier.last()
+            if best is None or ms < best[0]:
+                best = (ms, info, verdicts)
+        ms, info, verdicts = best
+        out = {"run": label, "K": len(batch), "wall_ms": round(ms, 3), "proofs_per_s": round(len(batch) / ms * 1e3, 1),
+               "rejected": sum(v != 0 for v in verdicts)}
+        out.update({k: (round(v, 3) if isinstance(v, float) else v) for k, v in info.items()})
+        print(json.dumps(out), flush=True)
+
+    for k in ks:
+        run(proofs[:k], "valid")
+    bad = list(proofs[:kmax])
+    for i in range(0, kmax, 1024):
+        j = i + 517 % min(1024, kmax - i)
+        b = bytearray(bad[j])
+        v = (int.from_bytes(b[528:560], "little") + 1) % E.Q
+        b[528:560] = v.to_bytes(32, "little")
+        bad[j] = bytes(b)
+    run(bad, "one bad per 1024")
+    verifier.close()
+    prover.close()
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()
