@@ -470,6 +470,34 @@ int plonk_verifier_set_version(plonk_verifier* v, int version);
 int plonk_verify(plonk_verifier* v, const uint8_t* proofs, const uint64_t* pi, uint64_t pi_count, uint64_t count,
                  int32_t* verdicts);
 int plonk_verifier_last(plonk_verifier* v, plonk_verify_info* out);
+/* plonk_verify_mixed checks `count` proofs of several circuits that share one opening key (circuits compiled from one
+ * PublicParameters) in one aggregated check.  Proof k (1008 bytes, Proof::to_bytes) belongs to verifiers[circuit[k]];
+ * each verifier's current version applies to its proofs, and one handle may appear in `verifiers` more than once (each
+ * position is a slot of its own).  pi: the proofs' public inputs concatenated, proof by proof, each in its verifier's count
+ * and index order (Montgomery limbs, like plonk_verify); pi_total: the number of Fr values in pi.  verdicts (count entries;
+ * may be NULL when count == 1) and the return value as plonk_verify: each verdict equals what a count == 1 plonk_verify
+ * of that proof with its own verifier returns, up to the aggregation's soundness error.  PLONK_ERR_ARG, with a text that
+ * names the check, for a NULL argument, nverifiers == 0, count == 0 or count > 2^24, circuit[k] >= nverifiers, pi_total
+ * not the sum of the proofs' public-input counts, verifiers on different contexts, or verifiers whose 240-byte opening
+ * keys (g, h, x_h) differ (mixing setups is not supported).
+ * Every check e(-L_k, x_h) e(R_k, h) == 1 shares (g, h, x_h), so the checks fold with the powers 1, rho, rho^2, ... of
+ * one challenge: one MSM over the 15 VK points of every circuit the batch uses (each with its circuit's summed scalars),
+ * g and 11 commitments per proof (13 K + 15 C + 1 terms, C the circuits used), and ONE pairing check; the probability
+ * that a batch with a bad proof passes is at most K / q per check, as for plonk_verify.  The transcripts replay on the
+ * device (one lane per proof, from its circuit's transcript seeded once by the host); each proof's replay draws
+ * challenge_bytes("batch digest", 32) after u, a digest of everything that proof's check depends on.  rho is
+ * challenge_scalar("rho") of a Merlin transcript "plonk-batch-verify-mixed-v1" that absorbs append_u64("batch length", m);
+ * for every slot the (sub-)batch uses, ascending, append_u64("slot", s) and append_message("circuit", verifier digest);
+ * for every proof in order append_u64("circuit", slot) and append_message("proof", proof digest).  The verifier digest
+ * is challenge_bytes("circuit digest", 32) of a transcript "plonk-verifier-digest-v1" over append_message("label"),
+ * append_u64("version"), append_u64("size"), append_u64("constraints"), 15 x append_message("vk", commitment)
+ * (VerifierKey::to_bytes order), append_message("opening key", 240 bytes), append_u64("public inputs", count) and
+ * append_u64("public input index", i) per index.  With m = 1 the weight is 1.  A failing batch is bisected like
+ * plonk_verify's, a fresh rho per sub-batch: b bad proofs cost O(b log K) further checks, an all-bad batch 2K - 1.  The
+ * call holds the context for its whole duration, writes nothing into any verifier's plonk_verifier_last and fills `info`
+ * (may be NULL) the same way instead; ms_scalars covers the replay kernel, the rho derivation and the weighting. */
+int plonk_verify_mixed(plonk_verifier* const* verifiers, uint32_t nverifiers, const uint32_t* circuit, const uint8_t* proofs,
+                       const uint64_t* pi, uint64_t pi_total, uint64_t count, int32_t* verdicts, plonk_verify_info* info);
 typedef struct {
   uint64_t size, constraints;
   uint64_t label_off, label_len;

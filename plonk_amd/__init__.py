@@ -60,6 +60,7 @@ EXPORTS = [
     "plonk_compile", "plonk_prover_prove_witnesses", "plonk_prover_to_bytes", "plonk_verifier_to_bytes",
     "plonk_public_parameters_check", "plonk_srs_load_public_parameters",
     "plonk_verifier_from_bytes", "plonk_verifier_destroy", "plonk_verifier_set_version", "plonk_verify", "plonk_verifier_last",
+    "plonk_verify_mixed",
 ]
 
 POLY_ORDER = ["q_m", "q_l", "q_r", "q_o", "q_f", "q_c", "q_arith", "q_range", "q_logic",
@@ -246,6 +247,8 @@ def load_library() -> ctypes.CDLL:
     lib.plonk_verify.argtypes = [vp, vp, vp, u64, u64, vp]
     lib.plonk_verifier_last.argtypes = [vp, vp]
     lib.plonk_test_verify_msm.argtypes = [vp, vp, vp, u64, vp]   # test hook of verify.hip, not in the header
+    lib.plonk_verify_mixed.argtypes = [vp, u32, vp, vp, vp, u64, u64, vp, vp]
+    lib.plonk_test_verify_replay.argtypes = [vp, u32, vp, vp, vp, u64, u64, vp, vp, vp]   # test hook of verify.hip
     lib.plonk_host_alloc.argtypes = [u64, ctypes.POINTER(vp)]
     lib.plonk_host_free.argtypes = [vp]
     lib.plonk_comm_unique_id.argtypes = [vp]
@@ -526,6 +529,19 @@ class Context:
         out = ctypes.create_string_buffer(97)
         self._check(self.lib.plonk_test_verify_msm(self.handle, comp, sc, len(points), out))
         return g1_from_raw97(out.raw)
+
+    def _verify_replay(self, items):
+        """TEST HOOK: the device replay of plonk_verify_mixed (verify.hip) on items [(Verifier, proof, public_inputs)];
+        returns per proof (status, 28 scalars as Montgomery bytes, 32-byte digest).  Not part of the C API."""
+        args = _mixed_args(items)
+        count = len(items)
+        status = (ctypes.c_int32 * count)()
+        scalars = ctypes.create_string_buffer(28 * 32 * count)
+        digests = ctypes.create_string_buffer(32 * count)
+        self._check(self.lib.plonk_test_verify_replay(*args, status, scalars, digests))
+        raw = scalars.raw
+        return [(int(status[k]), [raw[896 * k + 32 * j:896 * k + 32 * j + 32] for j in range(28)],
+                 digests.raw[32 * k:32 * k + 32]) for k in range(count)]
 
     def alloc(self, nbytes: int) -> DeviceBuffer:
         return DeviceBuffer(self, nbytes)
@@ -940,3 +956,42 @@ class Verifier:
             self.close()
         except Exception:
             pass
+
+
+def _mixed_args(items):
+    """(verifiers array, nverifiers, circuit, proofs, pi, pi_total, count) of plonk_verify_mixed: one slot per distinct
+    Verifier object, in the order of first appearance"""
+    items = list(items)
+    if not items:
+        raise ValueError("empty batch")
+    slots, pos = [], {}
+    circuit, proofs, pis = [], [], []
+    for v, proof, public_inputs in items:
+        if id(v) not in pos:
+            pos[id(v)] = len(slots)
+            slots.append(v)
+        if len(proof) != 1008:
+            raise ValueError("a proof is 1008 bytes")
+        circuit.append(pos[id(v)])
+        proofs.append(bytes(proof))
+        pis.extend(public_inputs)
+    handles = (ctypes.c_void_p * len(slots))(*[v.handle for v in slots])
+    circ = (ctypes.c_uint32 * len(circuit))(*circuit)
+    pi = fr_to_bytes_mont(pis) if pis else None
+    return handles, len(slots), circ, b"".join(proofs), pi, len(pis), len(items)
+
+
+def verify_mixed(items):
+    """plonk_verify_mixed: proofs of several circuits that share one opening key, in one aggregated pairing check.
+    items: [(Verifier, proof_bytes, public_inputs)], public_inputs in that verifier's index order.  Returns (verdicts,
+    info): per-proof codes as Verifier.verify_batch (0 = valid, -12 PLONK_ERR_VERIFY, -9 PLONK_ERR_DATA, -10
+    PLONK_ERR_POINT) and the plonk_verify_info of the call as a dict.  Raises on argument errors (PLONK_ERR_ARG)."""
+    items = list(items)
+    args = _mixed_args(items)
+    ctx = items[0][0].ctx
+    verdicts = (ctypes.c_int32 * len(items))()
+    info = _VerifyInfo()
+    rc = ctx.lib.plonk_verify_mixed(*args, verdicts, ctypes.byref(info))
+    if rc not in (PLONK_OK, -12):
+        ctx._check(rc)
+    return [int(x) for x in verdicts], {k: getattr(info, k) for k, _ in info._fields_}

@@ -420,6 +420,7 @@ void plonk_ctx_destroy(plonk_ctx* ctx) {
     return;
   }
   (void)hipStreamSynchronize(c.stream);
+  verify_ws_release(&c);
   for (auto& kv : c.ntt_tables) {
     NttTables* t = kv.second;
     (void)hipFree(t->tw_lo); (void)hipFree(t->tw_hi); (void)hipFree(t->tw_lo_scaled);

@@ -32,6 +32,7 @@ struct Ctx;
 // refusal with PLONK_ERR_STATE), and the destroy paths ask ctx_abandon() whether the device side has to be leaked.
 int ctx_refuse_poisoned(const char* api_fn);          // capi.hip: sets the last-error text, returns PLONK_ERR_STATE
 void finish_pool_release(Ctx* c);                     // prover.hip: joins and deletes the context's host helper threads
+void verify_ws_release(Ctx* c);                       // verify.hip: frees plonk_verify_mixed's device workspace
 bool ctx_abandon(Ctx* c);                             // capi.hip: poisoned AND the streams did not drain within a bounded poll
 #define CTX_ENTER(C, FN)                      \
   std::lock_guard<std::mutex> lk((C).mu);     \
@@ -232,6 +233,7 @@ struct Ctx {
   bool comm_poisoned = false;      // comm_sync timed out and the stream never drained: sharded proofs and new communicators are refused
   bool comm_loopback = false;      // measurement only: collectives return the rank's own contribution (plonk_comm_measure_loopback)
   void* finish_pool = nullptr;     // FinishPool* (finish_pool.hpp), created by the first commitment group of a prover (prover.hip), freed by finish_pool_release
+  void* verify_ws = nullptr;       // MixedWork* (verify.hip): plonk_verify_mixed's grow-only device workspace, freed by verify_ws_release
   // instrumentation: hipEvent pairs around the dominant kernels
   bool profile = false;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;

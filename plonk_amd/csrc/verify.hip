@@ -7,6 +7,9 @@
 //                               threads (verify_core.hpp), aggregate the K checks with powers of a batch challenge rho,
 //                               one grouped MSM for L and R (device), one two-pair pairing check (host); a failing batch is
 //                               bisected with a fresh challenge per sub-batch, so b bad proofs cost O(b log K) checks.
+//   plonk_verify_mixed          the same check for proofs of several circuits that share one opening key: the transcript
+//                               replays run on the device (replay kernel below, the shared verify_core.hpp code), rho is
+//                               drawn from 32-byte digests, the weighting and the per-circuit VK sums stay on the device.
 //
 // Device work:
 //   verify_decode_kernel   one lane per compressed commitment: g1_decompress48 + g1r_on_curve_in_subgroup
@@ -15,6 +18,13 @@
 //                          the host adds the per-block partial sums.  Every addition is G1R::add, the general XYZZ law
 //                          that doubles equal points and cancels opposite ones: adversarial commitments (duplicates,
 //                          P and -P, the identity) and scalars 0 / q - 1 need no special case.
+//   verify_gather_kernel   plonk_verify_mixed: the 11 commitments of every proof out of the uploaded proofs, for decode
+//   verify_replay_kernel   plonk_verify_mixed: one lane per proof, replay_scalars (verify_core.hpp) from its circuit's
+//                          pre-seeded transcript -> status, the 28 scalars of ProofScalars and the 32-byte proof digest
+//   verify_weight_kernel   one lane per proof of a sub-batch: rho^i, the 13 weighted proof terms of the MSM, and the 16
+//                          weighted VK / g scalars in a column per scalar for
+//   verify_vksum_kernel    one block per (circuit of the sub-batch, VK scalar): the segmented sum over that circuit's proofs
+//   verify_gsum_kernel     one block: the g scalar summed over the circuits
 // The SRS MSM of msm.hip is not used: its speed comes from per-key tables of row multiples, which would cost more to build
 // for one call's points than the sum itself.
 #include <hip/hip_runtime.h>
@@ -36,6 +46,12 @@
 #include "verify_core.hpp"
 
 #define PTRY_V(expr) do { int _rc = (expr); if (_rc) return _rc; } while (0)
+
+namespace plonk { struct Verifier; }
+struct plonk_verifier {
+  plonk::Verifier* v;
+  plonk_ctx* ctx;
+};
 
 namespace plonk {
 
@@ -96,12 +112,143 @@ __global__ void __launch_bounds__(VMSM_LANES) verify_msm_kernel(const uint32_t* 
   if (!lane) part[g * gridDim.x + blockIdx.x] = sh[0].to_g1();
 }
 
+// ---- plonk_verify_mixed: device replay and weighting ----------------------------------------------------------------
+// One circuit of a mixed call on the device: its constants and its transcript after the label and seed_transcript_vk
+// (identical for every proof of the circuit, so the host seeds it once per slot).
+struct MixedSlot {
+  SlotConst k;
+  Transcript tr;
+};
+
+constexpr uint32_t PROOF_COMM_WORDS = PC_COUNT * 48 / 4;   // 132 words of commitments at the start of Proof::to_bytes
+
+// comp[k][0, 528) = proofs[k][0, 528): the layout verify_decode_kernel reads (1008 and 528 are multiples of 4)
+__global__ void __launch_bounds__(256) verify_gather_kernel(const uint32_t* __restrict__ proofs, uint64_t count,
+                                                            uint32_t* __restrict__ comp) {
+  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= count * PROOF_COMM_WORDS) return;
+  const uint64_t k = t / PROOF_COMM_WORDS, w = t - k * PROOF_COMM_WORDS;
+  comp[t] = proofs[(PROOF_BYTES / 4) * k + w];
+}
+
+// one lane per proof: a proof with a commitment that failed to decode gets VS_POINT, every other one is replayed from its
+// circuit's seeded transcript.  kind: decode statuses of the combined point table, the proofs' 11 each from pt_proof0.
+__global__ void __launch_bounds__(64) verify_replay_kernel(const uint8_t* __restrict__ proofs, const uint32_t* __restrict__ slot,
+                                                           const uint64_t* __restrict__ pi_off, const Fr* __restrict__ pi,
+                                                           const MixedSlot* __restrict__ slots, const Fr* __restrict__ pi_root,
+                                                           const int32_t* __restrict__ kind, uint32_t pt_proof0, uint32_t count,
+                                                           int32_t* __restrict__ status, ProofScalars* __restrict__ ps,
+                                                           uint8_t* __restrict__ digest) {
+  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= count) return;
+  bool bad = false;
+#pragma unroll
+  for (int c = 0; c < PC_COUNT; ++c) bad |= kind[pt_proof0 + (uint64_t)PC_COUNT * k + c] == VDEC_BAD;
+  if (bad) {
+    ps[k].status = VS_POINT;
+    status[k] = VS_POINT;
+    memset(digest + 32ull * k, 0, 32);
+    return;
+  }
+  const MixedSlot& s = slots[slot[k]];
+  Transcript tr = s.tr;
+  replay_scalars(s.k, pi_root + s.k.pi_root_off, tr, proofs + PROOF_BYTES * k, pi + pi_off[k], ps + k, digest + 32ull * k);
+  status[k] = ps[k].status;
+}
+
+__device__ __forceinline__ void put_canonical(uint32_t* dst, const Fr& s_mont) {
+  const Fr s = s_mont.from_mont();
+#pragma unroll
+  for (int w = 0; w < 8; ++w) dst[w] = s.l[w];
+}
+
+// One lane per proof of a sub-batch, taken in slot-grouped order: p -> sub-batch position i = order[p], proof which[i],
+// weight rho^i.  Writes the proof's 2 L terms (2i, 2i + 1) and 11 R terms (nL + r0 + 11 i + c) with their point ids, and its
+// 15 weighted VK scalars and g scalar into wv[j][p] (column j, m per column) for the segmented sums.
+__global__ void __launch_bounds__(256) verify_weight_kernel(const uint32_t* __restrict__ which, const uint32_t* __restrict__ order,
+                                                            uint32_t m, Fr rho, const ProofScalars* __restrict__ ps,
+                                                            uint32_t pt_proof0, uint32_t nL, uint32_t r0,
+                                                            uint32_t* __restrict__ sc, uint32_t* __restrict__ ids,
+                                                            Fr* __restrict__ wv) {
+  const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= m) return;
+  const uint32_t i = order[p], k = which[i];
+  const Fr w = rho.pow_u64(i);
+  const ProofScalars& s = ps[k];
+  const uint32_t base = pt_proof0 + PC_COUNT * k;
+  put_canonical(sc + 16ull * i, w);
+  ids[2 * i] = base + PC_WZ;
+  put_canonical(sc + 16ull * i + 8, w * s.u);
+  ids[2 * i + 1] = base + PC_WZW;
+#pragma unroll
+  for (int c = 0; c < PC_COUNT; ++c) {
+    const uint64_t t = (uint64_t)nL + r0 + (uint64_t)PC_COUNT * i + c;
+    put_canonical(sc + 8 * t, w * s.comm[c]);
+    ids[t] = base + c;
+  }
+#pragma unroll
+  for (int j = 0; j < P_COUNT; ++j) wv[(uint64_t)j * m + p] = w * s.vk[j];
+  wv[(uint64_t)P_COUNT * m + p] = w * s.g;
+}
+
+constexpr int VSUM_LANES = 256;
+
+template <int LANES>
+__device__ __forceinline__ Fr block_sum(Fr acc, Fr* sh) {
+  const uint32_t t = threadIdx.x;
+  sh[t] = acc;
+  __syncthreads();
+  for (uint32_t h = LANES / 2; h; h >>= 1) {
+    if (t < h) sh[t] = sh[t] + sh[t + h];
+    __syncthreads();
+  }
+  return sh[0];
+}
+
+// grid (circuits of the sub-batch, 16): block (s, j) sums column j of wv over segment s = positions [seg[s], seg[s + 1])
+// (the proofs of one circuit).  j < 15: the R term nL + 15 s + j with the circuit's VK point j (seg_pt[s] + j); j = 15:
+// the circuit's share of the g scalar, to gpart[s].
+__global__ void __launch_bounds__(VSUM_LANES) verify_vksum_kernel(const Fr* __restrict__ wv, uint32_t m,
+                                                                  const uint32_t* __restrict__ seg,
+                                                                  const uint32_t* __restrict__ seg_pt, uint32_t nL,
+                                                                  uint32_t* __restrict__ sc, uint32_t* __restrict__ ids,
+                                                                  Fr* __restrict__ gpart) {
+  __shared__ Fr sh[VSUM_LANES];
+  const uint32_t s = blockIdx.x, j = blockIdx.y;
+  Fr acc = Fr::zero();
+  for (uint32_t p = seg[s] + threadIdx.x; p < seg[s + 1]; p += VSUM_LANES) acc = acc + wv[(uint64_t)j * m + p];
+  acc = block_sum<VSUM_LANES>(acc, sh);
+  if (threadIdx.x) return;
+  if (j < P_COUNT) {
+    const uint64_t t = (uint64_t)nL + P_COUNT * s + j;
+    put_canonical(sc + 8 * t, acc);
+    ids[t] = seg_pt[s] + j;
+  } else {
+    gpart[s] = acc;
+  }
+}
+
+// one block: the g scalar, summed over the ns circuits' shares, as R term nL + 15 ns with point pt_g
+__global__ void __launch_bounds__(VSUM_LANES) verify_gsum_kernel(const Fr* __restrict__ gpart, uint32_t ns, uint32_t nL,
+                                                                 uint32_t pt_g, uint32_t* __restrict__ sc,
+                                                                 uint32_t* __restrict__ ids) {
+  __shared__ Fr sh[VSUM_LANES];
+  Fr acc = Fr::zero();
+  for (uint32_t s = threadIdx.x; s < ns; s += VSUM_LANES) acc = acc + gpart[s];
+  acc = block_sum<VSUM_LANES>(acc, sh);
+  if (threadIdx.x) return;
+  const uint64_t t = (uint64_t)nL + (uint64_t)P_COUNT * ns;
+  put_canonical(sc + 8 * t, acc);
+  ids[t] = pt_g;
+}
+
 // ---- the verifier object --------------------------------------------------------------------------------------------
 struct Verifier {
   Ctx* c = nullptr;
   VerifierCore core;
   G2Prepared h, x_h;
   uint8_t g48[48];
+  uint8_t opening_key[OPENING_KEY_LEN];   // g || h || x_h as in the blob: plonk_verify_mixed compares and digests them
   // device: points [0, 16) = VK (PolyId order) and g, then 11 per proof of the current call
   G1Affine* pts = nullptr;
   int32_t* kind = nullptr;
@@ -188,21 +335,19 @@ struct BatchState {
   uint32_t checks = 0;
 };
 
-// the two sums of a check on the device: terms [0, nL) (L) and [nL, nL + nR) (R) of the host arrays (canonical scalars,
-// 8 words each; point ids into v->pts); the host adds the per-block partial sums
-static int msm_device(Verifier* v, const uint32_t* sc_host, const uint32_t* id_host, uint64_t nL, uint64_t nR, H1 sums[2]) {
-  Ctx* c = v->c;
+// the two sums of a check from term arrays on the device: terms [0, nL) (L) and [nL, nL + nR) (R) (canonical scalars, 8
+// words each; point ids into pts / kind); the host adds the per-block partial sums
+static int msm_run(Ctx* c, const uint32_t* sc, const uint32_t* ids, uint64_t nL, uint64_t nR, const G1Affine* pts,
+                   const int32_t* kind, G1* part_dev, H1 sums[2]) {
   const uint64_t nmax = nR > nL ? nR : nL;
   uint32_t blocks = (uint32_t)((nmax + 4 * VMSM_LANES - 1) / (4 * VMSM_LANES));   // ~4 terms per lane
   if (blocks > VMSM_MAX_BLOCKS) blocks = VMSM_MAX_BLOCKS;
   if (!blocks) blocks = 1;
-  HIP_TRY(hipMemcpyAsync(v->sc, sc_host, 32 * (nL + nR), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(v->ids, id_host, 4 * (nL + nR), hipMemcpyHostToDevice, c->stream));
-  hipLaunchKernelGGL(verify_msm_kernel, dim3(blocks, 2), dim3(VMSM_LANES), 0, c->stream, v->sc, v->ids, (uint32_t)nL,
-                     (uint32_t)nR, v->pts, v->kind, v->part);
+  hipLaunchKernelGGL(verify_msm_kernel, dim3(blocks, 2), dim3(VMSM_LANES), 0, c->stream, sc, ids, (uint32_t)nL,
+                     (uint32_t)nR, pts, kind, part_dev);
   HIP_TRY(hipGetLastError());
   std::vector<G1> part(2 * blocks);
-  HIP_TRY(hipMemcpyAsync(part.data(), v->part, sizeof(G1) * 2 * blocks, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(part.data(), part_dev, sizeof(G1) * 2 * blocks, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   for (int g = 0; g < 2; ++g) {
     memset(&sums[g], 0, sizeof(H1));
@@ -215,6 +360,26 @@ static int msm_device(Verifier* v, const uint32_t* sc_host, const uint32_t* id_h
     }
   }
   return PLONK_OK;
+}
+
+// the same from host term arrays (plonk_verify): uploaded to the verifier's buffers first
+static int msm_device(Verifier* v, const uint32_t* sc_host, const uint32_t* id_host, uint64_t nL, uint64_t nR, H1 sums[2]) {
+  Ctx* c = v->c;
+  HIP_TRY(hipMemcpyAsync(v->sc, sc_host, 32 * (nL + nR), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(v->ids, id_host, 4 * (nL + nR), hipMemcpyHostToDevice, c->stream));
+  return msm_run(c, v->sc, v->ids, nL, nR, v->pts, v->kind, v->part, sums);
+}
+
+// e(-L, x_h) e(R, h) == 1 for the two sums of a check
+static bool pairing_check(const H1 sums[2], const G2Prepared& x_h, const G2Prepared& h) {
+  G1Aff64 pairs[2] = {xyzz_to_aff(sums[0]), xyzz_to_aff(sums[1])};
+  if (!pairs[0].inf) {   // -L
+    Fp64 z;
+    memset(&z, 0, sizeof z);
+    pairs[0].y = fp64_sub(z, pairs[0].y);
+  }
+  const G2Prepared* qs[2] = {&x_h, &h};
+  return f12_is_one(final_exponentiation(multi_miller_loop(pairs, qs, 2)));
 }
 
 // e(-L, x_h) e(R, h) == 1 for the proofs `which` (all with status VS_OK), weighted by rho^i
@@ -255,14 +420,7 @@ static int batch_check(BatchState& b, const uint32_t* which, size_t m, bool* ok)
   H1 sums[2];
   PTRY_V(msm_device(v, b.sc_host.data(), b.id_host.data(), nL, nR, sums));
   const auto t1 = std::chrono::steady_clock::now();
-  G1Aff64 pairs[2] = {xyzz_to_aff(sums[0]), xyzz_to_aff(sums[1])};
-  if (!pairs[0].inf) {   // -L
-    Fp64 z;
-    memset(&z, 0, sizeof z);
-    pairs[0].y = fp64_sub(z, pairs[0].y);
-  }
-  const G2Prepared* qs[2] = {&v->x_h, &v->h};
-  *ok = f12_is_one(final_exponentiation(multi_miller_loop(pairs, qs, 2)));
+  *ok = pairing_check(sums, v->x_h, v->h);
   const auto t2 = std::chrono::steady_clock::now();
   if (!b.checks) b.first_terms = nL + nR;
   ++b.checks;
@@ -303,14 +461,264 @@ static void replay_task(void* arg, int index) {
   }
 }
 
+// ---- plonk_verify_mixed: the host side --------------------------------------------------------------------------------
+// The context's grow-only workspace of mixed calls (Ctx::verify_ws): a call whose sizes fit an earlier one allocates nothing.
+struct MixedWork {
+  enum { PTS, KIND, COMP, PROOFS, SLOT, PI_OFF, PI, SLOTS, PI_ROOT, STATUS, SCALARS, DIGEST, WHICH, ORDER, SEG, SEG_PT,
+         WV, GPART, SC, IDS, PART, NBUF };
+  void* p[NBUF] = {};
+  uint64_t cap[NBUF] = {};
+  ~MixedWork() {
+    for (int i = 0; i < NBUF; ++i) (void)hipFree(p[i]);
+  }
+  int need(int i, uint64_t bytes) {
+    if (bytes <= cap[i]) return PLONK_OK;
+    (void)hipFree(p[i]);
+    p[i] = nullptr;
+    cap[i] = 0;
+    HIP_TRY(hipMalloc(&p[i], bytes));
+    cap[i] = bytes;
+    return PLONK_OK;
+  }
+  template <class T>
+  T* at(int i) const { return (T*)p[i]; }
+};
+
+void verify_ws_release(Ctx* c) {
+  delete (MixedWork*)c->verify_ws;
+  c->verify_ws = nullptr;
+}
+
+// one plonk_verify_mixed call after its replay: what the checks and the bisection need
+struct MixedState {
+  Ctx* c;
+  MixedWork* w;
+  const uint32_t* circuit;            // per proof: its slot
+  std::vector<uint32_t> dense;        // per proof: the slot's position among the used slots
+  std::vector<uint32_t> used;         // the slots some proof references, ascending
+  std::vector<uint8_t> slot_digest;   // 32 bytes per slot (verifier digests; used slots only)
+  std::vector<int32_t> status;        // per proof (VerifyStatus)
+  std::vector<uint8_t> digest;        // 32 bytes per proof
+  const G2Prepared *h = nullptr, *x_h = nullptr;
+  uint32_t pt_g = 0, pt_proof0 = 0;   // combined table: [15 per used slot | g | 11 per proof]
+  double ms_decode = 0, ms_replay = 0, ms_weight = 0, ms_msm = 0, ms_pairing = 0;
+  uint64_t first_terms = 0;
+  uint32_t checks = 0;
+  // per check (host staging of the small index arrays)
+  std::vector<uint32_t> order, seg, seg_pt, sub_slots, cnt;
+};
+
+static double ms_since(std::chrono::steady_clock::time_point t) {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
+}
+
+// Everything up to the checks: the combined point table (the verifiers' decoded VK points and g copied, the proofs'
+// commitments decoded), the per-slot constants, the replay kernel; statuses and digests back to the host.
+static int mixed_front(MixedState& b, plonk_verifier* const* verifiers, uint32_t nverifiers, const uint32_t* circuit,
+                       const uint8_t* proofs, const uint64_t* pi, uint64_t pi_total, uint64_t count) {
+  Ctx* c = b.c;
+  if (!c->verify_ws) c->verify_ws = new MixedWork();
+  MixedWork& w = *(MixedWork*)c->verify_ws;
+  b.w = &w;
+  b.circuit = circuit;
+  std::vector<uint32_t> pos(nverifiers, UINT32_MAX);
+  for (uint64_t k = 0; k < count; ++k) pos[circuit[k]] = 0;
+  for (uint32_t s = 0; s < nverifiers; ++s)
+    if (pos[s] == 0) { pos[s] = (uint32_t)b.used.size(); b.used.push_back(s); }
+  const uint64_t nu = b.used.size();
+  b.dense.resize(count);
+  for (uint64_t k = 0; k < count; ++k) b.dense[k] = pos[circuit[k]];
+  b.pt_g = (uint32_t)(P_COUNT * nu);
+  b.pt_proof0 = b.pt_g + 1;
+  const uint64_t npts = b.pt_proof0 + PC_COUNT * count, nterms = 13 * count + P_COUNT * nu + 1;
+  // the slots' constants, seeded transcripts and public-input roots; the verifier digests
+  std::vector<MixedSlot> slots;
+  std::vector<Fr> roots;
+  b.slot_digest.assign(32ull * nverifiers, 0);
+  for (uint64_t u = 0; u < nu; ++u) {
+    const Verifier* v = verifiers[b.used[u]]->v;
+    slots.push_back(MixedSlot{slot_const(v->core, roots.size()), seeded_transcript(v->core)});
+    roots.insert(roots.end(), v->core.pi_root.begin(), v->core.pi_root.end());
+    verifier_digest(v->core, v->opening_key, b.slot_digest.data() + 32ull * b.used[u]);
+  }
+  std::vector<uint64_t> pi_off(count);
+  uint64_t off = 0;
+  for (uint64_t k = 0; k < count; ++k) {
+    pi_off[k] = off;
+    off += verifiers[circuit[k]]->v->core.pi_idx.size();
+  }
+  PTRY_V(w.need(MixedWork::PTS, sizeof(G1Affine) * npts));
+  PTRY_V(w.need(MixedWork::KIND, 4 * npts));
+  PTRY_V(w.need(MixedWork::COMP, 48ull * PC_COUNT * count));
+  PTRY_V(w.need(MixedWork::PROOFS, PROOF_BYTES * count));
+  PTRY_V(w.need(MixedWork::SLOT, 4 * count));
+  PTRY_V(w.need(MixedWork::PI_OFF, 8 * count));
+  PTRY_V(w.need(MixedWork::PI, 32 * (pi_total ? pi_total : 1)));
+  PTRY_V(w.need(MixedWork::SLOTS, sizeof(MixedSlot) * nu));
+  PTRY_V(w.need(MixedWork::PI_ROOT, 32 * (roots.empty() ? 1 : roots.size())));
+  PTRY_V(w.need(MixedWork::STATUS, 4 * count));
+  PTRY_V(w.need(MixedWork::SCALARS, sizeof(ProofScalars) * count));
+  PTRY_V(w.need(MixedWork::DIGEST, 32 * count));
+  PTRY_V(w.need(MixedWork::WHICH, 4 * count));
+  PTRY_V(w.need(MixedWork::ORDER, 4 * count));
+  PTRY_V(w.need(MixedWork::SEG, 4 * (nu + 1)));
+  PTRY_V(w.need(MixedWork::SEG_PT, 4 * nu));
+  PTRY_V(w.need(MixedWork::WV, 32ull * (P_COUNT + 1) * count));
+  PTRY_V(w.need(MixedWork::GPART, 32 * nu));
+  PTRY_V(w.need(MixedWork::SC, 32 * nterms));
+  PTRY_V(w.need(MixedWork::IDS, 4 * nterms));
+  PTRY_V(w.need(MixedWork::PART, sizeof(G1) * 2 * VMSM_MAX_BLOCKS));
+  const hipStream_t st = c->stream;
+  const auto t0 = std::chrono::steady_clock::now();
+  // decode: the verifiers' VK points and g device to device, the proofs' commitments through verify_decode_kernel
+  G1Affine* pts = w.at<G1Affine>(MixedWork::PTS);
+  int32_t* kind = w.at<int32_t>(MixedWork::KIND);
+  for (uint64_t u = 0; u < nu; ++u) {
+    const Verifier* v = verifiers[b.used[u]]->v;
+    HIP_TRY(hipMemcpyAsync(pts + P_COUNT * u, v->pts, sizeof(G1Affine) * P_COUNT, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(kind + P_COUNT * u, v->kind, 4 * P_COUNT, hipMemcpyDeviceToDevice, st));
+  }
+  const Verifier* v0 = verifiers[b.used[0]]->v;
+  HIP_TRY(hipMemcpyAsync(pts + b.pt_g, v0->pts + P_COUNT, sizeof(G1Affine), hipMemcpyDeviceToDevice, st));
+  HIP_TRY(hipMemcpyAsync(kind + b.pt_g, v0->kind + P_COUNT, 4, hipMemcpyDeviceToDevice, st));
+  HIP_TRY(hipMemcpyAsync(w.p[MixedWork::PROOFS], proofs, PROOF_BYTES * count, hipMemcpyHostToDevice, st));
+  const uint64_t words = PROOF_COMM_WORDS * count, ncomp = PC_COUNT * count;
+  hipLaunchKernelGGL(verify_gather_kernel, dim3((uint32_t)((words + 255) / 256)), dim3(256), 0, st,
+                     w.at<const uint32_t>(MixedWork::PROOFS), count, w.at<uint32_t>(MixedWork::COMP));
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(verify_decode_kernel, dim3((uint32_t)((ncomp + 63) / 64)), dim3(64), 0, st, w.at<const uint8_t>(MixedWork::COMP),
+                     (uint32_t)ncomp, pts + b.pt_proof0, kind + b.pt_proof0);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(st));
+  b.ms_decode = ms_since(t0);
+  // replay
+  const auto t1 = std::chrono::steady_clock::now();
+  HIP_TRY(hipMemcpyAsync(w.p[MixedWork::SLOT], b.dense.data(), 4 * count, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(w.p[MixedWork::PI_OFF], pi_off.data(), 8 * count, hipMemcpyHostToDevice, st));
+  if (pi_total) HIP_TRY(hipMemcpyAsync(w.p[MixedWork::PI], pi, 32 * pi_total, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(w.p[MixedWork::SLOTS], slots.data(), sizeof(MixedSlot) * nu, hipMemcpyHostToDevice, st));
+  if (!roots.empty()) HIP_TRY(hipMemcpyAsync(w.p[MixedWork::PI_ROOT], roots.data(), 32 * roots.size(), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(verify_replay_kernel, dim3((uint32_t)((count + 63) / 64)), dim3(64), 0, st, w.at<const uint8_t>(MixedWork::PROOFS),
+                     w.at<const uint32_t>(MixedWork::SLOT), w.at<const uint64_t>(MixedWork::PI_OFF), w.at<const Fr>(MixedWork::PI),
+                     w.at<const MixedSlot>(MixedWork::SLOTS), w.at<const Fr>(MixedWork::PI_ROOT), kind, b.pt_proof0,
+                     (uint32_t)count, w.at<int32_t>(MixedWork::STATUS), w.at<ProofScalars>(MixedWork::SCALARS),
+                     w.at<uint8_t>(MixedWork::DIGEST));
+  HIP_TRY(hipGetLastError());
+  b.status.resize(count);
+  b.digest.resize(32 * count);
+  HIP_TRY(hipMemcpyAsync(b.status.data(), w.p[MixedWork::STATUS], 4 * count, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(b.digest.data(), w.p[MixedWork::DIGEST], 32 * count, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  b.ms_replay = ms_since(t1);
+  b.h = &v0->h;
+  b.x_h = &v0->x_h;
+  return PLONK_OK;
+}
+
+// one aggregated check of the proofs `which` (all VS_OK): rho from the digests, the weighting and the VK / g sums on the
+// device, the MSM, the pairing
+static int mixed_check(MixedState& b, const uint32_t* which, size_t m, bool* ok) {
+  Ctx* c = b.c;
+  MixedWork& w = *b.w;
+  const hipStream_t st = c->stream;
+  const auto t0 = std::chrono::steady_clock::now();
+  // the sub-batch's slots (ascending) and its positions grouped by slot (a counting sort, stable)
+  const size_t nu = b.used.size();
+  b.cnt.assign(nu + 1, 0);
+  for (size_t i = 0; i < m; ++i) ++b.cnt[b.dense[which[i]] + 1];
+  b.sub_slots.clear();
+  b.seg.assign(1, 0);
+  b.seg_pt.clear();
+  std::vector<uint32_t> first(nu + 1);   // where slot u's positions start in the grouped order
+  for (size_t u = 0; u < nu; ++u) {
+    first[u] = b.seg.back();
+    if (!b.cnt[u + 1]) continue;
+    b.sub_slots.push_back(b.used[u]);
+    b.seg.push_back(b.seg.back() + b.cnt[u + 1]);
+    b.seg_pt.push_back((uint32_t)(P_COUNT * u));
+  }
+  b.order.resize(m);
+  for (size_t i = 0; i < m; ++i) b.order[first[b.dense[which[i]]]++] = (uint32_t)i;
+  const uint32_t ns = (uint32_t)b.sub_slots.size();
+  const Fr rho = m == 1 ? Fr::one()
+                        : mixed_batch_challenge(b.sub_slots.data(), ns, b.slot_digest.data(), b.circuit, b.digest.data(), which, m);
+  const uint32_t nL = (uint32_t)(2 * m), r0 = P_COUNT * ns + 1;
+  const uint64_t nR = r0 + (uint64_t)PC_COUNT * m;
+  HIP_TRY(hipMemcpyAsync(w.p[MixedWork::WHICH], which, 4 * m, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(w.p[MixedWork::ORDER], b.order.data(), 4 * m, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(w.p[MixedWork::SEG], b.seg.data(), 4 * (ns + 1), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(w.p[MixedWork::SEG_PT], b.seg_pt.data(), 4 * ns, hipMemcpyHostToDevice, st));
+  uint32_t* sc = w.at<uint32_t>(MixedWork::SC);
+  uint32_t* ids = w.at<uint32_t>(MixedWork::IDS);
+  hipLaunchKernelGGL(verify_weight_kernel, dim3((uint32_t)((m + 255) / 256)), dim3(256), 0, st, w.at<const uint32_t>(MixedWork::WHICH),
+                     w.at<const uint32_t>(MixedWork::ORDER), (uint32_t)m, rho, w.at<const ProofScalars>(MixedWork::SCALARS),
+                     b.pt_proof0, nL, r0, sc, ids, w.at<Fr>(MixedWork::WV));
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(verify_vksum_kernel, dim3(ns, P_COUNT + 1), dim3(VSUM_LANES), 0, st, w.at<const Fr>(MixedWork::WV), (uint32_t)m,
+                     w.at<const uint32_t>(MixedWork::SEG), w.at<const uint32_t>(MixedWork::SEG_PT), nL, sc, ids,
+                     w.at<Fr>(MixedWork::GPART));
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(verify_gsum_kernel, dim3(1), dim3(VSUM_LANES), 0, st, w.at<const Fr>(MixedWork::GPART), ns, nL, b.pt_g, sc, ids);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(st));   // the weighting is scalar work (ms_scalars), not MSM
+  const auto tp = std::chrono::steady_clock::now();
+  H1 sums[2];
+  PTRY_V(msm_run(c, sc, ids, nL, nR, w.at<const G1Affine>(MixedWork::PTS), w.at<const int32_t>(MixedWork::KIND),
+                 w.at<G1>(MixedWork::PART), sums));
+  const auto t1 = std::chrono::steady_clock::now();
+  *ok = pairing_check(sums, *b.x_h, *b.h);
+  const auto t2 = std::chrono::steady_clock::now();
+  if (!b.checks) b.first_terms = nL + nR;
+  ++b.checks;
+  b.ms_weight += std::chrono::duration<double, std::milli>(tp - t0).count();
+  b.ms_msm += std::chrono::duration<double, std::milli>(t1 - tp).count();
+  b.ms_pairing += std::chrono::duration<double, std::milli>(t2 - t1).count();
+  return PLONK_OK;
+}
+
+// as bisect: a failing set is halved, each half with its own rho
+static int mixed_bisect(MixedState& b, std::vector<uint32_t>& which, size_t lo, size_t hi) {
+  if (lo >= hi) return PLONK_OK;
+  bool ok = false;
+  PTRY_V(mixed_check(b, which.data() + lo, hi - lo, &ok));
+  if (ok) return PLONK_OK;
+  if (hi - lo == 1) {
+    b.status[which[lo]] = VS_REJECT;
+    return PLONK_OK;
+  }
+  const size_t mid = lo + (hi - lo) / 2;
+  PTRY_V(mixed_bisect(b, which, lo, mid));
+  return mixed_bisect(b, which, mid, hi);
+}
+
+#define MIXED_ARG(msg) return (set_last_error(api_fn, msg, __FILE__, __LINE__), PLONK_ERR_ARG)
+
+// the PLONK_ERR_ARG checks of plonk_verify_mixed (and of its test hook), each with its own text
+static int mixed_args(const char* api_fn, plonk_verifier* const* verifiers, uint32_t nverifiers, const uint32_t* circuit,
+                      const uint8_t* proofs, const uint64_t* pi, uint64_t pi_total, uint64_t count) {
+  if (!verifiers || !circuit || !proofs || (pi_total && !pi)) MIXED_ARG("invalid argument: a required pointer is NULL");
+  if (nverifiers == 0) MIXED_ARG("invalid argument: nverifiers == 0");
+  for (uint32_t s = 0; s < nverifiers; ++s)
+    if (!verifiers[s]) MIXED_ARG("invalid argument: verifiers[] holds a NULL verifier");
+  if (count == 0 || count > (1ull << 24)) MIXED_ARG("invalid argument: count must be in [1, 2^24]");
+  uint64_t sum = 0;
+  for (uint64_t k = 0; k < count; ++k) {
+    if (circuit[k] >= nverifiers) MIXED_ARG("invalid argument: circuit[k] >= nverifiers");
+    sum += verifiers[circuit[k]]->v->core.pi_idx.size();
+  }
+  if (sum != pi_total) MIXED_ARG("invalid argument: pi_total differs from the sum of the proofs' public-input counts");
+  for (uint32_t s = 1; s < nverifiers; ++s) {
+    if (verifiers[s]->ctx != verifiers[0]->ctx) MIXED_ARG("invalid argument: the verifiers are on different contexts");
+    if (memcmp(verifiers[s]->v->opening_key, verifiers[0]->v->opening_key, OPENING_KEY_LEN))
+      MIXED_ARG("invalid argument: the verifiers' opening keys (g, h, x_h) differ");
+  }
+  return PLONK_OK;
+}
+#undef MIXED_ARG
+
 }  // namespace plonk
 
 using namespace plonk;
-
-struct plonk_verifier {
-  plonk::Verifier* v;
-  plonk_ctx* ctx;
-};
 
 
 extern "C" {
@@ -323,6 +731,9 @@ int plonk_verifier_from_bytes(plonk_ctx* ctx, const uint8_t* blob, uint64_t len,
   uint8_t h96[96], xh96[96];
   std::unique_ptr<plonk::Verifier> v(new plonk::Verifier());
   PTRY_V(plonk::parse_verifier_blob(blob, len, &v->core, v->g48, h96, xh96));
+  memcpy(v->opening_key, v->g48, 48);
+  memcpy(v->opening_key + 48, h96, 96);
+  memcpy(v->opening_key + 144, xh96, 96);
   v->h = plonk::g2_prepare(plonk::g2_decode_valid(h96));
   v->x_h = plonk::g2_prepare(plonk::g2_decode_valid(xh96));
   CTX_ENTER(ctx->c, api_fn);
@@ -462,6 +873,76 @@ int plonk_test_verify_msm(plonk_ctx* ctx, const uint8_t* comp48, const uint32_t*
   if (a.inf) { out97[96] = 1; return PLONK_OK; }
   memcpy(out97, a.x.l, 48);
   memcpy(out97 + 48, a.y.l, 48);
+  return PLONK_OK;
+  });
+}
+
+int plonk_verify_mixed(plonk_verifier* const* verifiers, uint32_t nverifiers, const uint32_t* circuit, const uint8_t* proofs,
+                       const uint64_t* pi, uint64_t pi_total, uint64_t count, int32_t* verdicts, plonk_verify_info* info) {
+  const char* const api_fn = __func__;
+  return plonk::api_guard(api_fn, [&]() -> int {
+  PTRY_V(plonk::mixed_args(api_fn, verifiers, nverifiers, circuit, proofs, pi, pi_total, count));
+  if (count > 1 && !verdicts) return (plonk::set_last_error(api_fn, "invalid argument: verdicts is NULL and count > 1", __FILE__, __LINE__), PLONK_ERR_ARG);
+  CTX_ENTER(verifiers[0]->ctx->c, api_fn);
+  plonk::MixedState b;
+  b.c = &verifiers[0]->ctx->c;
+  HIP_TRY(hipSetDevice(b.c->device));
+  PTRY_V(plonk::mixed_front(b, verifiers, nverifiers, circuit, proofs, pi, pi_total, count));
+  std::vector<uint32_t> which;
+  for (uint64_t k = 0; k < count; ++k)
+    if (b.status[k] == plonk::VS_OK) which.push_back((uint32_t)k);
+  PTRY_V(plonk::mixed_bisect(b, which, 0, which.size()));
+  uint32_t rejected = 0;
+  int rc = PLONK_OK;
+  for (uint64_t k = 0; k < count; ++k) {
+    const int s = b.status[k];
+    const int32_t code = s == plonk::VS_OK ? PLONK_OK : s == plonk::VS_DATA ? PLONK_ERR_DATA : s == plonk::VS_POINT ? PLONK_ERR_POINT : PLONK_ERR_VERIFY;
+    if (verdicts) verdicts[k] = code;
+    if (code != PLONK_OK) { ++rejected; rc = PLONK_ERR_VERIFY; }
+  }
+  if (info) {
+    info->proofs = count;
+    info->msm_terms = b.first_terms;
+    info->pairing_checks = b.checks;
+    info->rejected = rejected;
+    info->ms_decode = b.ms_decode;
+    info->ms_scalars = b.ms_replay + b.ms_weight;
+    info->ms_msm = b.ms_msm;
+    info->ms_pairing = b.ms_pairing;
+  }
+  if (rc != PLONK_OK) plonk::set_last_error(api_fn, "proof verification failed (Error::ProofVerificationError)", __FILE__, __LINE__);
+  return rc;
+  });
+}
+
+// Test hook (not in include/plonk_hip.h, not part of the API): the front half of plonk_verify_mixed — decode and the device
+// replay — with its arguments and checks, returning per proof the replay's status (VerifyStatus: 0 ok, 1 rejected by the
+// barycentric evaluation, 2 non-canonical evaluation, 3 bad commitment), the 28 scalars of ProofScalars (vk[15] in PolyId
+// order, g, comm[11], u; Montgomery, 8 words each) and the 32-byte proof digest.  The binding's Context._verify_replay
+// calls it for tests/test_gpu_verify_mixed.py.
+int plonk_test_verify_replay(plonk_verifier* const* verifiers, uint32_t nverifiers, const uint32_t* circuit,
+                             const uint8_t* proofs, const uint64_t* pi, uint64_t pi_total, uint64_t count, int32_t* status,
+                             uint32_t* scalars, uint8_t* digests) {
+  const char* const api_fn = __func__;
+  return plonk::api_guard(api_fn, [&]() -> int {
+  PTRY_V(plonk::mixed_args(api_fn, verifiers, nverifiers, circuit, proofs, pi, pi_total, count));
+  if (!status || !scalars || !digests) return (plonk::set_last_error(api_fn, "invalid argument", __FILE__, __LINE__), PLONK_ERR_ARG);
+  CTX_ENTER(verifiers[0]->ctx->c, api_fn);
+  plonk::MixedState b;
+  b.c = &verifiers[0]->ctx->c;
+  HIP_TRY(hipSetDevice(b.c->device));
+  PTRY_V(plonk::mixed_front(b, verifiers, nverifiers, circuit, proofs, pi, pi_total, count));
+  std::vector<plonk::ProofScalars> ps(count);
+  HIP_TRY(hipMemcpy(ps.data(), b.w->p[plonk::MixedWork::SCALARS], sizeof(plonk::ProofScalars) * count, hipMemcpyDeviceToHost));
+  for (uint64_t k = 0; k < count; ++k) {
+    status[k] = b.status[k];
+    uint32_t* o = scalars + 28 * 8 * k;
+    memcpy(o, ps[k].vk, 32 * plonk::P_COUNT);
+    memcpy(o + 8 * 15, ps[k].g.l, 32);
+    memcpy(o + 8 * 16, ps[k].comm, 32 * plonk::PC_COUNT);
+    memcpy(o + 8 * 27, ps[k].u.l, 32);
+  }
+  memcpy(digests, b.digest.data(), 32 * count);
   return PLONK_OK;
   });
 }

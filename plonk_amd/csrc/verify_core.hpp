@@ -8,7 +8,7 @@
 //
 // over the 15 verifier-key points VK_j, the opening key's g and the proof's 11 commitments C_c.  The MSM (device,
 // verify.hip) and the pairing (hostpairing.hpp) come after, for a whole batch.
-// Included by verify.hip and by the CPU test harness.
+// Included by verify.hip and by the CPU test harnesses (tests/csrc/host_verify.cpp, tests/csrc/host_verify_mixed.cpp).
 #pragma once
 #include <string>
 #include <vector>
@@ -60,64 +60,80 @@ struct ProofScalars {
   Fr u;                // L = [W_z] + u [W_zw]
 };
 
+// The replay and the scalars below are __host__ __device__ (field.cuh's HD): plonk_verify runs them on host threads through
+// the VerifierCore wrappers (verify_scalars, barycentric_eval), plonk_verify_mixed in one device lane per proof
+// (verify.hip), which reads a circuit's constants from this POD and its pi_root from a concatenated array.
+struct SlotConst {
+  uint64_t n, constraints;          // domain size, circuit size (vk.n)
+  Fr omega, n_inv, edwards_d;
+  uint64_t pi_count, pi_root_off;   // the circuit's pi_root: pi_root_all + pi_root_off
+};
+
 // compute_lagrange_and_barycentric_evaluations: false (Error::ProofVerificationError) when z = 1 or z is the root of a
-// non-zero public input
-static bool barycentric_eval(const VerifierCore& v, const Fr& z, const Fr* pi, const Fr& z_h, Fr* l1, Fr* pi_eval) {
+// non-zero public input.  sum_i pi_i / d_i is accumulated as one fraction num / den, so one inversion of den_0 * den gives
+// L1(z) = z_h / den_0 and PI(z) = z_h n^-1 num / den without scratch (the same field values as a batch inversion).
+HD_NOINLINE bool barycentric_core(uint64_t n, const Fr& n_inv, const Fr* pi_root, uint64_t m, const Fr& z, const Fr* pi, const Fr& z_h,
+                         Fr* l1, Fr* pi_eval) {
   const Fr one = Fr::one();
-  const size_t m = v.pi_root.size();
-  std::vector<Fr> den(m + 1), pre(m + 1);
-  den[0] = Fr::from_u64(v.n) * (z - one);
-  std::vector<size_t> idx;
-  Fr run = one;
-  for (size_t i = 0; i <= m; ++i) {
-    if (i) {
-      if (pi[i - 1].is_zero()) continue;
-      den[i] = v.pi_root[i - 1] * z - one;
-    }
-    if (den[i].is_zero()) return false;
-    pre[i] = run;
-    run = run * den[i];
-    idx.push_back(i);
+  const Fr den0 = Fr::from_u64(n) * (z - one);
+  if (den0.is_zero()) return false;
+  Fr num = Fr::zero(), den = one;
+  for (uint64_t i = 0; i < m; ++i) {
+    if (pi[i].is_zero()) continue;
+    const Fr d = pi_root[i] * z - one;
+    if (d.is_zero()) return false;
+    num = num * d + pi[i] * den;
+    den = den * d;
   }
-  Fr inv = fr_inv_gcd(run), acc = Fr::zero();
-  for (size_t j = idx.size(); j-- > 0;) {
-    const size_t i = idx[j];
-    const Fr di = inv * pre[i];
-    inv = inv * den[i];
-    if (i) acc = acc + di * pi[i - 1];
-    else *l1 = z_h * di;
-  }
-  *pi_eval = acc * z_h * v.n_inv;
+  const Fr inv = fr_inv_gcd(den0 * den);
+  *l1 = z_h * den * inv;
+  *pi_eval = num * den0 * inv * z_h * n_inv;
   return true;
 }
+static bool barycentric_eval(const VerifierCore& v, const Fr& z, const Fr* pi, const Fr& z_h, Fr* l1, Fr* pi_eval) {
+  return barycentric_core(v.n, v.n_inv, v.pi_root.data(), v.pi_root.size(), z, pi, z_h, l1, pi_eval);
+}
 
-static bool fr_from_canonical(const uint8_t b[32], Fr* out) {
+HD bool fr_from_canonical(const uint8_t b[32], Fr* out) {   // BlsScalar::from_bytes: only values < q
   Fr x;
   memcpy(x.l, b, 32);
-  for (int i = 7; i >= 0; --i)
-    if (x.l[i] != FrP::MOD[i]) {
-      if (x.l[i] > FrP::MOD[i]) return false;
-      break;
-    } else if (i == 0) {
-      return false;   // == q
-    }
+  uint64_t borrow = 0;   // x - q borrows iff x < q
+#pragma unroll
+  for (int i = 0; i < 8; ++i) borrow = (((uint64_t)x.l[i] - FrP::MOD[i] - borrow) >> 63) & 1;
+  if (!borrow) return false;
   *out = x.to_mont();
   return true;
 }
 
-// Proof::verify up to its MSM (proof.rs:218-502).  pi: the verifier's public inputs in Montgomery form.
-static ProofScalars verify_scalars(const VerifierCore& v, const uint8_t proof[PROOF_BYTES], const Fr* pi) {
-  ProofScalars o;
+// Proof::verify up to its MSM (proof.rs:218-502) from a transcript already seeded with the label and the verifier key
+// (seed_transcript_vk).  pi: the circuit's public inputs in Montgomery form.  digest (may be null): the proof digest of a
+// mixed batch, challenge_bytes("batch digest", 32) drawn after u; zero when the evaluations are not canonical.
+HD void replay_scalars(const SlotConst& v, const Fr* pi_root, Transcript& tr, const uint8_t* proof, const Fr* pi,
+                       ProofScalars* out, uint8_t* digest) {
+  ProofScalars& o = *out;
+  o.status = VS_OK;
+#pragma unroll
+  for (int j = 0; j < P_COUNT; ++j) o.vk[j] = Fr::zero();
+#pragma unroll
+  for (int c = 0; c < PC_COUNT; ++c) o.comm[c] = Fr::zero();
+  o.g = Fr::zero();
+  o.u = Fr::zero();
+  Fr raw[15];   // Proof::to_bytes evaluation order
+  bool canonical = true;
+#pragma unroll
+  for (int k = 0; k < 15; ++k) canonical = fr_from_canonical(proof + PC_COUNT * 48 + 32 * k, &raw[k]) && canonical;
+  if (!canonical) {
+    o.status = VS_DATA;
+    if (digest) memset(digest, 0, 32);
+    return;
+  }
   Evals ev;
-  Fr* order[15] = {&ev.a, &ev.b, &ev.c, &ev.d, &ev.a_w, &ev.b_w, &ev.d_w, &ev.q_arith, &ev.q_c, &ev.q_l,
-                   &ev.q_r, &ev.s1, &ev.s2, &ev.s3, &ev.z};
-  for (int k = 0; k < 15; ++k)
-    if (!fr_from_canonical(proof + PC_COUNT * 48 + 32 * k, order[k])) { o.status = VS_DATA; return o; }
+  ev.a = raw[0]; ev.b = raw[1]; ev.c = raw[2]; ev.d = raw[3]; ev.a_w = raw[4]; ev.b_w = raw[5]; ev.d_w = raw[6];
+  ev.q_arith = raw[7]; ev.q_c = raw[8]; ev.q_l = raw[9]; ev.q_r = raw[10]; ev.s1 = raw[11]; ev.s2 = raw[12]; ev.s3 = raw[13];
+  ev.z = raw[14];
   const uint8_t* cm = proof;   // 11 x 48 compressed commitments
-  // transcript_for_version + the public inputs (prover.rs:440-442, proof.rs:231-245)
-  Transcript tr((const uint8_t*)v.label.data(), v.label.size());
-  seed_transcript_vk(tr, v.constraints, v.vk, v.version);   // the prover's seeding (widgets.hpp)
-  for (size_t i = 0; i < v.pi_idx.size(); ++i) tr.append_scalar("pi", pi[i]);
+  // the public inputs (prover.rs:440-442, proof.rs:231-245)
+  for (uint64_t i = 0; i < v.pi_count; ++i) tr.append_scalar("pi", pi[i]);
   tr.append_commitment("a_comm", cm + 48 * PC_A);
   tr.append_commitment("b_comm", cm + 48 * PC_B);
   tr.append_commitment("c_comm", cm + 48 * PC_C);
@@ -157,26 +173,28 @@ static ProofScalars verify_scalars(const VerifierCore& v, const uint8_t proof[PR
   tr.append_commitment("w_z_chall_w_comm", cm + 48 * PC_WZW);
   const Fr u = tr.challenge_scalar("u_challenge");
 
+  if (digest) tr.challenge_bytes("batch digest", digest, 32);
+
   const Fr one = Fr::one();
   const Fr z_n = z.pow_u64(v.n), z_h = z_n - one;
   Fr l1, pi_eval;
-  if (!barycentric_eval(v, z, pi, z_h, &l1, &pi_eval)) { o.status = VS_REJECT; return o; }
+  if (!barycentric_core(v.n, v.n_inv, pi_root, v.pi_count, z, pi, z_h, &l1, &pi_eval)) { o.status = VS_REJECT; return; }
   const Fr a2 = alpha.sqr();
   const Fr perm = (ev.a + beta * ev.s1 + gamma) * (ev.b + beta * ev.s2 + gamma) * (ev.c + beta * ev.s3 + gamma);
   const Fr r0 = pi_eval - l1 * a2 - alpha * perm * (ev.d + gamma) * ev.z;
   // v^1 .. v^11, then v_w u, v_w^2 u, v_w^3 u  (proof.rs:330-353)
   Fr vc[14];
   vc[0] = vch;
+#pragma unroll
   for (int i = 1; i < 11; ++i) vc[i] = vc[i - 1] * vch;
   vc[11] = v_w * u;
   vc[12] = vc[11] * v_w;
   vc[13] = vc[12] * v_w;
   const Fr e_evals[14] = {ev.a, ev.b, ev.c, ev.d, ev.s1, ev.s2, ev.s3, ev.q_arith, ev.q_c, ev.q_l, ev.q_r, ev.a_w, ev.b_w, ev.d_w};
   Fr e_scalar = u * ev.z - r0;
+#pragma unroll
   for (int i = 0; i < 14; ++i) e_scalar = e_scalar + e_evals[i] * vc[i];
 
-  for (int j = 0; j < P_COUNT; ++j) o.vk[j] = Fr::zero();
-  for (int c = 0; c < PC_COUNT; ++c) o.comm[c] = Fr::zero();
   // [D]: the widgets' linearisation terms (append_linearization_commitment_terms, proof.rs:808-889)
   const Fr qa = ev.q_arith;
   o.vk[P_QM] = ev.a * ev.b * qa;
@@ -215,6 +233,31 @@ static ProofScalars verify_scalars(const VerifierCore& v, const uint8_t proof[PR
   o.comm[PC_WZ] = z;
   o.comm[PC_WZW] = u * z * v.omega;
   o.u = u;
+}
+
+// the replay's inputs from a VerifierCore: the constants of its circuit and its seeded transcript (label, version, VK)
+static SlotConst slot_const(const VerifierCore& v, uint64_t pi_root_off) {
+  SlotConst s;
+  s.n = v.n;
+  s.constraints = v.constraints;
+  s.omega = v.omega;
+  s.n_inv = v.n_inv;
+  s.edwards_d = v.edwards_d;
+  s.pi_count = v.pi_idx.size();
+  s.pi_root_off = pi_root_off;
+  return s;
+}
+static Transcript seeded_transcript(const VerifierCore& v) {   // transcript_for_version + seed_transcript (prover.rs:440)
+  Transcript tr((const uint8_t*)v.label.data(), v.label.size());
+  seed_transcript_vk(tr, v.constraints, v.vk, v.version);   // the prover's seeding (widgets.hpp)
+  return tr;
+}
+
+// Proof::verify up to its MSM for plonk_verify's host threads: the shared replay from a freshly seeded transcript
+static ProofScalars verify_scalars(const VerifierCore& v, const uint8_t proof[PROOF_BYTES], const Fr* pi) {
+  ProofScalars o;
+  Transcript tr = seeded_transcript(v);
+  replay_scalars(slot_const(v, 0), v.pi_root.data(), tr, proof, pi, &o, nullptr);
   return o;
 }
 
@@ -290,5 +333,42 @@ static int parse_verifier_blob(const uint8_t* blob, uint64_t len, VerifierCore* 
   return PLONK_OK;
 }
 #undef VFAIL
+
+// ---- mixed batches (plonk_verify_mixed) ---------------------------------------------------------------------------------
+// The verifier digest: everything a circuit's check depends on besides the proof — its label, transcript version, domain
+// size, constraints, the 15 VK commitments (VerifierKey::to_bytes order), the 240-byte opening key and the public-input
+// indexes.
+static void verifier_digest(const VerifierCore& v, const uint8_t opening_key[OPENING_KEY_LEN], uint8_t out[32]) {
+  const char* dom = "plonk-verifier-digest-v1";
+  Transcript tr((const uint8_t*)dom, cstr_len(dom));
+  tr.append_message("label", (const uint8_t*)v.label.data(), v.label.size());
+  tr.append_u64("version", (uint64_t)v.version);
+  tr.append_u64("size", v.n);
+  tr.append_u64("constraints", v.constraints);
+  for (int j = 0; j < 15; ++j) tr.append_commitment("vk", v.vk[VK_BLOB_ORDER[j]]);
+  tr.append_message("opening key", opening_key, OPENING_KEY_LEN);
+  tr.append_u64("public inputs", v.pi_idx.size());
+  for (uint64_t idx : v.pi_idx) tr.append_u64("public input index", idx);
+  tr.challenge_bytes("circuit digest", out, 32);
+}
+
+// rho of a mixed (sub-)batch: its length, every verifier slot it uses (ascending) with that slot's verifier digest, then
+// every proof's slot and proof digest.  used: the slots, ascending; slot_digest: 32 bytes per slot; circuit / proof_digest:
+// per proof of the call; which: the m proofs of the sub-batch.
+static Fr mixed_batch_challenge(const uint32_t* used, size_t nused, const uint8_t* slot_digest, const uint32_t* circuit,
+                                const uint8_t* proof_digest, const uint32_t* which, size_t m) {
+  const char* dom = "plonk-batch-verify-mixed-v1";
+  Transcript tr((const uint8_t*)dom, cstr_len(dom));
+  tr.append_u64("batch length", m);
+  for (size_t i = 0; i < nused; ++i) {
+    tr.append_u64("slot", used[i]);
+    tr.append_message("circuit", slot_digest + 32ull * used[i], 32);
+  }
+  for (size_t i = 0; i < m; ++i) {
+    tr.append_u64("circuit", circuit[which[i]]);
+    tr.append_message("proof", proof_digest + 32ull * which[i], 32);
+  }
+  return tr.challenge_scalar("rho");
+}
 
 }  // namespace plonk

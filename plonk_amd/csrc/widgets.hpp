@@ -17,7 +17,7 @@ enum PolyId {
   P_S1, P_S2, P_S3, P_S4, P_COUNT
 };
 
-static inline Fr fr_small(uint64_t v) { return Fr::from_u64(v); }
+static HD Fr fr_small(uint64_t v) { return Fr::from_u64(v); }
 
 // transcript labels in VerifierKey::seed_transcript order (widget.rs:229-254): the prover's seeding and the verifier's replay
 static const int VK_ORDER[15] = {P_QM, P_QL, P_QR, P_QO, P_QC, P_QF, P_QARITH, P_QRANGE, P_QLOGIC,
@@ -72,21 +72,22 @@ struct EvalsT {
 using Evals = EvalsT<Fr>;
 
 template <class T>
-static T delta_h(const T& f) {   // f (f-1)(f-2)(f-3)
+static HD T delta_h(const T& f) {   // f (f-1)(f-2)(f-3)
   return f * (f - Fr::one()) * (f - fr_small(2)) * (f - fr_small(3));
 }
 
-// widget identities: at the evaluation point (T = Fr, the scalar factors of compute_linearization)
-// and as power series in X (T = Ser, the same expressions inside compute_quotient_i)
+// widget identities: at the evaluation point (T = Fr, the scalar factors of compute_linearization; also on the device,
+// in plonk_verify_mixed's replay kernel) and as power series in X (T = Ser, the same expressions inside compute_quotient_i,
+// host only)
 template <class T>
-static T range_identity(const Fr& ch, const EvalsT<T>& e) {            // range/proverkey.rs:60-85
+static HD_NOINLINE T range_identity(const Fr& ch, const EvalsT<T>& e) {            // range/proverkey.rs:60-85
   const Fr four = fr_small(4);
   const Fr k1 = ch.sqr(), k2 = k1.sqr(), k3 = k2 * k1;
   return delta_h(e.c - four * e.d) + delta_h(e.b - four * e.c) * k1 + delta_h(e.a - four * e.b) * k2 +
          delta_h(e.d_w - four * e.a) * k3;
 }
 template <class T>
-static T logic_identity(const Fr& ch, const EvalsT<T>& e) {            // logic/proverkey.rs:72-144
+static HD_NOINLINE T logic_identity(const Fr& ch, const EvalsT<T>& e) {            // logic/proverkey.rs:72-144
   const Fr four = fr_small(4);
   const Fr k1 = ch.sqr(), k2 = k1.sqr(), k3 = k2 * k1, k4 = k3 * k1;
   const T a = e.a_w - four * e.a, b = e.b_w - four * e.b, d = e.d_w - four * e.d, w = e.c;
@@ -98,7 +99,7 @@ static T logic_identity(const Fr& ch, const EvalsT<T>& e) {            // logic/
   return delta_h(a) + delta_h(b) * k1 + delta_h(d) * k2 + (w - a * b) * k3 + (Bb + Ee) * k4;
 }
 template <class T>
-static T fixed_identity(const Fr& ch, const EvalsT<T>& e, const Fr& ed) {   // fixed_base/proverkey.rs:103-159
+static HD_NOINLINE T fixed_identity(const Fr& ch, const EvalsT<T>& e, const Fr& ed) {   // fixed_base/proverkey.rs:103-159
   const Fr one = Fr::one();
   const Fr k1 = ch.sqr(), k2 = k1.sqr(), k3 = k2 * k1;
   const T bit = e.d_w - e.d - e.d;
@@ -112,7 +113,7 @@ static T fixed_identity(const Fr& ch, const EvalsT<T>& e, const Fr& ed) {   // f
   return bit_cons + x_acc + y_acc + xy_cons;
 }
 template <class T>
-static T var_identity(const Fr& ch, const EvalsT<T>& e, const Fr& ed) {     // curve_addition/proverkey.rs:79-120
+static HD_NOINLINE T var_identity(const Fr& ch, const EvalsT<T>& e, const Fr& ed) {     // curve_addition/proverkey.rs:79-120
   const Fr k1 = ch.sqr();
   const T x1y2 = e.d_w, y1x2 = e.b * e.c, y1y2 = e.b * e.d, x1x2 = e.a * e.c;
   const T dxy = ed * x1y2 * y1x2;

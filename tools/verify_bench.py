@@ -3,7 +3,11 @@ four public inputs, made once on the GPU with different blinders, verified in ba
 the call (it returns after its last device synchronisation), proofs per second, the plonk_verifier_last phase times,
 msm_terms and pairing_checks; then one run with one bad proof per 1024.
 
-    python tools/verify_bench.py [--log-n 12] [--ks 1,64,1024,8192] [--reps 3]
+With --circuits C, C circuits of different sizes (2^log_n, 2^(log_n - 1), ...) and public-input counts (4, 1, 6, 0, ...) are
+compiled from one SRS and their proofs interleaved (proof k of circuit k mod C); each K prints a plonk_verify_mixed line
+and, for C = 1, a plonk_verify line on the same batch, the two alternating in this process (best of --reps each).
+
+    python tools/verify_bench.py [--log-n 12] [--ks 1,64,1024,8192] [--reps 3] [--circuits 1]
 """
 import argparse
 import json
@@ -38,6 +42,7 @@ def main():
     ap.add_argument("--log-n", type=int, default=12)
     ap.add_argument("--ks", default="1,64,1024,8192")
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--circuits", type=int, default=1)
     args = ap.parse_args()
     ks = [int(k) for k in args.ks.split(",")]
     import plonk_amd
@@ -46,48 +51,69 @@ def main():
     import g2_ref as G2
     tau, g = 0x5EED0000 * 0x9E3779B97F4A7C15 % E.Q, 0xA5A5A5A5DEADBEEF   # circuits.synthetic_srs's defaults
     ctx = plonk_amd.Context(0)
-    comp = circuit(1 << args.log_n, 4)
-    case = C.compile_fast(comp, b"verify-bench")
-    srs = C.synthetic_srs(case["size"] + 7)
+    npis = [4, 1, 6, 0]
+    shapes = [(max(args.log_n - c, 4), npis[c % 4]) for c in range(args.circuits)]
+    srs = C.synthetic_srs((1 << args.log_n) + 7)   # one SRS for every circuit, loaded before any is compiled
     ctx.srs_load_bytes(srs, len(srs) // 96)
-    cols = C.circuit_columns(comp)
-    prover = plonk_amd.Prover.compile(ctx, b"verify-bench", cols["selectors"], cols["wires"], cols["witnesses"])
     opening_key = E.g1_compress(E.g1_mul(E.G1_GEN, g)) + G2.g2_compress(G2.G2_GEN) + G2.g2_compress(G2.g2_mul(G2.G2_GEN, tau))
-    verifier = plonk_amd.Verifier(ctx, prover.verifier_to_bytes(opening_key, case["pi_idx"]))
-    pis = [case["pi"][i] for i in case["pi_idx"]]
     kmax = max(ks)
+    circs = []
     t0 = time.perf_counter()
-    proofs = [prover.prove_witnesses(cols["values"], case["pi"], C.blinders(k)) for k in range(kmax)]
-    print(json.dumps({"setup": "proofs", "log_n": args.log_n, "public_inputs": len(pis), "count": kmax,
-                      "seconds": round(time.perf_counter() - t0, 2)}), flush=True)
+    for c, (log_n, npi) in enumerate(shapes):
+        label = b"verify-bench" if args.circuits == 1 else b"verify-bench-%d" % c
+        comp = circuit(1 << log_n, npi, seed=4242 + c)
+        case = C.compile_fast(comp, label)
+        cols = C.circuit_columns(comp)
+        prover = plonk_amd.Prover.compile(ctx, label, cols["selectors"], cols["wires"], cols["witnesses"])
+        verifier = plonk_amd.Verifier(ctx, prover.verifier_to_bytes(opening_key, case["pi_idx"]))
+        pis = [case["pi"][i] for i in case["pi_idx"]]
+        n = len(range(c, kmax, args.circuits))
+        proofs = [prover.prove_witnesses(cols["values"], case["pi"], C.blinders(k)) for k in range(n)]
+        circs.append((prover, verifier, pis, proofs))
+    items = [(circs[k % args.circuits][1], circs[k % args.circuits][3][k // args.circuits], circs[k % args.circuits][2])
+             for k in range(kmax)]
+    print(json.dumps({"setup": "proofs", "log_n": args.log_n, "circuits": [{"log_n": ln, "public_inputs": p} for ln, p in shapes],
+                      "count": kmax, "seconds": round(time.perf_counter() - t0, 2)}), flush=True)
+
+    def one(batch, call):
+        t = time.perf_counter()
+        if call == "plonk_verify":
+            v = batch[0][0]
+            verdicts = v.verify_batch([p for _, p, _ in batch], [x for _, _, x in batch])
+            info = v.last()
+        else:
+            verdicts, info = plonk_amd.verify_mixed(batch)
+        return (time.perf_counter() - t) * 1e3, info, verdicts
 
     def run(batch, label):
-        best = None
-        for _ in range(args.reps):
-            t = time.perf_counter()
-            verdicts = verifier.verify_batch(batch, [pis] * len(batch))
-            ms = (time.perf_counter() - t) * 1e3
-            info = verifier.last()
-            if best is None or ms < best[0]:
-                best = (ms, info, verdicts)
-        ms, info, verdicts = best
-        out = {"run": label, "K": len(batch), "wall_ms": round(ms, 3), "proofs_per_s": round(len(batch) / ms * 1e3, 1),
-               "rejected": sum(v != 0 for v in verdicts)}
-        out.update({k: (round(v, 3) if isinstance(v, float) else v) for k, v in info.items()})
-        print(json.dumps(out), flush=True)
+        calls = ["plonk_verify_mixed"] + (["plonk_verify"] if args.circuits == 1 else [])
+        best = {}
+        for _ in range(args.reps):   # the calls alternate, so both see the same state of the machine
+            for call in calls:
+                r = one(batch, call)
+                if call not in best or r[0] < best[call][0]:
+                    best[call] = r
+        for call in calls:
+            ms, info, verdicts = best[call]
+            out = {"run": label, "call": call, "circuits": args.circuits, "K": len(batch), "wall_ms": round(ms, 3),
+                   "proofs_per_s": round(len(batch) / ms * 1e3, 1), "rejected": sum(v != 0 for v in verdicts)}
+            out.update({k: (round(v, 3) if isinstance(v, float) else v) for k, v in info.items()})
+            print(json.dumps(out), flush=True)
 
     for k in ks:
-        run(proofs[:k], "valid")
-    bad = list(proofs[:kmax])
+        run(items[:k], "valid")
+    bad = list(items[:kmax])
     for i in range(0, kmax, 1024):
         j = i + 517 % min(1024, kmax - i)
-        b = bytearray(bad[j])
-        v = (int.from_bytes(b[528:560], "little") + 1) % E.Q
-        b[528:560] = v.to_bytes(32, "little")
-        bad[j] = bytes(b)
+        v, p, x = bad[j]
+        b = bytearray(p)
+        val = (int.from_bytes(b[528:560], "little") + 1) % E.Q
+        b[528:560] = val.to_bytes(32, "little")
+        bad[j] = (v, bytes(b), x)
     run(bad, "one bad per 1024")
-    verifier.close()
-    prover.close()
+    for prover, verifier, _, _ in circs:
+        verifier.close()
+        prover.close()
     ctx.close()
 
 
