@@ -343,6 +343,61 @@ int plonk_prover_prove_witnesses(plonk_prover* p, const uint64_t* witnesses, uin
                                  const uint64_t* pi_val, uint64_t pi_count, const uint64_t* blinders,
                                  uint8_t proof[1008]);
 
+/* ---- witness diagnosis: which gates and copy constraints fail --------------------------------
+ * The proving entry points answer an unsatisfied witness with the bare PLONK_ERR_UNSAT, found at the very end of a proof
+ * (the quotient identity at the evaluation challenge), when the rows have long been folded into one polynomial.  These
+ * three calls give the row-level answer the reference's debugger gives its users (src/debugger.rs:95-236) — and the
+ * copy-constraint violations it cannot see — from what the prover already holds in HBM, without a proof: no group
+ * operation, no challenge, nothing probabilistic.  Use them as a pre-check before a proof or as a post-mortem after one.
+ *
+ * The arguments mean what they mean for plonk_prover_prove / _prove_dev / _prove_witnesses (wire columns over the whole
+ * domain, Fr Montgomery; sparse public inputs); there are no blinders.  Rows are taken over the whole domain of size n;
+ * the rotated values a_w, b_w, d_w of row i are those of row i + 1 mod n — the last row reads row 0, a live row when the
+ * gate count is a power of two (debugger.rs:74-93).  For every row the 17 gate identities are evaluated and each is tested
+ * for zero on its own; bit f of `families` is set when identity f is non-zero there:
+ *    0       arithmetic   (q_m a b + q_l a + q_r b + q_o c + q_f d + q_c) q_arith + PI
+ *    1 - 4   range        the quad deltas of c/d, b/c, a/b, next-row d / a, each times q_range
+ *    5 - 9   logic        the quad deltas of a, b, d, the product term, the xor/and relation, each times q_logic
+ *   10 - 13  fixed base   bit consistency, xy consistency, x accumulator, y accumulator, each times q_fixed_group_add
+ *   14 - 16  variable-base addition   xy consistency, x3, y3, each times q_variable_group_add
+ * Bit k of `copy_wires` (0..3 = a, b, c, d) is set when the value on wire k of the row differs from the value at the
+ * position sigma maps (k, row) to; the position is decoded from the prover's own sigma evaluations, and a value that
+ * decodes to no position counts as failing.  All copy masks are empty iff the columns are constant on every cycle of the
+ * permutation.  A row fails when either mask is non-zero; `out` receives the failing rows in ascending order, the first
+ * min(cap, rows_failing) of them, while the totals of `info` count all.  out == NULL with cap == 0 asks for the summary
+ * only; info may be NULL.
+ * Returns PLONK_OK when no row fails, PLONK_ERR_UNSAT when at least one does (info and the records are filled), and the
+ * usual PLONK_ERR_ARG / _STATE / _HIP otherwise: the witness form needs a prover from plonk_compile (PLONK_ERR_STATE), a
+ * sharded prover holds only its slices and answers PLONK_ERR_STATE.  Every single-GPU prover works (plonk_prover_create,
+ * plonk_compile, plonk_prover_from_bytes).
+ * Cost: the first call on a prover builds two proof-independent caches that live until plonk_prover_destroy — the values
+ * of the non-zero selector polynomials over the domain (32 n bytes each) and the decoded positions (16 n bytes); a prover
+ * that is never diagnosed allocates neither.  A call works in the prover's per-proof scratch and leaves the prover as it
+ * found it: the next proof is bit-identical to one made without the call.  DESIGN.md, "Witness diagnosis". */
+typedef struct plonk_unsat_row {
+  uint64_t row;
+  uint32_t families;          /* bit f: identity f (0..16) is non-zero on this row */
+  uint32_t copy_wires;        /* bit k: wire k (a, b, c, d) of this row breaks its copy constraint */
+} plonk_unsat_row;
+typedef struct plonk_unsat_info {
+  uint64_t rows_checked;      /* n */
+  uint64_t rows_failing;      /* all of them, also beyond cap */
+  uint64_t family_rows[18];   /* rows failing family f (0..16); [17] = rows with a copy-constraint failure */
+  uint64_t first_row;         /* lowest failing row, UINT64_MAX when none */
+  uint32_t first_family;      /* lowest set bit of that row's families, 17 when only a copy constraint fails there */
+  uint32_t reserved;
+  double ms;                  /* host wall clock of the call */
+} plonk_unsat_info;
+int plonk_prover_diagnose(plonk_prover* p, const uint64_t* const wires[4], const uint64_t* pi_idx,
+                          const uint64_t* pi_val, uint64_t pi_count, plonk_unsat_row* out, uint64_t cap,
+                          plonk_unsat_info* info);
+int plonk_prover_diagnose_dev(plonk_prover* p, const void* wires_dev, const uint64_t* pi_idx,
+                              const uint64_t* pi_val, uint64_t pi_count, plonk_unsat_row* out, uint64_t cap,
+                              plonk_unsat_info* info);
+int plonk_prover_diagnose_witnesses(plonk_prover* p, const uint64_t* witnesses, uint64_t count, const uint64_t* pi_idx,
+                                    const uint64_t* pi_val, uint64_t pi_count, plonk_unsat_row* out, uint64_t cap,
+                                    plonk_unsat_info* info);
+
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI ---------------------------------------
  * Rank 0 calls plonk_comm_unique_id and hands the 128 bytes (an ncclUniqueId) to the other ranks by
  * whatever out-of-band channel the host program has; every rank then calls plonk_comm_init on its

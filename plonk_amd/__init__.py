@@ -61,6 +61,18 @@ EXPORTS = [
     "plonk_public_parameters_check", "plonk_srs_load_public_parameters",
     "plonk_verifier_from_bytes", "plonk_verifier_destroy", "plonk_verifier_set_version", "plonk_verify", "plonk_verifier_last",
     "plonk_verify_mixed",
+    "plonk_prover_diagnose", "plonk_prover_diagnose_dev", "plonk_prover_diagnose_witnesses",
+]
+
+# what bit f of plonk_unsat_row.families / slot f of plonk_unsat_info.family_rows stands for (include/plonk_hip.h); the
+# 18th names the copy-constraint slot
+IDENTITY_FAMILIES = [
+    "arithmetic gate",
+    "range: quad c - 4d", "range: quad b - 4c", "range: quad a - 4b", "range: quad next d - 4a",
+    "logic: left quad", "logic: right quad", "logic: output quad", "logic: product of the input quads", "logic: xor/and relation",
+    "fixed-base: scalar bit", "fixed-base: xy of the bit", "fixed-base: x accumulator", "fixed-base: y accumulator",
+    "curve addition: x1 y2", "curve addition: x3", "curve addition: y3",
+    "copy constraint",
 ]
 
 POLY_ORDER = ["q_m", "q_l", "q_r", "q_o", "q_f", "q_c", "q_arith", "q_range", "q_logic",
@@ -119,6 +131,40 @@ class _CircuitDesc(ctypes.Structure):
                 ("shard_rank", ctypes.c_int), ("shard_world", ctypes.c_int),
                 ("srs_total", ctypes.c_uint64), ("allgather", ctypes.c_void_p), ("allgather_user", ctypes.c_void_p),
                 ("lagrange_xy96", ctypes.c_char_p), ("lagrange_count", ctypes.c_uint64)]
+
+
+class _UnsatRow(ctypes.Structure):
+    _fields_ = [("row", ctypes.c_uint64), ("families", ctypes.c_uint32), ("copy_wires", ctypes.c_uint32)]
+
+
+class _UnsatInfo(ctypes.Structure):
+    _fields_ = [("rows_checked", ctypes.c_uint64), ("rows_failing", ctypes.c_uint64), ("family_rows", ctypes.c_uint64 * 18),
+                ("first_row", ctypes.c_uint64), ("first_family", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("ms", ctypes.c_double)]
+
+
+class Diagnosis:
+    """What plonk_prover_diagnose* reports: ok, rows = [(row, families, copy_wires)] ascending (at most `cap` of them),
+    and the plonk_unsat_info fields as attributes (info: the same as a dict, without the timing)."""
+
+    def __init__(self, rc: int, rows, info: "_UnsatInfo"):
+        self.ok = rc == PLONK_OK
+        self.rows = rows
+        self.rows_checked, self.rows_failing = info.rows_checked, info.rows_failing
+        self.family_rows = list(info.family_rows)
+        self.first_row, self.first_family = info.first_row, info.first_family   # 2^64 - 1 / 0 when no row fails
+        self.ms = info.ms
+
+    @property
+    def info(self) -> dict:
+        return dict(rows_checked=self.rows_checked, rows_failing=self.rows_failing, family_rows=self.family_rows,
+                    first_row=self.first_row, first_family=self.first_family)
+
+    def __repr__(self):
+        if self.ok:
+            return f"Diagnosis(ok, {self.rows_checked} rows)"
+        return (f"Diagnosis({self.rows_failing} of {self.rows_checked} rows fail; first: row {self.first_row}, "
+                f"{IDENTITY_FAMILIES[self.first_family]})")
 
 
 class _BlobInfo(ctypes.Structure):
@@ -268,6 +314,9 @@ def load_library() -> ctypes.CDLL:
     lib.plonk_comm_set_library.argtypes = [ctypes.c_char_p]
     lib.plonk_comm_library.argtypes = [vp, u64]
     lib.plonk_prover_set_version.argtypes = [vp, ci]
+    lib.plonk_prover_diagnose.argtypes = [vp, ctypes.POINTER(vp), vp, vp, u64, vp, u64, vp]
+    lib.plonk_prover_diagnose_dev.argtypes = [vp, vp, vp, vp, u64, vp, u64, vp]
+    lib.plonk_prover_diagnose_witnesses.argtypes = [vp, vp, u64, vp, vp, u64, vp, u64, vp]
     _lib = lib
     return lib
 
@@ -870,6 +919,39 @@ class Prover:
         self.ctx._check(self.ctx.lib.plonk_prover_prove_dev(self.handle, wires_ptr, idx, val, cnt,
                                                             blinders_mont, proof))
         return proof.raw
+
+    # ---- witness diagnosis (plonk_prover_diagnose*): which rows fail which identity family / copy constraint
+    def _diagnose(self, call, cap: int) -> Diagnosis:
+        out = (_UnsatRow * cap)() if cap else None
+        info = _UnsatInfo()
+        rc = call(out, cap, ctypes.byref(info))
+        if rc not in (PLONK_OK, -6):
+            self.ctx._check(rc)
+        got = min(cap, info.rows_failing)
+        return Diagnosis(rc, [(out[i].row, out[i].families, out[i].copy_wires) for i in range(got)], info)
+
+    def diagnose(self, wires, public_inputs=None, cap: int = 64) -> Diagnosis:
+        """wires: 4 sequences of ints (length <= size, zero padded) or of size x 32 Montgomery bytes."""
+        n = self.size
+        bufs = []
+        for w in wires:
+            raw = w if isinstance(w, (bytes, bytearray)) else fr_to_bytes_mont(list(w) + [0] * (n - len(w)))
+            assert len(raw) == 32 * n
+            bufs.append(ctypes.create_string_buffer(bytes(raw), len(raw)))
+        arr = (ctypes.c_void_p * 4)(*[ctypes.cast(b, ctypes.c_void_p) for b in bufs])
+        idx, val, cnt = self._pi(public_inputs)
+        return self._diagnose(lambda out, c, info: self.ctx.lib.plonk_prover_diagnose(self.handle, arr, idx, val, cnt, out, c, info), cap)
+
+    def diagnose_dev(self, wires_ptr: int, public_inputs=None, cap: int = 64) -> Diagnosis:
+        """the 4 x size wire columns already resident in HBM (contiguous a|b|c|d), as prove_dev takes them"""
+        idx, val, cnt = self._pi(public_inputs)
+        return self._diagnose(lambda out, c, info: self.ctx.lib.plonk_prover_diagnose_dev(self.handle, wires_ptr, idx, val, cnt, out, c, info), cap)
+
+    def diagnose_witnesses(self, values, public_inputs=None, cap: int = 64) -> Diagnosis:
+        """from the witness values (ints or Montgomery bytes) on a compiled prover, as prove_witnesses takes them"""
+        raw = bytes(values) if isinstance(values, (bytes, bytearray)) else fr_to_bytes_mont(values)
+        idx, val, cnt = self._pi(public_inputs)
+        return self._diagnose(lambda out, c, info: self.ctx.lib.plonk_prover_diagnose_witnesses(self.handle, raw, len(raw) // 32, idx, val, cnt, out, c, info), cap)
 
     def peek(self, which: int, offset: int, count: int) -> list[int]:
         out = ctypes.create_string_buffer(32 * count)

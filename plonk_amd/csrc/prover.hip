@@ -21,7 +21,10 @@
 #include "finish_pool.hpp"
 #include "widgets.hpp"
 #include "permutation.hpp"
+#include "diagnose.hpp"
 
+static_assert(plonk::DQ_M == plonk::QS_M && plonk::DQ_ARITH == plonk::QS_ARITH && plonk::DQ_VAR == plonk::QS_VAR &&
+              plonk::DQ_COUNT == plonk::QS_COUNT, "diagnose_core.hpp selector ids");
 static_assert(plonk::WQS_RANGE == plonk::QS_RANGE && plonk::WQS_LOGIC == plonk::QS_LOGIC && plonk::WQS_FIXED == plonk::QS_FIXED &&
               plonk::WQS_VAR == plonk::QS_VAR && plonk::WQS_COUNT == plonk::QS_COUNT, "widgets.hpp selector ids");
 
@@ -122,6 +125,11 @@ struct Prover {
   uint32_t* wire_idx = nullptr;    // [4][constraints]
   uint64_t witnesses = 0;
   Fr* wit_vals = nullptr;          // [witnesses] staging of one proof's values
+  // witness diagnosis (plonk_prover_diagnose*): proof-independent, built by the FIRST diagnose call and freed with the prover —
+  // a prover that never diagnoses allocates neither
+  Fr* diag_sel = nullptr;          // [non-zero selectors][n] selector values over the proving domain
+  const Fr* diag_sel_ptr[QS_COUNT] = {};   // selector id -> its slice of diag_sel (nullptr: identically zero)
+  uint32_t* diag_pos = nullptr;    // [4][n] sigma_n decoded into packed wire positions (permutation.hpp)
 };
 
 // ---- host helpers -------------------------------------------------------------------
@@ -380,7 +388,7 @@ static void prover_free(Prover* p) {
   for (void* b : bufs) if (b) (void)hipFree(b);
   for (void* b : {(void*)p->fold, (void*)p->Fbuf, (void*)p->send, (void*)p->recv, (void*)p->agg2, (void*)p->scratch2, (void*)p->wscal}) if (b) (void)hipFree(b);
   srs_table_release(p->c, p->lag_table, p->lag_rows, p->lag_n);   // gives the bytes back to the context's table budget
-  for (void* b : {(void*)p->wire_idx, (void*)p->wit_vals}) if (b) (void)hipFree(b);
+  for (void* b : {(void*)p->wire_idx, (void*)p->wit_vals, (void*)p->diag_sel, (void*)p->diag_pos}) if (b) (void)hipFree(b);
   for (int k = 0; k < 8; ++k) { ntt_coset_free(&p->cs_fwd[k]); ntt_coset_free(&p->cs_inv[k]); }
   if (p->ev_ready) (void)hipEventDestroy(p->ev_ready);
   if (p->ev_side) (void)hipEventDestroy(p->ev_side);
@@ -832,7 +840,8 @@ static bool quotient_identity_holds(const Fr& numerator_at_z, const Evals& ev, c
   return numerator_at_z == expect;
 }
 // the sparse public inputs -> dense evaluation vector -> PI(X) in coefficient form, on the current stream
-static int public_input_polynomial(Prover* p, const uint64_t* pi_idx, const Fr* pi_val, uint64_t pi_count, Fr* ntt_tmp) {
+// the sparse public inputs on the device (p->pi_idx_dev / pi_val_dev), on the current stream
+static int public_input_stage(Prover* p, const uint64_t* pi_idx, const Fr* pi_val, uint64_t pi_count) {
   Ctx* c = p->c;
   const uint64_t n = p->n;
   if (pi_count > p->pi_cap) {
@@ -844,8 +853,13 @@ static int public_input_polynomial(Prover* p, const uint64_t* pi_idx, const Fr* 
   for (uint64_t i = 0; i < pi_count; ++i) if (pi_idx[i] >= n) return (plonk::set_last_error("invalid argument", "public input row beyond the domain", __FILE__, __LINE__), PLONK_ERR_ARG);
   HIP_TRY(hipMemcpyAsync(p->pi_idx_dev, pi_idx, sizeof(uint64_t) * pi_count, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(p->pi_val_dev, pi_val, sizeof(Fr) * pi_count, hipMemcpyHostToDevice, c->stream));
+  return PLONK_OK;
+}
+static int public_input_polynomial(Prover* p, const uint64_t* pi_idx, const Fr* pi_val, uint64_t pi_count, Fr* ntt_tmp) {
+  Ctx* c = p->c;
+  PTRY(public_input_stage(p, pi_idx, pi_val, pi_count));
   PTRY(poly_scatter_pi(c, p->pipoly, p->pi_idx_dev, p->pi_val_dev, pi_count));
-  return ntt_device(c, p->pipoly, p->pipoly, ntt_tmp, p->logn, true, false, n);
+  return ntt_device(c, p->pipoly, p->pipoly, ntt_tmp, p->logn, true, false, p->n);
 }
 
 static int prover_prove_sharded(Prover* p, const Fr* wires_dev, const uint64_t* pi_idx, const Fr* pi_val, uint64_t pi_count,
@@ -2147,6 +2161,162 @@ int plonk_prover_prove(plonk_prover* pr, const uint64_t* const wires[4], const u
   p->wires_pending = false;
   (void)hipStreamSynchronize(c->copy_stream);
   return rc;
+  });
+}
+
+}  // extern "C"
+
+// ---- witness diagnosis (plonk_prover_diagnose*) ------------------------------------------------------------------------
+// Which rows of a wire assignment fail which gate identity or copy constraint: the exact, row-level answer the quotient
+// identity at the evaluation challenge cannot give (by then the rows are folded into one polynomial).  No group operation
+// and no challenge: the selector VALUES over the proving domain (forward size-n transforms of the key polynomials) and the
+// sigma evaluations decoded back into wire positions are proof-independent and cached in the prover by the first call;
+// a call then runs three kernels (diagnose.hip) over the wire columns in the prover's per-proof scratch — `cos` for the
+// masks, the scan and the records, `scratch` for the dense public inputs — and copies back one counter block and at most
+// `cap` records.  Nothing a proof reads between calls is touched, so the next proof is bit-identical.
+namespace plonk {
+static int diagnose_cache(Prover* p) {
+  Ctx* c = p->c;
+  const uint64_t n = p->n, np = p->np;
+  if (!p->diag_sel) {
+    uint64_t cnt = 0;
+    for (int k = 0; k < QS_COUNT; ++k) cnt += p->has[k] ? 1 : 0;
+    Fr* buf = nullptr;
+    hipError_t e = hipMalloc((void**)&buf, sizeof(Fr) * n * (cnt ? cnt : 1));
+    if (e != hipSuccess) return (set_last_error("hipMalloc diag_sel", hipGetErrorString(e), __FILE__, __LINE__), PLONK_ERR_HIP);
+    uint64_t at = 0;
+    for (int k = 0; k < QS_COUNT; ++k) {
+      p->diag_sel_ptr[k] = nullptr;
+      if (!p->has[k]) continue;
+      Fr* dst = buf + at++ * n;
+      const int rc = ntt_device(c, p->polys + k * np, dst, p->tmp8, p->logn, false, false, p->poly_len[k]);
+      if (rc) { (void)hipStreamSynchronize(c->stream); (void)hipFree(buf); return rc; }
+      p->diag_sel_ptr[k] = dst;
+    }
+    p->diag_sel = buf;
+  }
+  if (!p->diag_pos) {
+    uint32_t* pos = nullptr;
+    hipError_t e = hipMalloc((void**)&pos, sizeof(uint32_t) * 4 * n);
+    if (e != hipSuccess) return (set_last_error("hipMalloc diag_pos", hipGetErrorString(e), __FILE__, __LINE__), PLONK_ERR_HIP);
+    const int rc = diag_sigma_decode(c, p->sigma_n, pos, n, p->logn);
+    if (rc) { (void)hipFree(pos); return rc; }
+    p->diag_pos = pos;
+  }
+  return PLONK_OK;
+}
+// refusals shared by the three entry points (before any device work)
+static int diagnose_guard(const Prover* p, const char* api_fn) {
+  if (p->world > 1) return (set_last_error("a sharded prover holds residue classes and key slices, not the whole circuit; diagnose where the whole prover is", api_fn, __FILE__, __LINE__), PLONK_ERR_STATE);
+  return PLONK_OK;
+}
+static int prover_diagnose(Prover* p, const Fr* wires_dev, const uint64_t* pi_idx, const Fr* pi_val, uint64_t pi_count,
+                           plonk_unsat_row* out, uint64_t cap, plonk_unsat_info* info,
+                           std::chrono::steady_clock::time_point t0) {
+  Ctx* c = p->c;
+  const uint64_t n = p->n;
+  PTRY(diagnose_cache(p));
+  DiagArgs a{};
+  a.n = n;
+  a.wires = wires_dev;
+  if (pi_count) {
+    PTRY(public_input_stage(p, pi_idx, pi_val, pi_count));
+    PTRY(poly_fill_zero(c, p->scratch, n));
+    PTRY(poly_scatter_pi(c, p->scratch, p->pi_idx_dev, p->pi_val_dev, pi_count));
+    a.pi = p->scratch;
+  }
+  for (int k = 0; k < QS_COUNT; ++k) a.sel[k] = p->diag_sel_ptr[k];
+  a.pos = p->diag_pos;
+  // carve the report's buffers out of `cos` (6 x quotient-domain scalars: >= 768 n bytes)
+  const uint64_t nb = diag_blocks(n), kept = cap < n ? cap : n;
+  auto up16 = [](uint64_t v) { return (v + 15) & ~15ull; };
+  const uint64_t off_ctr = up16(kept * sizeof(plonk_unsat_row)), off_mask = off_ctr + up16(sizeof(DiagCounters));
+  const uint64_t off_cnt = off_mask + up16(4 * n), off_off = off_cnt + up16(4 * nb), end = off_off + up16(4 * nb);
+  if (end > 6 * p->qn * sizeof(Fr)) return (set_last_error("plonk_prover_diagnose", "scratch accounting", __FILE__, __LINE__), PLONK_ERR_STATE);
+  uint8_t* base = (uint8_t*)p->cos;
+  a.out = (plonk_unsat_row*)base;
+  a.ctr = (DiagCounters*)(base + off_ctr);
+  a.mask = (uint32_t*)(base + off_mask);
+  a.block_cnt = (uint32_t*)(base + off_cnt);
+  a.block_off = (uint32_t*)(base + off_off);
+  a.cap = kept;
+  PTRY(diag_report(c, a));
+  DiagCounters ctr;
+  HIP_TRY(hipMemcpyAsync(&ctr, a.ctr, sizeof ctr, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  const uint64_t written = ctr.failing < kept ? ctr.failing : kept;
+  if (written) {
+    HIP_TRY(hipMemcpyAsync(out, a.out, written * sizeof(plonk_unsat_row), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+  }
+  if (info) {
+    memset(info, 0, sizeof *info);
+    info->rows_checked = n;
+    info->rows_failing = ctr.failing;
+    for (int f = 0; f < 18; ++f) info->family_rows[f] = ctr.family[f];
+    info->first_row = ctr.failing ? ctr.first_row : UINT64_MAX;
+    info->first_family = 0;
+    if (ctr.failing) {
+      uint32_t f = 0;
+      while (f < 17 && !((ctr.first_families >> f) & 1u)) ++f;
+      info->first_family = f;
+    }
+    info->ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  }
+  return ctr.failing ? PLONK_ERR_UNSAT : PLONK_OK;
+}
+}  // namespace plonk
+
+extern "C" {
+
+int plonk_prover_diagnose_dev(plonk_prover* pr, const void* wires_dev, const uint64_t* pi_idx, const uint64_t* pi_val,
+                              uint64_t pi_count, plonk_unsat_row* out, uint64_t cap, plonk_unsat_info* info) {
+  const char* const api_fn = __func__;
+  return plonk::api_guard(api_fn, [&]() -> int {
+  const auto t0 = std::chrono::steady_clock::now();
+  if (!pr || !wires_dev || (cap && !out) || (pi_count && (!pi_idx || !pi_val))) return (plonk::set_last_error("invalid argument", api_fn, __FILE__, __LINE__), PLONK_ERR_ARG);
+  CTX_ENTER(pr->ctx->c, api_fn);
+  HIP_TRY(hipSetDevice(pr->ctx->c.device));
+  PTRY(diagnose_guard(pr->p, api_fn));
+  return prover_diagnose(pr->p, (const Fr*)wires_dev, pi_idx, (const Fr*)pi_val, pi_count, out, cap, info, t0);
+  });
+}
+
+int plonk_prover_diagnose_witnesses(plonk_prover* pr, const uint64_t* witnesses, uint64_t count, const uint64_t* pi_idx,
+                                    const uint64_t* pi_val, uint64_t pi_count, plonk_unsat_row* out, uint64_t cap,
+                                    plonk_unsat_info* info) {
+  const char* const api_fn = __func__;
+  return plonk::api_guard(api_fn, [&]() -> int {
+  const auto t0 = std::chrono::steady_clock::now();
+  if (!pr || (cap && !out) || (count && !witnesses) || (pi_count && (!pi_idx || !pi_val))) return (plonk::set_last_error("invalid argument", api_fn, __FILE__, __LINE__), PLONK_ERR_ARG);
+  CTX_ENTER(pr->ctx->c, api_fn);
+  HIP_TRY(hipSetDevice(pr->ctx->c.device));
+  plonk::Prover* p = pr->p;
+  Ctx* c = p->c;
+  PTRY(diagnose_guard(p, api_fn));
+  if (!p->wire_idx) return (plonk::set_last_error("prover was not built by plonk_compile: it has no wire -> witness table", api_fn, __FILE__, __LINE__), PLONK_ERR_STATE);
+  if (count != p->witnesses) return (plonk::set_last_error("invalid argument", "witness count differs from the compiled circuit's", __FILE__, __LINE__), PLONK_ERR_ARG);
+  if (count) HIP_TRY(hipMemcpyAsync(p->wit_vals, witnesses, sizeof(Fr) * count, hipMemcpyHostToDevice, c->stream));
+  PTRY(poly_gather_wires(c, p->wire_idx, p->wit_vals, p->wires, p->constraints, p->n));
+  return prover_diagnose(p, p->wires, pi_idx, (const Fr*)pi_val, pi_count, out, cap, info, t0);
+  });
+}
+
+int plonk_prover_diagnose(plonk_prover* pr, const uint64_t* const wires[4], const uint64_t* pi_idx, const uint64_t* pi_val,
+                          uint64_t pi_count, plonk_unsat_row* out, uint64_t cap, plonk_unsat_info* info) {
+  const char* const api_fn = __func__;
+  return plonk::api_guard(api_fn, [&]() -> int {
+  const auto t0 = std::chrono::steady_clock::now();
+  if (!pr || !wires || (cap && !out) || (pi_count && (!pi_idx || !pi_val))) return (plonk::set_last_error("invalid argument", api_fn, __FILE__, __LINE__), PLONK_ERR_ARG);
+  for (int k = 0; k < 4; ++k) if (!wires[k]) return (plonk::set_last_error("invalid argument", api_fn, __FILE__, __LINE__), PLONK_ERR_ARG);
+  CTX_ENTER(pr->ctx->c, api_fn);
+  HIP_TRY(hipSetDevice(pr->ctx->c.device));
+  plonk::Prover* p = pr->p;
+  Ctx* c = p->c;
+  PTRY(diagnose_guard(p, api_fn));
+  for (int k = 0; k < 4; ++k)
+    HIP_TRY(hipMemcpyAsync(p->wires + k * p->n, wires[k], sizeof(Fr) * p->n, hipMemcpyHostToDevice, c->stream));
+  return prover_diagnose(p, p->wires, pi_idx, (const Fr*)pi_val, pi_count, out, cap, info, t0);
   });
 }
 
