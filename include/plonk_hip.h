@@ -14,6 +14,8 @@
  *                                 CommitKey::commit, key.rs:376-388, and the 4-way
  *                                 rayon::join fan-out of Prover::commit_polynomials,
  *                                 src/compiler/prover.rs:187-210
+ *   plonk_kzg_open / _flatten /   CommitKey::compute_aggregate_witness + commit, AggregateProof::flatten and
+ *   _batch_check                  OpeningKey::batch_check, key.rs:394-417, 661-707, proof.rs:69-109
  *
  * Data conventions (bit-identical to the reference's in-memory types):
  *   Fr  = BlsScalar.0 : 4 x uint64 little-endian limbs, Montgomery form, R = 2^256.
@@ -606,6 +608,74 @@ int plonk_srs_load_public_parameters(plonk_ctx* ctx, const uint8_t* bytes, uint6
                                      int mode, uint8_t opening_key_out[240] /* may be NULL */,
                                      uint64_t* points_loaded /* may be NULL */);
 
+/* ---- KZG10 openings -----------------------------------------------------------------------------
+ * The part of the reference's commitment scheme that PROVES something about a commitment: CommitKey::compute_aggregate_witness,
+ * open_single / open_multiple, AggregateProof::flatten and OpeningKey::batch_check (src/commitment_scheme/kzg10/key.rs:394-417,
+ * 571-591, 661-707, 724-809; proof.rs:15-111).  Scalars are Fr in Montgomery limbs, commitments 48-byte compressed G1
+ * (Commitment::to_bytes), errors the codes above.
+ *
+ * plonk_kzg_open: `count` polynomials in coefficient form (host pointers; lengths may differ, zero lengths are allowed,
+ *   count <= 65536), opened at `point`:
+ *     evaluations[i] = p_i(point);  commitments[i] = commit(p_i) (NULL skips them: 48 bytes each otherwise);
+ *     witness48 = commit of (sum_i v^i p_i) / (X - point) with the remainder dropped — compute_aggregate_witness followed by
+ *     commit.  count == 1 is open_single (v_challenge may be NULL then: the weight is 1); count == 0 gives the identity witness
+ *     (Polynomial::zero()).  point == 0 works (the quotient is a shift).
+ *   Degrees are checked on the length WITHOUT trailing zeros (Polynomial::from_coefficients_vec, then commit):
+ *   PLONK_ERR_DEGREE when that exceeds the commit key, PLONK_ERR_NO_SRS for any call with count > 0 before a key is loaded
+ *   (also when every polynomial is empty; count == 0 needs no key).  A context with a communicator holds only a range of
+ *   the key: PLONK_ERR_STATE.  An error leaves nothing of the call queued on the context's streams.  Every coefficient crosses HBM once per call (fold contribution and
+ *   evaluation partial in one pass); the host form stages the polynomials through two context-owned buffers of
+ *   max(longest polynomial, 2^16) coefficients, group after group, the upload of one group under the kernel of the one before,
+ *   so count x length is never resident.  The workspace grows on demand and is released with the context.  The call leaves
+ *   the context as it found it: the next proof of a prover on the same context is bit-identical.
+ * plonk_kzg_open_dev: the same with an array (host memory) of `count` DEVICE pointers on the context's GPU.
+ * plonk_kzg_flatten: AggregateProof::flatten (proof.rs:87-110): out.commitment = sum_i v^i C_i (on the device), out.evaluation =
+ *   sum_i v^i e_i, out.witness = witness48 unchanged.  PLONK_ERR_ARG for count == 0 (the reference underflows there),
+ *   PLONK_ERR_POINT for a commitment that is not a valid compressed G1 point, PLONK_ERR_DATA for a non-canonical scalar.
+ * plonk_kzg_key_create: OpeningKey::from_bytes + try_new on the 240 bytes g || h || x_h (key.rs:609-648), validated as
+ *   plonk_verifier_from_bytes validates its opening key (PLONK_ERR_DATA); g is decoded on the device, h and x_h are prepared
+ *   for the Miller loop once.  Destroy the key before its context.
+ * plonk_kzg_batch_check: OpeningKey::batch_check (key.rs:661-707) of `count` openings, proofs[k] at points[k]:
+ *     total_w = sum_k u^k W_k,  total_c = sum_k u^k C_k + sum_k (u^k z_k) W_k - (sum_k u^k v_k) g    (3 count + 1 terms, ONE
+ *     launch of the verifier's two-sum MSM), then e(-total_w, x_h) e(total_c, h) == 1 on the host.  count == 1 is the
+ *     reference's single `check`.  With u_override == NULL, u is the reference's batch_challenge on a fresh
+ *     Transcript::new(label): append_message("dom-sep", "kzg10-batch-check-v1"), append_u64("batch-len", count), per item
+ *     append_scalar("batch-point"), append_commitment("batch-polynomial-commitment"), append_scalar("batch-evaluation"),
+ *     append_commitment("batch-witness-commitment"), then challenge_scalar("batch-challenge").  A caller whose surrounding
+ *     transcript already has state derives u from ITS transcript the same way and passes it as u_override — a u the prover
+ *     of the openings could predict (a constant, a counter, anything fixed before the batch is) VOIDS the check.
+ *   PLONK_OK; PLONK_ERR_VERIFY for a failing batch and for count == 0 (key.rs:667); PLONK_ERR_POINT for a commitment that is
+ *   not a valid compressed G1 point (the identity is legal); PLONK_ERR_DATA for a non-canonical scalar.  No bisection: a
+ *   caller who wants per-item answers calls with count == 1.  info (may be NULL) is filled as plonk_verify_mixed fills it.
+ * plonk_srs_check: is the commit key the key's context holds (N points P_i) [tau^i] g for the tau of THIS opening key?
+ *     P_0 == g  and  e(sum_{i < N-1} r^i P_(i+1), h) == e(sum_{i < N-1} r^i P_i, x_h),
+ *   r = challenge_scalar("r") of a Merlin transcript "plonk-srs-check-v1" over append_message("seed", seed32),
+ *   append_u64("points", N), append_message("opening key", 240 bytes).  seed32 is the CALLER's fresh randomness, chosen after
+ *   the file under test is fixed: whoever wrote the file must not be able to predict it.  A wrong key passes with probability
+ *   at most N / q.  A file whose points are all on the curve and in the subgroup passes every other
+ *   check of this library although no proof made from it verifies; this call closes that hole.  PLONK_OK, PLONK_ERR_VERIFY on a
+ *   mismatch, PLONK_ERR_NO_SRS, PLONK_ERR_STATE on a context with a communicator, PLONK_ERR_ARG for a NULL argument (a key is
+ *   bound to the context it was created on, so "the key of another context" cannot be expressed). */
+typedef struct plonk_kzg_proof {   /* kzg10::Proof, proof.rs:15-23 */
+  uint8_t  commitment[48];         /* commitment_to_polynomial */
+  uint64_t evaluation[4];          /* evaluated_point */
+  uint8_t  witness[48];            /* commitment_to_witness */
+} plonk_kzg_proof;                 /* 128 bytes */
+typedef struct plonk_kzg_key plonk_kzg_key;   /* an OpeningKey bound to a context */
+int plonk_kzg_open(plonk_ctx* ctx, const uint64_t* const* polys, const uint64_t* lens, uint64_t count, const uint64_t point[4],
+                   const uint64_t* v_challenge /* 4 limbs; may be NULL when count <= 1 */, uint64_t* evaluations /* count x 4 */,
+                   uint8_t* commitments /* count x 48, or NULL */, uint8_t witness48[48]);
+int plonk_kzg_open_dev(plonk_ctx* ctx, const void* const* polys_dev, const uint64_t* lens, uint64_t count, const uint64_t point[4],
+                       const uint64_t* v_challenge, uint64_t* evaluations, uint8_t* commitments, uint8_t witness48[48]);
+int plonk_kzg_flatten(plonk_ctx* ctx, const uint8_t* commitments /* count x 48 */, const uint64_t* evaluations /* count x 4 */,
+                      uint64_t count, const uint64_t v[4], const uint8_t witness48[48], plonk_kzg_proof* out);
+int plonk_kzg_key_create(plonk_ctx* ctx, const uint8_t opening_key240[240], plonk_kzg_key** out);
+void plonk_kzg_key_destroy(plonk_kzg_key* key);
+int plonk_kzg_batch_check(plonk_kzg_key* key, const uint64_t* points /* count x 4 */, const plonk_kzg_proof* proofs, uint64_t count,
+                          const uint8_t* label, uint64_t label_len, const uint64_t* u_override /* 4 limbs or NULL */,
+                          plonk_verify_info* info);
+int plonk_srs_check(plonk_kzg_key* key, const uint8_t seed32[32]);
+
 /* ---- measurement --------------------------------------------------------------
  * When enabled, every launch of the dominant kernels is bracketed by a hipEvent
  * pair ON THE LIBRARY'S STREAM and accumulated per slot.  Slots:
@@ -619,6 +689,10 @@ int plonk_srs_load_public_parameters(plonk_ctx* ctx, const uint8_t* bytes, uint6
  *   synchronisations of a proof (six or seven for a rank of a sharded proof: the grand product's and the opening
  *   quotients' range totals are exchanged too) to the next launch (slot 8 included: the device's main stream is idle for that long),
  *   10 the time blocked in those synchronisations; 11 (a count, not a time) the helper threads each commitment group had.
+ *   plonk_kzg_open / _open_dev (device events): 12 the non-commitment front of an open — the trimmed-length kernel of resident
+ *   polynomials with its copies, the powers of v and every fold + evaluate launch (in the host form NOT the uploads the
+ *   launches wait for, nor the polynomial commitments between them); 13 Ruffini (or the shift at the point 0); 14 the witness
+ *   commitment, bit sums copied back included (its MSM kernels also count in slots 1 and 2).
  *   Slots 0 .. 31 are valid.
  *
  * Host threads.  A context starts up to 3 helper threads (none when the process may run on fewer than 8 CPUs: sched_getaffinity) with its first

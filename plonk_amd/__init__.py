@@ -7,6 +7,8 @@ libplonk_hip.so (include/plonk_hip.h):
                      (reference src/fft/domain.rs:166-232)
   Context.srs_load   CommitKey { powers_of_g } (src/commitment_scheme/kzg10/key.rs:37-41)
   Context.msm / commit   CommitKey::commit -> msm_variable_base (key.rs:376-388)
+  Context.kzg_open / kzg_flatten, KzgKey.batch_check   compute_aggregate_witness + commit, AggregateProof::flatten,
+                     OpeningKey::batch_check (key.rs:394-417, 661-707; proof.rs:69-109)
 
 There is NO CPU fallback: if the HIP library or a GPU is missing every call
 raises.  Nothing in this package imports `oracle/`.
@@ -62,6 +64,8 @@ EXPORTS = [
     "plonk_verifier_from_bytes", "plonk_verifier_destroy", "plonk_verifier_set_version", "plonk_verify", "plonk_verifier_last",
     "plonk_verify_mixed",
     "plonk_prover_diagnose", "plonk_prover_diagnose_dev", "plonk_prover_diagnose_witnesses",
+    "plonk_kzg_open", "plonk_kzg_open_dev", "plonk_kzg_flatten", "plonk_kzg_key_create", "plonk_kzg_key_destroy",
+    "plonk_kzg_batch_check", "plonk_srs_check",
 ]
 
 # what bit f of plonk_unsat_row.families / slot f of plonk_unsat_info.family_rows stands for (include/plonk_hip.h); the
@@ -177,6 +181,25 @@ class _VerifyInfo(ctypes.Structure):
     _fields_ = [("proofs", ctypes.c_uint64), ("msm_terms", ctypes.c_uint64), ("pairing_checks", ctypes.c_uint32),
                 ("rejected", ctypes.c_uint32), ("ms_decode", ctypes.c_double), ("ms_scalars", ctypes.c_double),
                 ("ms_msm", ctypes.c_double), ("ms_pairing", ctypes.c_double)]
+
+
+class KzgProof(ctypes.Structure):
+    """plonk_kzg_proof = kzg10::Proof (reference proof.rs:15-23): commitment to the polynomial (48-byte compressed), the
+    evaluation (Fr, Montgomery limbs), commitment to the witness.  `KzgProof.make(commitment, evaluation, witness)` takes the
+    evaluation as an int; `.value` gives it back."""
+    _fields_ = [("commitment", ctypes.c_uint8 * 48), ("evaluation", ctypes.c_uint64 * 4), ("witness", ctypes.c_uint8 * 48)]
+
+    @classmethod
+    def make(cls, commitment: bytes, evaluation: int, witness: bytes) -> "KzgProof":
+        p = cls()
+        ctypes.memmove(p.commitment, bytes(commitment), 48)
+        ctypes.memmove(p.evaluation, fr_to_bytes_mont([evaluation]), 32)
+        ctypes.memmove(p.witness, bytes(witness), 48)
+        return p
+
+    @property
+    def value(self) -> int:
+        return fr_from_bytes_mont(bytes(self.evaluation))[0]
 
 
 class _PublicParametersInfo(ctypes.Structure):
@@ -317,6 +340,15 @@ def load_library() -> ctypes.CDLL:
     lib.plonk_prover_diagnose.argtypes = [vp, ctypes.POINTER(vp), vp, vp, u64, vp, u64, vp]
     lib.plonk_prover_diagnose_dev.argtypes = [vp, vp, vp, vp, u64, vp, u64, vp]
     lib.plonk_prover_diagnose_witnesses.argtypes = [vp, vp, u64, vp, vp, u64, vp, u64, vp]
+    lib.plonk_kzg_open.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(u64), u64, vp, vp, vp, vp, vp]
+    lib.plonk_kzg_open_dev.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(u64), u64, vp, vp, vp, vp, vp]
+    lib.plonk_kzg_flatten.argtypes = [vp, vp, vp, u64, vp, vp, ctypes.POINTER(KzgProof)]
+    lib.plonk_kzg_key_create.argtypes = [vp, vp, ctypes.POINTER(vp)]
+    lib.plonk_kzg_key_destroy.argtypes = [vp]
+    lib.plonk_kzg_key_destroy.restype = None
+    lib.plonk_kzg_batch_check.argtypes = [vp, vp, vp, u64, vp, u64, vp, vp]
+    lib.plonk_srs_check.argtypes = [vp, vp]
+    lib.plonk_test_kzg_last.argtypes = [vp, vp, vp]   # test hook of kzg.hip, not in the header
     _lib = lib
     return lib
 
@@ -569,6 +601,39 @@ class Context:
         return self.msm(c)
 
     # ---- device-resident API ----------------------------------------------------
+    def _kzg_open(self, fn, ptrs, lens, point, v, commitments):
+        count = len(lens)
+        parr = (ctypes.c_void_p * max(count, 1))(*ptrs)
+        larr = (ctypes.c_uint64 * max(count, 1))(*lens)
+        evals = ctypes.create_string_buffer(32 * max(count, 1))
+        comms = ctypes.create_string_buffer(48 * max(count, 1)) if commitments else None
+        wit = ctypes.create_string_buffer(48)
+        vb = fr_to_bytes_mont([v]) if v is not None else None
+        self._check(fn(self.handle, parr, larr, count, fr_to_bytes_mont([point]), vb, evals, comms, wit))
+        return (fr_from_bytes_mont(evals.raw[:32 * count]),
+                [comms.raw[48 * i:48 * i + 48] for i in range(count)] if commitments else None, wit.raw)
+
+    def kzg_open(self, polys, point: int, v: "int | None" = None, commitments: bool = True):
+        """plonk_kzg_open: open the polynomials (coefficient lists of ints, or Montgomery bytes) at `point` ->
+        (evaluations, commitments or None, witness): p_i(point), the 48-byte commit(p_i), and the 48-byte commitment of
+        (sum_i v^i p_i) / (X - point) — CommitKey::compute_aggregate_witness + commit (reference key.rs:394-417).  One
+        polynomial is open_single (v may be None)."""
+        bufs = [p if isinstance(p, (bytes, bytearray)) else fr_to_bytes_mont(p) for p in polys]
+        keep = [ctypes.create_string_buffer(bytes(b), len(b)) if b else None for b in bufs]
+        ptrs = [ctypes.cast(k, ctypes.c_void_p).value if k is not None else None for k in keep]
+        return self._kzg_open(self.lib.plonk_kzg_open, ptrs, [len(b) // 32 for b in bufs], point, v, commitments)
+
+    def kzg_open_dev(self, ptrs, lens, point: int, v: "int | None" = None, commitments: bool = True):
+        """plonk_kzg_open_dev: the same for polynomials resident in HBM (device pointers, coefficients each)."""
+        return self._kzg_open(self.lib.plonk_kzg_open_dev, list(ptrs), list(lens), point, v, commitments)
+
+    def kzg_flatten(self, commitments, evaluations, v: int, witness: bytes) -> "KzgProof":
+        """plonk_kzg_flatten = AggregateProof::flatten (reference proof.rs:69-109)."""
+        out = KzgProof()
+        self._check(self.lib.plonk_kzg_flatten(self.handle, b"".join(bytes(c) for c in commitments), fr_to_bytes_mont(evaluations),
+                                               len(commitments), fr_to_bytes_mont([v]), bytes(witness), ctypes.byref(out)))
+        return out
+
     def _verify_msm(self, points, scalars):
         """TEST HOOK: the device MSM of plonk_verify (verify.hip) on affine points (None = identity) and integer scalars;
         returns the affine sum.  Not part of the C API."""
@@ -1031,6 +1096,75 @@ class Verifier:
         if getattr(self, "handle", None):
             if getattr(self.ctx, "handle", None):
                 self.ctx.lib.plonk_verifier_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def kzg_flatten(ctx: Context, commitments, evaluations, v: int, witness: bytes) -> KzgProof:
+    """AggregateProof::flatten on `ctx` (Context.kzg_flatten)."""
+    return ctx.kzg_flatten(commitments, evaluations, v, witness)
+
+
+class KzgKey:
+    """An OpeningKey (240 bytes g || h || x_h, OpeningKey::to_bytes) bound to a context: plonk_kzg_key_create validates it like
+    OpeningKey::from_bytes (raises InvalidData).  `batch_check` is OpeningKey::batch_check (reference key.rs:661-707),
+    `srs_check` tests the context's commit key against this key.  Destroyed before its context, like a Prover."""
+
+    def __init__(self, ctx: Context, opening_key: bytes):
+        if len(opening_key) != 240:
+            raise ValueError("an opening key is 240 bytes")
+        self.ctx = ctx
+        h = ctypes.c_void_p()
+        ctx._check(ctx.lib.plonk_kzg_key_create(ctx.handle, bytes(opening_key), ctypes.byref(h)))
+        self.handle = h
+        ctx._provers.add(self)
+
+    def batch_check_code(self, points, proofs, label: bytes = b"", u: "int | None" = None):
+        """(return code of plonk_kzg_batch_check, plonk_verify_info as a dict)"""
+        points, proofs = list(points), list(proofs)
+        if len(points) != len(proofs):
+            raise ValueError("one point per proof")
+        arr = (KzgProof * max(len(proofs), 1))(*proofs)
+        info = _VerifyInfo()
+        rc = self.ctx.lib.plonk_kzg_batch_check(self.handle, fr_to_bytes_mont(points), arr, len(proofs), label, len(label),
+                                                fr_to_bytes_mont([u]) if u is not None else None, ctypes.byref(info))
+        return rc, {k: getattr(info, k) for k, _ in info._fields_}
+
+    def batch_check(self, points, proofs, label: bytes = b"", u: "int | None" = None) -> bool:
+        """True when every opening proofs[k] at points[k] holds, False when the batch does not verify (PLONK_ERR_VERIFY, an
+        empty batch included).  Malformed input raises like every other error: a commitment that is no compressed G1 point
+        (PLONK_ERR_POINT), a non-canonical scalar (PLONK_ERR_DATA) — `batch_check_code` returns the bare code instead.  `u`
+        replaces the challenge the library derives from a fresh transcript over `label` — for a caller whose own transcript
+        already has state; a predictable u voids the check."""
+        rc, _ = self.batch_check_code(points, proofs, label, u)
+        if rc not in (PLONK_OK, -12):
+            self.ctx._check(rc)
+        return rc == PLONK_OK
+
+    def srs_check(self, seed: bytes) -> bool:
+        """plonk_srs_check: is the context's commit key the powers of this opening key's tau?  seed: 32 fresh random bytes
+        chosen after the key file was fixed."""
+        if len(seed) != 32:
+            raise ValueError("seed is 32 bytes")
+        rc = self.ctx.lib.plonk_srs_check(self.handle, bytes(seed))
+        if rc not in (PLONK_OK, -12):
+            self.ctx._check(rc)
+        return rc == PLONK_OK
+
+    def _last_challenges(self):
+        u, r = ctypes.create_string_buffer(32), ctypes.create_string_buffer(32)
+        self.ctx._check(self.ctx.lib.plonk_test_kzg_last(self.handle, u, r))
+        return fr_from_bytes_mont(u.raw)[0], fr_from_bytes_mont(r.raw)[0]
+
+    def close(self):
+        if getattr(self, "handle", None):
+            if getattr(self.ctx, "handle", None):
+                self.ctx.lib.plonk_kzg_key_destroy(self.handle)
             self.handle = None
 
     def __del__(self):

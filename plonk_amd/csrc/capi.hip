@@ -143,6 +143,19 @@ static int ensure_ntt_staging(Ctx* c, uint64_t n) {
   return PLONK_OK;
 }
 
+int msm_group_sums(Ctx* c, const Fr* const* scalars_dev, const uint64_t* m, int cnt, G1* sums) {
+  G1* res[MSM_MAX_BATCH];
+  for (int k = 0; k < cnt; ++k) res[k] = (G1*)c->msm.result + (size_t)k * MSM_BIT_SUMS;
+  const int rc = msm_batch_device(c, scalars_dev, m, cnt, res, true);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(c->msm.result_host, c->msm.result, sizeof(G1) * MSM_BIT_SUMS * cnt, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  for (int k = 0; k < cnt; ++k)
+    sums[k] = finish_bit_sums(reinterpret_cast<const G1*>(c->msm.result_host) + (size_t)k * MSM_BIT_SUMS, c->msm.last_rowbits,
+                              c->srs_rows == MSM_ROWS_BITPOS);
+  return PLONK_OK;
+}
+
 static int ensure_scalar_staging(Ctx* c, uint64_t m) {
   MsmWork& w = c->msm;
   if (m <= w.cap_stage) return PLONK_OK;
@@ -421,6 +434,7 @@ void plonk_ctx_destroy(plonk_ctx* ctx) {
   }
   (void)hipStreamSynchronize(c.stream);
   verify_ws_release(&c);
+  kzg_ws_release(&c);
   for (auto& kv : c.ntt_tables) {
     NttTables* t = kv.second;
     (void)hipFree(t->tw_lo); (void)hipFree(t->tw_hi); (void)hipFree(t->tw_lo_scaled);
@@ -765,12 +779,10 @@ int plonk_msm(plonk_ctx* ctx, const uint64_t* scalars, uint64_t m, uint8_t out_x
   // same tail as plonk_msm_batch: the 17 bit sums come back and the host finishes (15-term Horner chain + one Fp
   // inversion) — ~25 dependent additions and a Fermat inversion that a single GPU lane would otherwise serialise
   const Fr* sc = c.msm.scalars_stage;
-  G1* res = (G1*)c.msm.result;
-  rc = msm_batch_device(&c, &sc, &m, 1, &res, true);
+  G1 sum;
+  rc = msm_group_sums(&c, &sc, &m, 1, &sum);
   if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(c.msm.result_host, c.msm.result, sizeof(G1) * MSM_BIT_SUMS, hipMemcpyDeviceToHost, c.stream));
-  HIP_TRY(hipStreamSynchronize(c.stream));
-  xyzz_to_affine97_host(finish_bit_sums(reinterpret_cast<const G1*>(c.msm.result_host), c.msm.last_rowbits, c.srs_rows == MSM_ROWS_BITPOS), out_xy_inf);
+  xyzz_to_affine97_host(sum, out_xy_inf);
   return PLONK_OK;
   });
 }
@@ -801,20 +813,15 @@ int plonk_msm_batch(plonk_ctx* ctx, const uint64_t* const* scalars, const uint64
     const int cnt = count - k0 < MSM_MAX_BATCH ? count - k0 : MSM_MAX_BATCH;
     const Fr* sc[MSM_MAX_BATCH];
     uint64_t ms[MSM_MAX_BATCH];
-    G1* res[MSM_MAX_BATCH];
     for (int k = 0; k < cnt; ++k) {
       Fr* dst = c.msm.scalars_stage + (uint64_t)k * (mmax ? mmax : 1);
       if (m[k0 + k]) HIP_TRY(hipMemcpyAsync(dst, scalars[k0 + k], sizeof(Fr) * m[k0 + k], hipMemcpyHostToDevice, c.stream));
       sc[k] = dst;
       ms[k] = m[k0 + k];
-      res[k] = (G1*)c.msm.result + (size_t)k * MSM_BIT_SUMS;
     }
-    rc = msm_batch_device(&c, sc, ms, cnt, res, true);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(c.msm.result_host, c.msm.result, sizeof(G1) * MSM_BIT_SUMS * cnt, hipMemcpyDeviceToHost, c.stream));
-    HIP_TRY(hipStreamSynchronize(c.stream));
     G1 sums[MSM_MAX_BATCH];
-    for (int k = 0; k < cnt; ++k) sums[k] = finish_bit_sums(reinterpret_cast<const G1*>(c.msm.result_host) + (size_t)k * MSM_BIT_SUMS, c.msm.last_rowbits, c.srs_rows == MSM_ROWS_BITPOS);
+    rc = msm_group_sums(&c, sc, ms, cnt, sums);
+    if (rc) return rc;
     batch_xyzz_to_affine97(sums, cnt, reinterpret_cast<uint8_t (*)[97]>(out + 97 * (size_t)k0));
   }
   return PLONK_OK;

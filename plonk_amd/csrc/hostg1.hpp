@@ -171,6 +171,14 @@ struct H1 {
   Fp64 X, Y, ZZ, ZZZ;
   bool inf() const { return fp64_is_zero(ZZ); }
 };
+// a device-format XYZZ point (canonical Montgomery coordinates) as the host type
+static H1 h1_of_g1(const G1& q) {
+  H1 h;
+  memset(&h, 0, sizeof h);
+  if (q.is_identity()) return h;
+  memcpy(h.X.l, q.X.l, 48); memcpy(h.Y.l, q.Y.l, 48); memcpy(h.ZZ.l, q.ZZ.l, 48); memcpy(h.ZZZ.l, q.ZZZ.l, 48);
+  return h;
+}
 static H1 h1_dbl(const H1& p) {
   if (p.inf()) return p;
   const Fp64 U = fp64_add(p.Y, p.Y), V = fp64_mul(U, U), W = fp64_mul(U, V), S = fp64_mul(p.X, V);

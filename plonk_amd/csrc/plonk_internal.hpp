@@ -234,10 +234,11 @@ struct Ctx {
   bool comm_loopback = false;      // measurement only: collectives return the rank's own contribution (plonk_comm_measure_loopback)
   void* finish_pool = nullptr;     // FinishPool* (finish_pool.hpp), created by the first commitment group of a prover (prover.hip), freed by finish_pool_release
   void* verify_ws = nullptr;       // MixedWork* (verify.hip): plonk_verify_mixed's grow-only device workspace, freed by verify_ws_release
+  void* kzg_ws = nullptr;          // KzgWork* (kzg.hip): the grow-only workspace of the KZG10 opening calls, freed by kzg_ws_release
   // instrumentation: hipEvent pairs around the dominant kernels
   bool profile = false;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  static constexpr int PROF_SLOTS = 32;   // 0-7: the bench line's slots; 8-10: HOST time of prove() (prover.hip HostGap), 11: helper threads per commitment group (a count); 16-21 / 24-29: MSM phases of groups of >= 3 / <= 2 commitments (PLONK_PROF_FINE=1)
+  static constexpr int PROF_SLOTS = 32;   // 0-7: the bench line's slots; 8-10: HOST time of prove() (prover.hip HostGap), 11: helper threads per commitment group (a count); 12-14: plonk_kzg_open (fold + evaluate, Ruffini, witness commitment); 16-21 / 24-29: MSM phases of groups of >= 3 / <= 2 commitments (PLONK_PROF_FINE=1)
   double acc_ms[PROF_SLOTS] = {0};
   uint64_t acc_n[PROF_SLOTS] = {0};
 };
@@ -327,6 +328,27 @@ int xyzz_to_affine97_device(Ctx* c, const G1* in_dev, uint8_t* out97_dev);
 // host-side affine normalisation of an XYZZ result: out = x || y || infinity flag
 void xyzz_to_affine97_host(const G1& p, uint8_t out[97]);
 int msm_reserve(Ctx* c, uint64_t m);
+
+// verify.hip: what the proof verifier and the KZG opening checks (kzg.hip) share.  H1 / G1Aff64 / G2Prepared are the host
+// types of hostg1.hpp / hostpairing.hpp; a caller includes those.
+struct H1;
+struct G1Aff64;
+struct G2Prepared;
+enum : int { VDEC_OK = 0, VDEC_IDENTITY = 1, VDEC_BAD = 2 };   // what verify_decode_kernel found a compressed commitment to be
+static constexpr uint32_t VERIFY_MSM_MAX_BLOCKS = 512;          // msm_run's part_dev holds 2 * this many G1
+// n compressed commitments from the host -> comp_dev, decoded and subgroup-checked into pts_dev / kind_dev; st: the kinds
+int decode_points(Ctx* c, const uint8_t* comp_host, uint32_t n, uint8_t* comp_dev, G1Affine* pts_dev, int32_t* kind_dev,
+                  std::vector<int32_t>* st);
+// two sums in one launch: terms [0, nL) and [nL, nL + nR) of canonical scalars (8 words each) over pts[ids[.]]
+int msm_run(Ctx* c, const uint32_t* sc, const uint32_t* ids, uint64_t nL, uint64_t nR, const G1Affine* pts,
+            const int32_t* kind, G1* part_dev, H1 sums[2]);
+bool pairing_check(const H1 sums[2], const G2Prepared& x_h, const G2Prepared& h);   // e(-sums[0], x_h) e(sums[1], h) == 1
+G1Aff64 xyzz_to_aff(const H1& p);
+// capi.hip: up to MSM_MAX_BATCH resident scalar sets over the commit key as ONE grouped launch, the bit sums copied back and
+// finished on the host (plonk_msm / plonk_msm_batch / the KZG opening calls): sums[k] = the commitment as an XYZZ point.
+// The caller has reserved the MSM scratch (msm_reserve) for the largest m; returns with the stream synchronised.
+int msm_group_sums(Ctx* c, const Fr* const* scalars_dev, const uint64_t* m, int cnt, G1* sums);
+void kzg_ws_release(Ctx* c);                          // kzg.hip: frees the opening workspace of the context
 int msm_sort_reserve_fixed(Ctx* c);
 
 }  // namespace plonk

@@ -1227,6 +1227,150 @@ int poly_ruffini(Ctx* c, const Fr* src, Fr* dst, uint64_t len, const Fr& z, cons
   return PLONK_OK;
 }
 
+// ---------------------------------------------------------------------------
+// KZG10 openings (kzg.hip): CommitKey::compute_aggregate_witness' sum and the evaluations of its polynomials in ONE
+// pass over the coefficients (reference key.rs:394-417 reads every polynomial twice: once to evaluate, once to fold).
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ void st_slot(void* base, uint64_t idx, const Fr29& v) {
+  uint32_t* w = reinterpret_cast<Fr29Slot*>(base)[idx].w;
+#pragma unroll
+  for (int i = 0; i < 9; ++i) w[i] = v.l[i];
+  w[9] = 0; w[10] = 0; w[11] = 0;
+}
+// tab[i] = x^i in twiddle form, one lane per power (square-and-multiply: 2 log2(i) products)
+__global__ void __launch_bounds__(256) kzg_powers_kernel(void* __restrict__ tab, uint32_t count, Tw xt, Tw one_t) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= count) return;
+  st_slot(tab, i, pow_tw(tw29(xt), i, tw29(one_t)));
+}
+// out[i] = x^i as data (R form): one (R form) times x^i (twiddle form)
+__global__ void __launch_bounds__(256) power_array_kernel(Fr* __restrict__ out, uint64_t n, Tw xt, Tw one_t) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  stf(out + i, Fr29::mul(Fr29::from_fr(Fr::one()), pow_tw(tw29(xt), i, tw29(one_t))).to_fr());
+}
+// one workgroup per polynomial: the length without its trailing zeros (Polynomial::from_coefficients_vec, the degree
+// CommitKey::commit checks).  Chunks of 256 from the top; a polynomial whose leading coefficient is set takes one step.
+__global__ void __launch_bounds__(256) kzg_trim_kernel(KzgDesc* __restrict__ desc) {
+  __shared__ unsigned long long best;
+  const Fr* p = desc[blockIdx.x].p;
+  uint64_t hi = desc[blockIdx.x].len;
+  while (hi) {
+    if (!threadIdx.x) best = 0;
+    __syncthreads();
+    const uint64_t lo = hi > 256 ? hi - 256 : 0, idx = lo + threadIdx.x;
+    if (idx < hi && !ldf(p + idx).is_zero()) atomicMax(&best, (unsigned long long)(idx + 1));
+    __syncthreads();
+    const uint64_t b = best;
+    __syncthreads();
+    if (b) { hi = b; break; }
+    hi = lo;
+  }
+  if (!threadIdx.x) desc[blockIdx.x].len = hi;
+}
+// A lane owns KZG_FOLD_E consecutive coefficient positions j.  Per polynomial i of the launch it loads its coefficients
+// ONCE and uses each twice: f[k] += v^i c (the fold) and the Horner step h = h z + c (the evaluation partial, scaled by
+// z^j0 afterwards).  The partials of a wave are summed by shuffles — no LDS, no barrier — and lane 0 writes one value per
+// (polynomial, wave); kzg_eval_final_kernel adds those.  Values stay in data form throughout: data x twiddle -> data.
+__global__ void __launch_bounds__(KZG_FOLD_T) kzg_fold_eval_kernel(KzgFoldArgs a, Tw zt_, Tw one_t, uint32_t nwaves) {
+  const uint64_t t = (uint64_t)blockIdx.x * KZG_FOLD_T + threadIdx.x;
+  const uint64_t j0 = t * KZG_FOLD_E;
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t wave = t >> 6, wave_j0 = (t - lane) * KZG_FOLD_E;
+  const Fr29 zt = tw29(zt_);
+  const Fr29 zb = pow_tw(zt, j0, tw29(one_t));   // z^j0
+  Fr29 f[KZG_FOLD_E] = {Fr29::zero(), Fr29::zero(), Fr29::zero(), Fr29::zero()};
+  for (uint32_t i = 0; i < a.count; ++i) {
+    const KzgDesc d = a.desc[a.first + i];
+    if (wave_j0 >= d.len) {   // wave-uniform: nothing of this polynomial here
+      if (!lane) stf(a.partial + (uint64_t)i * nwaves + wave, Fr::zero());
+      continue;
+    }
+    const Fr29 vt = ld_slot(a.vpow, a.first + i);
+    Fr29 h = Fr29::zero();
+    // Horner runs from the top coefficient down; written out so that f[] has constant indices and stays in registers
+#define KZG_STEP(k)                                                       \
+  {                                                                       \
+    const Fr29 cf = j0 + (k) < d.len ? ld29_(d.p + j0 + (k)) : Fr29::zero(); \
+    f[k] = Fr29::add_csub(f[k], Fr29::mul(cf, vt));                       \
+    h = Fr29::add_csub(Fr29::mul(h, zt), cf);                             \
+  }
+    static_assert(KZG_FOLD_E == 4, "KZG_STEP is written out for four coefficients per lane");
+    KZG_STEP(3) KZG_STEP(2) KZG_STEP(1) KZG_STEP(0)
+#undef KZG_STEP
+    h = Fr29::mul(h, zb);
+#pragma unroll
+    for (int off = 32; off; off >>= 1) {
+      Fr29 o;
+#pragma unroll
+      for (int w = 0; w < 9; ++w) o.l[w] = __shfl_down(h.l[w], off, 64);
+      h = Fr29::add_csub(h, o);
+    }
+    if (!lane) stf(a.partial + (uint64_t)i * nwaves + wave, h.to_fr());
+  }
+#define KZG_STORE(k)                                                      \
+  if (j0 + (k) < a.len) {                                                 \
+    Fr29 r = f[k];                                                        \
+    if (a.accumulate) r = Fr29::add_csub(r, ld29_(a.fold + j0 + (k)));    \
+    stf(a.fold + j0 + (k), r.to_fr());                                    \
+  }
+  KZG_STORE(0) KZG_STORE(1) KZG_STORE(2) KZG_STORE(3)
+#undef KZG_STORE
+}
+// one workgroup per polynomial of the launch: evals[i] = the sum of its nwaves partials
+__global__ void __launch_bounds__(256) kzg_eval_final_kernel(const Fr* __restrict__ partial, uint32_t nwaves, Fr* __restrict__ evals) {
+  __shared__ Fr sh[256];
+  const uint32_t t = threadIdx.x;
+  Fr acc = Fr::zero();
+  for (uint32_t w = t; w < nwaves; w += 256) acc = acc + ldf(partial + (uint64_t)blockIdx.x * nwaves + w);
+  sh[t] = acc;
+  __syncthreads();
+  for (uint32_t h = 128; h; h >>= 1) {
+    if (t < h) sh[t] = sh[t] + sh[t + h];
+    __syncthreads();
+  }
+  if (!t) stf(evals + blockIdx.x, sh[0]);
+}
+__global__ void __launch_bounds__(256) shift_down_kernel(const Fr* __restrict__ src, Fr* __restrict__ dst, uint64_t len) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= len) return;
+  stf(dst + i, i + 1 < len ? ldf(src + i + 1) : Fr::zero());
+}
+int poly_kzg_trim(Ctx* c, KzgDesc* desc_dev, uint32_t count) {
+  if (!count) return PLONK_OK;
+  hipLaunchKernelGGL(kzg_trim_kernel, dim3(count), dim3(256), 0, c->stream, desc_dev);
+  HIP_TRY(hipGetLastError());
+  return PLONK_OK;
+}
+int poly_kzg_powers(Ctx* c, void* vpow_dev, uint32_t count, const Fr& v) {
+  if (!count) return PLONK_OK;
+  hipLaunchKernelGGL(kzg_powers_kernel, grid1(count, 256), dim3(256), 0, c->stream, vpow_dev, count, tw_of(v), tw_of(Fr::one()));
+  HIP_TRY(hipGetLastError());
+  return PLONK_OK;
+}
+int poly_power_array(Ctx* c, Fr* out, uint64_t n, const Fr& x) {
+  if (!n) return PLONK_OK;
+  hipLaunchKernelGGL(power_array_kernel, grid1(n, 256), dim3(256), 0, c->stream, out, n, tw_of(x), tw_of(Fr::one()));
+  HIP_TRY(hipGetLastError());
+  return PLONK_OK;
+}
+int poly_kzg_fold_eval(Ctx* c, const KzgFoldArgs& a, Fr* evals_dev) {
+  if (!a.count || a.count > KZG_GROUP || !a.len) return (plonk::set_last_error("invalid argument", __func__, __FILE__, __LINE__), PLONK_ERR_ARG);
+  const uint32_t nwaves = kzg_fold_waves(a.len);
+  hipLaunchKernelGGL(kzg_fold_eval_kernel, dim3(nwaves / (KZG_FOLD_T / 64)), dim3(KZG_FOLD_T), 0, c->stream, a, tw_of(a.point),
+                     tw_of(Fr::one()), nwaves);
+  hipLaunchKernelGGL(kzg_eval_final_kernel, dim3(a.count), dim3(256), 0, c->stream, a.partial, nwaves, evals_dev);
+  HIP_TRY(hipGetLastError());
+  return PLONK_OK;
+}
+// the quotient by X - 0 is a shift: poly_ruffini's q_i = S_(i+1) z^-(i+1) has no meaning there
+int poly_shift_down(Ctx* c, const Fr* src, Fr* dst, uint64_t len) {
+  if (!len) return PLONK_OK;
+  hipLaunchKernelGGL(shift_down_kernel, grid1(len, 256), dim3(256), 0, c->stream, src, dst, len);
+  HIP_TRY(hipGetLastError());
+  return PLONK_OK;
+}
+
 int poly_fold(Ctx* c, const Fr* src, Fr* dst, uint64_t n, uint32_t extra, const Fr& cn) {
   hipLaunchKernelGGL(fold_kernel, grid1(n, 256), dim3(256), 0, c->stream, src, dst, n, extra, cn);
   HIP_TRY(hipGetLastError());

@@ -102,6 +102,33 @@ struct ShardSplitFix {
   uint64_t lo, hi, n;
   Fr b[3];
 };
+// ---- KZG10 openings (kzg.hip): fold and evaluate over a device table of polynomials --------------------------------
+struct KzgDesc {     // one polynomial in coefficient form
+  const Fr* p;
+  uint64_t len;
+};
+static constexpr uint32_t KZG_FOLD_T = 256, KZG_FOLD_E = 4;   // lanes per workgroup, consecutive coefficients per lane
+static constexpr uint32_t KZG_GROUP = 64;                    // polynomials per launch of the fold kernel
+inline uint32_t kzg_fold_waves(uint64_t len) {               // evaluation partials a launch over `len` coefficients writes per polynomial
+  const uint64_t per = (uint64_t)KZG_FOLD_T * KZG_FOLD_E;
+  return (uint32_t)((len + per - 1) / per) * (KZG_FOLD_T / 64);
+}
+struct KzgFoldArgs {
+  const KzgDesc* desc;     // device table; the launch covers desc[first, first + count), count <= KZG_GROUP
+  const void* vpow;        // v^i, i < (all polynomials of the call), twiddle form (Fr29Slot)
+  uint32_t first, count;
+  uint64_t len;            // coefficients the launch covers: >= every len of its polynomials
+  int accumulate;          // 0: fold[j] = sum; 1: fold[j] += sum
+  Fr* fold;                // len
+  Fr* partial;             // [count][kzg_fold_waves(len)] evaluation partials
+  Fr point;
+};
+int poly_kzg_trim(Ctx* c, KzgDesc* desc_dev, uint32_t count);                       // desc[i].len -> trimmed length
+int poly_kzg_powers(Ctx* c, void* vpow_dev, uint32_t count, const Fr& v);           // v^i in twiddle form
+int poly_power_array(Ctx* c, Fr* out, uint64_t n, const Fr& x);                     // out[i] = x^i (Montgomery)
+int poly_kzg_fold_eval(Ctx* c, const KzgFoldArgs& a, Fr* evals_dev);                // + evals_dev[i] = p_(first + i)(point), i < count
+int poly_shift_down(Ctx* c, const Fr* src, Fr* dst, uint64_t len);                  // ruffini at the point 0: dst[i] = src[i + 1], dst[len - 1] = 0
+
 int poly_fold(Ctx* c, const Fr* src, Fr* dst, uint64_t n, uint32_t extra, const Fr& cn);
 int poly_shard_pack(Ctx* c, const ShardPackArgs& a, uint32_t world);
 int poly_shard_combine(Ctx* c, const ShardCombineArgs& a);

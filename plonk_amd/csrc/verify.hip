@@ -57,8 +57,6 @@ namespace plonk {
 
 FinishPool* finish_pool_acquire(Ctx* c);   // prover.hip: the context's host helper threads (cfg.host_threads), or null
 
-enum : int { VDEC_OK = 0, VDEC_IDENTITY = 1, VDEC_BAD = 2 };
-
 __global__ void __launch_bounds__(64) verify_decode_kernel(const uint8_t* __restrict__ comp, uint32_t n, G1Affine* __restrict__ out,
                                      int32_t* __restrict__ status) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -81,7 +79,7 @@ __global__ void __launch_bounds__(64) verify_decode_kernel(const uint8_t* __rest
 }
 
 constexpr int VMSM_LANES = 64;   // one wave per block: the LDS tree needs no barrier beyond the wave's own
-constexpr uint32_t VMSM_MAX_BLOCKS = 512;
+constexpr uint32_t VMSM_MAX_BLOCKS = VERIFY_MSM_MAX_BLOCKS;
 
 // sum 0 (L) takes terms [0, n0), sum 1 (R) terms [n0, n0 + n1).  sc: canonical scalars (8 words each); id: point index
 // into pts / kind (VDEC_*).  part: [2][gridDim.x] partial sums (XYZZ, canonical Montgomery coordinates).
@@ -296,19 +294,23 @@ struct Verifier {
   }
 };
 
-static int decode_points(Verifier* v, const uint8_t* comp_host, uint32_t first, uint32_t n, std::vector<int32_t>* st) {
-  Ctx* c = v->c;
-  HIP_TRY(hipMemcpyAsync(v->comp + 48ull * first, comp_host, 48ull * n, hipMemcpyHostToDevice, c->stream));
-  hipLaunchKernelGGL(verify_decode_kernel, dim3((n + 63) / 64), dim3(64), 0, c->stream, v->comp + 48ull * first, n,
-                     v->pts + first, v->kind + first);
-  HIP_TRY(hipGetLastError());
+// n compressed commitments from the host -> comp_dev, decoded and subgroup-checked into pts_dev / kind_dev; st: the kinds
+int decode_points(Ctx* c, const uint8_t* comp_host, uint32_t n, uint8_t* comp_dev, G1Affine* pts_dev, int32_t* kind_dev,
+                  std::vector<int32_t>* st) {
   st->resize(n);
-  HIP_TRY(hipMemcpyAsync(st->data(), v->kind + first, 4ull * n, hipMemcpyDeviceToHost, c->stream));
+  if (!n) return PLONK_OK;
+  HIP_TRY(hipMemcpyAsync(comp_dev, comp_host, 48ull * n, hipMemcpyHostToDevice, c->stream));
+  hipLaunchKernelGGL(verify_decode_kernel, dim3((n + 63) / 64), dim3(64), 0, c->stream, comp_dev, n, pts_dev, kind_dev);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(st->data(), kind_dev, 4ull * n, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return PLONK_OK;
 }
+static int decode_points(Verifier* v, const uint8_t* comp_host, uint32_t first, uint32_t n, std::vector<int32_t>* st) {
+  return decode_points(v->c, comp_host, n, v->comp + 48ull * first, v->pts + first, v->kind + first, st);
+}
 
-static G1Aff64 xyzz_to_aff(const H1& p) {
+G1Aff64 xyzz_to_aff(const H1& p) {
   G1Aff64 a;
   memset(&a, 0, sizeof a);
   if (p.inf()) { a.inf = true; return a; }
@@ -337,7 +339,7 @@ struct BatchState {
 
 // the two sums of a check from term arrays on the device: terms [0, nL) (L) and [nL, nL + nR) (R) (canonical scalars, 8
 // words each; point ids into pts / kind); the host adds the per-block partial sums
-static int msm_run(Ctx* c, const uint32_t* sc, const uint32_t* ids, uint64_t nL, uint64_t nR, const G1Affine* pts,
+int msm_run(Ctx* c, const uint32_t* sc, const uint32_t* ids, uint64_t nL, uint64_t nR, const G1Affine* pts,
                    const int32_t* kind, G1* part_dev, H1 sums[2]) {
   const uint64_t nmax = nR > nL ? nR : nL;
   uint32_t blocks = (uint32_t)((nmax + 4 * VMSM_LANES - 1) / (4 * VMSM_LANES));   // ~4 terms per lane
@@ -354,9 +356,7 @@ static int msm_run(Ctx* c, const uint32_t* sc, const uint32_t* ids, uint64_t nL,
     for (uint32_t k = 0; k < blocks; ++k) {
       const G1& q = part[g * blocks + k];
       if (q.is_identity()) continue;
-      H1 h;
-      memcpy(h.X.l, q.X.l, 48); memcpy(h.Y.l, q.Y.l, 48); memcpy(h.ZZ.l, q.ZZ.l, 48); memcpy(h.ZZZ.l, q.ZZZ.l, 48);
-      sums[g] = h1_add(sums[g], h);
+      sums[g] = h1_add(sums[g], h1_of_g1(q));
     }
   }
   return PLONK_OK;
@@ -371,7 +371,7 @@ static int msm_device(Verifier* v, const uint32_t* sc_host, const uint32_t* id_h
 }
 
 // e(-L, x_h) e(R, h) == 1 for the two sums of a check
-static bool pairing_check(const H1 sums[2], const G2Prepared& x_h, const G2Prepared& h) {
+bool pairing_check(const H1 sums[2], const G2Prepared& x_h, const G2Prepared& h) {
   G1Aff64 pairs[2] = {xyzz_to_aff(sums[0]), xyzz_to_aff(sums[1])};
   if (!pairs[0].inf) {   // -L
     Fp64 z;

@@ -286,6 +286,16 @@ static uint64_t le64_at(const uint8_t* p) {
 static constexpr uint64_t VK_BLOB_BYTES = 20 * 48 + 8, OPENING_KEY_LEN = 48 + 96 + 96;
 #define VFAIL(code, msg) return (set_last_error("plonk_verifier_from_bytes", msg, __FILE__, __LINE__), code)
 
+// OpeningKey::from_bytes + try_new (key.rs:609-648) on the 240 bytes g || h || x_h: nullptr when valid, else what is wrong
+// (shared by plonk_verifier_from_bytes and plonk_kzg_key_create)
+static const char* opening_key_invalid(const uint8_t* p) {
+  if ((p[0] & 0x40) || (p[48] & 0x40) || (p[144] & 0x40)) return "opening key: g, h and x_h must not be the identity";
+  if (!g1_compressed_valid(p)) return "opening key: g is not a valid compressed G1 point";
+  if (!g2_compressed_valid(p + 48)) return "opening key: h is not a valid compressed G2 point";
+  if (!g2_compressed_valid(p + 144)) return "opening key: x_h is not a valid compressed G2 point";
+  return nullptr;
+}
+
 // Verifier::try_from_bytes (verifier.rs:121-200) -> VerifierKey::from_slice (widget.rs:113-134), OpeningKey::from_slice
 // (key.rs:596-648), Verifier::new
 static int parse_verifier_blob(const uint8_t* blob, uint64_t len, VerifierCore* core, uint8_t g48[48], uint8_t h96[96],
@@ -309,10 +319,7 @@ static int parse_verifier_blob(const uint8_t* blob, uint64_t len, VerifierCore* 
   }
   p += vk_len;
   if (ok_len < OPENING_KEY_LEN) VFAIL(PLONK_ERR_BYTES, "opening key length");
-  if ((p[0] & 0x40) || (p[48] & 0x40) || (p[144] & 0x40)) VFAIL(PLONK_ERR_DATA, "opening key: g, h and x_h must not be the identity");
-  if (!g1_compressed_valid(p)) VFAIL(PLONK_ERR_DATA, "opening key: g is not a valid compressed G1 point");
-  if (!g2_compressed_valid(p + 48)) VFAIL(PLONK_ERR_DATA, "opening key: h is not a valid compressed G2 point");
-  if (!g2_compressed_valid(p + 144)) VFAIL(PLONK_ERR_DATA, "opening key: x_h is not a valid compressed G2 point");
+  if (const char* why = opening_key_invalid(p)) VFAIL(PLONK_ERR_DATA, why);
   memcpy(g48, p, 48);
   memcpy(h96, p + 48, 96);
   memcpy(xh96, p + 144, 96);
