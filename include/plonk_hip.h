@@ -676,6 +676,91 @@ int plonk_kzg_batch_check(plonk_kzg_key* key, const uint64_t* points /* count x 
                           plonk_verify_info* info);
 int plonk_srs_check(plonk_kzg_key* key, const uint8_t seed32[32]);
 
+/* ---- gadget composer: circuits from gadgets, witness generation on the device -------------------
+ * What the reference's Composer does for a Circuit (src/composer.rs and src/composer/{bits,range,logic,select,truncate,
+ * point,fixed_base}.rs): a plonk_composer RECORDS gadget calls and yields (a) the gate layout plonk_compile takes and
+ * (b) a witness program that computes every witness of one proof from the circuit's INPUT values — on the device, into the
+ * prover's resident witness table, where the reference re-runs the circuit on one host thread (Composer::prove,
+ * composer.rs:442).  A composer starts as Composer::initialized: witnesses 0 and 1 are the constants zero and one, four
+ * gates are there.  Witness indices are Witness::index; a point is a pair (x, y) of indices.
+ *
+ * plonk_composer_witness: append_witness — allocates an INPUT and returns its index; the inputs of a proof are given in
+ *   allocation order (PLONK_G_PUBLIC, _POINT and _PUBLIC_POINT allocate inputs too: one, two, two).
+ * plonk_composer_gate: one arithmetic gate.  selectors: q_m q_l q_r q_o q_f q_c (6 x 4 Montgomery limbs), wires a b c d.
+ *   flags bit 0: the row is a public-input row.  flags bit 1: append_evaluated_output (composer.rs:307-359) — solve the row
+ *   for c, allocate it, wire it (wires[2] is ignored) and return its index in *out; gate_add / gate_mul are this with
+ *   q_o = -1.  With q_o = 0 nothing is allocated, *out = 0xFFFFFFFF and the gate is appended with wires[2] as given (the
+ *   reference's None, composer.rs:352-356).
+ *   DEVIATION from the reference: its evaluated c includes the row's PI term (composer.rs:326), because its public value
+ *   is known while the circuit runs.  Here a public value is never given when recording, so with BOTH flags set c is
+ *   solved with PI = 0 and the fill then reports PI = 0 for the row.  A caller that needs a non-zero public term on an
+ *   evaluated row feeds it through a PLONK_G_PUBLIC witness on wire d instead.
+ * plonk_composer_gadget: one gadget call.  in: its input witnesses; width: its const parameter; consts: Montgomery limbs of a
+ *   constant, or x || y of a constant point / generator; out: the witnesses it returns (*nout of them; PLONK_ERR_ARG when
+ *   out_cap is smaller).  Per kind (inputs; constants; outputs):
+ *     PLONK_G_CONSTANT (-; value; w)        PLONK_G_PUBLIC (-; -; w)            PLONK_G_ASSERT_EQUAL (a b; -; -)
+ *     PLONK_G_ASSERT_EQUAL_CONSTANT (a; value; -), width bit 0 makes the row public as well
+ *     PLONK_G_BOOLEAN (a; -; -)             PLONK_G_SELECT (bit a b; -; w)      PLONK_G_SELECT_ONE / _ZERO (bit value; -; w)
+ *     PLONK_G_DECOMPOSITION<width 1..256> (a; -; width bits, little-endian)
+ *     PLONK_G_RANGE_BITS<width 0..256> (a; -; -), odd widths included     PLONK_G_RANGE<width = bit pairs> (a; -; -)
+ *     PLONK_G_TRUNCATE<width 0..254> (a; -; low)
+ *     PLONK_G_BIND_TRUNCATION_SPLIT<width> (input low; -; -)      PLONK_G_CANONICAL_TRUNCATION<width> (high low; -; -)
+ *     PLONK_G_LOGIC_AND / _XOR<width = bit pairs 0..127> (a b; -; w), the inputs bound as logic.rs:181-212 binds them
+ *     PLONK_G_POINT (-; -; x y)             PLONK_G_CONSTANT_POINT (-; x y; x y)      PLONK_G_PUBLIC_POINT (-; -; x y)
+ *     PLONK_G_ASSERT_EQUAL_POINT (ax ay bx by; -; -)              PLONK_G_ASSERT_EQUAL_PUBLIC_POINT (x y; -; -)
+ *     PLONK_G_NEG_POINT (x y; -; x y)       PLONK_G_SUB_POINT / _ADD_POINT (ax ay bx by; -; x y)
+ *     PLONK_G_SELECT_IDENTITY (bit x y; -; x y)                   PLONK_G_SELECT_POINT (bit ax ay bx by; -; x y)
+ *     PLONK_G_TORSION_FREE (x y; -; -)      PLONK_G_CANONICAL_JUBJUB_SCALAR (s; -; -)
+ *     PLONK_G_MUL_GENERATOR (s; generator x y; x y)               PLONK_G_MUL_POINT (s x y; -; x y)
+ *   A constant point is validated on the host as the reference validates it — on the curve and torsion-free, of exact prime
+ *   order for a generator: PLONK_ERR_POINT otherwise.  DEVIATION in form, not in result: a public row's value is not given
+ *   when recording; a fill computes it as whatever satisfies the row under the filled witnesses, which is the value the
+ *   honest reference passes, since its PI and its witness come from the same circuit field.
+ * plonk_composer_info / _layout: the counts, and what plonk_compile would be given (selectors[k] / wires[w]: `constraints`
+ *   entries each, any pointer may be NULL) plus the witness slot of every input and the rows of the public inputs,
+ *   ascending — for tests, and for callers who want plonk_compile with sharding.
+ * plonk_compile_composer: single GPU; the same prover plonk_compile builds from the exported layout, with the witness
+ *   program uploaded and attached.  The composer may be destroyed afterwards.
+ *
+ * Per proof, on a prover from plonk_compile_composer (PLONK_ERR_STATE on any other; PLONK_ERR_ARG when count differs from the
+ * circuit's inputs): inputs = count x 4 Montgomery limbs.
+ *   plonk_prover_fill_inputs: runs the witness program; witnesses_out (witnesses x 4 limbs) and pi_out (public_rows x 4
+ *     limbs) may be NULL.
+ *   plonk_prover_prove_inputs: fill, then the proof of plonk_prover_prove_witnesses over the filled table with the computed
+ *     public inputs (returned in pi_out, nullable).
+ *   plonk_prover_diagnose_inputs: fill, then the report of plonk_prover_diagnose_witnesses.
+ * A scalar that is not below the order of the JubJub subgroup handed to PLONK_G_MUL_GENERATOR is the reference's
+ * Error::JubJubScalarMalformed: PLONK_ERR_DATA with a text naming the gadget and the record, and no proof.  Everything else
+ * is total: an off-curve point falls back to the identity as point.rs:379-383 does, and the gates reject. */
+typedef enum plonk_gadget {
+  PLONK_G_CONSTANT = 0, PLONK_G_PUBLIC, PLONK_G_ASSERT_EQUAL, PLONK_G_ASSERT_EQUAL_CONSTANT, PLONK_G_BOOLEAN,
+  PLONK_G_SELECT, PLONK_G_SELECT_ONE, PLONK_G_SELECT_ZERO, PLONK_G_DECOMPOSITION, PLONK_G_RANGE_BITS, PLONK_G_RANGE,
+  PLONK_G_TRUNCATE, PLONK_G_BIND_TRUNCATION_SPLIT, PLONK_G_CANONICAL_TRUNCATION, PLONK_G_LOGIC_AND, PLONK_G_LOGIC_XOR,
+  PLONK_G_POINT, PLONK_G_CONSTANT_POINT, PLONK_G_PUBLIC_POINT, PLONK_G_ASSERT_EQUAL_POINT, PLONK_G_ASSERT_EQUAL_PUBLIC_POINT,
+  PLONK_G_NEG_POINT, PLONK_G_SUB_POINT, PLONK_G_ADD_POINT, PLONK_G_SELECT_IDENTITY, PLONK_G_SELECT_POINT,
+  PLONK_G_TORSION_FREE, PLONK_G_CANONICAL_JUBJUB_SCALAR, PLONK_G_MUL_GENERATOR, PLONK_G_MUL_POINT
+} plonk_gadget;
+typedef struct plonk_composer_summary {
+  uint64_t constraints, witnesses, inputs, public_rows;
+  uint64_t records, levels, widest_level;   /* of the witness program: records, dependency levels, records of the widest level */
+} plonk_composer_summary;
+typedef struct plonk_composer plonk_composer;
+int plonk_composer_create(plonk_composer** out);
+void plonk_composer_destroy(plonk_composer* c);
+int plonk_composer_witness(plonk_composer* c, uint32_t* out);
+int plonk_composer_gate(plonk_composer* c, const uint64_t* selectors /* 6 x 4 */, const uint32_t wires[4], uint32_t flags, uint32_t* out);
+int plonk_composer_gadget(plonk_composer* c, int kind, uint32_t width, const uint32_t* in, uint32_t nin, const uint64_t* consts,
+                          uint32_t nconsts, uint32_t* out, uint32_t out_cap, uint32_t* nout);
+int plonk_composer_info(plonk_composer* c, plonk_composer_summary* out);
+int plonk_composer_layout(plonk_composer* c, uint64_t* const selectors[11], uint32_t* const wires[4], uint32_t* input_slots,
+                          uint64_t* pi_rows);
+int plonk_compile_composer(plonk_ctx* ctx, plonk_composer* c, const uint8_t* label, uint64_t label_len, plonk_prover** out);
+int plonk_prover_fill_inputs(plonk_prover* p, const uint64_t* inputs, uint64_t count, uint64_t* witnesses_out, uint64_t* pi_out);
+int plonk_prover_prove_inputs(plonk_prover* p, const uint64_t* inputs, uint64_t count, const uint64_t* blinders, uint8_t proof[1008],
+                              uint64_t* pi_out);
+int plonk_prover_diagnose_inputs(plonk_prover* p, const uint64_t* inputs, uint64_t count, plonk_unsat_row* out, uint64_t cap,
+                                 plonk_unsat_info* info);
+
 /* ---- measurement --------------------------------------------------------------
  * When enabled, every launch of the dominant kernels is bracketed by a hipEvent
  * pair ON THE LIBRARY'S STREAM and accumulated per slot.  Slots:

@@ -66,6 +66,9 @@ EXPORTS = [
     "plonk_prover_diagnose", "plonk_prover_diagnose_dev", "plonk_prover_diagnose_witnesses",
     "plonk_kzg_open", "plonk_kzg_open_dev", "plonk_kzg_flatten", "plonk_kzg_key_create", "plonk_kzg_key_destroy",
     "plonk_kzg_batch_check", "plonk_srs_check",
+    "plonk_composer_create", "plonk_composer_destroy", "plonk_composer_witness", "plonk_composer_gate", "plonk_composer_gadget",
+    "plonk_composer_info", "plonk_composer_layout", "plonk_compile_composer",
+    "plonk_prover_fill_inputs", "plonk_prover_prove_inputs", "plonk_prover_diagnose_inputs",
 ]
 
 # what bit f of plonk_unsat_row.families / slot f of plonk_unsat_info.family_rows stands for (include/plonk_hip.h); the
@@ -169,6 +172,12 @@ class Diagnosis:
             return f"Diagnosis(ok, {self.rows_checked} rows)"
         return (f"Diagnosis({self.rows_failing} of {self.rows_checked} rows fail; first: row {self.first_row}, "
                 f"{IDENTITY_FAMILIES[self.first_family]})")
+
+
+class _ComposerSummary(ctypes.Structure):
+    _fields_ = [("constraints", ctypes.c_uint64), ("witnesses", ctypes.c_uint64), ("inputs", ctypes.c_uint64),
+                ("public_rows", ctypes.c_uint64), ("records", ctypes.c_uint64), ("levels", ctypes.c_uint64),
+                ("widest_level", ctypes.c_uint64)]
 
 
 class _BlobInfo(ctypes.Structure):
@@ -349,6 +358,18 @@ def load_library() -> ctypes.CDLL:
     lib.plonk_kzg_batch_check.argtypes = [vp, vp, vp, u64, vp, u64, vp, vp]
     lib.plonk_srs_check.argtypes = [vp, vp]
     lib.plonk_test_kzg_last.argtypes = [vp, vp, vp]   # test hook of kzg.hip, not in the header
+    lib.plonk_composer_create.argtypes = [ctypes.POINTER(vp)]
+    lib.plonk_composer_destroy.argtypes = [vp]
+    lib.plonk_composer_destroy.restype = None
+    lib.plonk_composer_witness.argtypes = [vp, ctypes.POINTER(u32)]
+    lib.plonk_composer_gate.argtypes = [vp, vp, vp, u32, ctypes.POINTER(u32)]
+    lib.plonk_composer_gadget.argtypes = [vp, ci, u32, vp, u32, vp, u32, vp, u32, ctypes.POINTER(u32)]
+    lib.plonk_composer_info.argtypes = [vp, ctypes.POINTER(_ComposerSummary)]
+    lib.plonk_composer_layout.argtypes = [vp, vp, vp, vp, vp]
+    lib.plonk_compile_composer.argtypes = [vp, vp, vp, u64, ctypes.POINTER(vp)]
+    lib.plonk_prover_fill_inputs.argtypes = [vp, vp, u64, vp, vp]
+    lib.plonk_prover_prove_inputs.argtypes = [vp, vp, u64, vp, vp, vp]
+    lib.plonk_prover_diagnose_inputs.argtypes = [vp, vp, u64, vp, u64, vp]
     _lib = lib
     return lib
 
@@ -783,6 +804,198 @@ class Context:
         return ms.value, n.value
 
 
+# kinds of plonk_composer_gadget (enum plonk_gadget of include/plonk_hip.h, in its order)
+GADGETS = ["CONSTANT", "PUBLIC", "ASSERT_EQUAL", "ASSERT_EQUAL_CONSTANT", "BOOLEAN", "SELECT", "SELECT_ONE", "SELECT_ZERO",
+           "DECOMPOSITION", "RANGE_BITS", "RANGE", "TRUNCATE", "BIND_TRUNCATION_SPLIT", "CANONICAL_TRUNCATION", "LOGIC_AND",
+           "LOGIC_XOR", "POINT", "CONSTANT_POINT", "PUBLIC_POINT", "ASSERT_EQUAL_POINT", "ASSERT_EQUAL_PUBLIC_POINT", "NEG_POINT",
+           "SUB_POINT", "ADD_POINT", "SELECT_IDENTITY", "SELECT_POINT", "TORSION_FREE", "CANONICAL_JUBJUB_SCALAR", "MUL_GENERATOR",
+           "MUL_POINT"]
+G = {name: k for k, name in enumerate(GADGETS)}
+
+
+class Composer:
+    """Records a circuit from gadgets (plonk_composer_*): one method per gadget of the reference's Composer, returning
+    witness indices — pairs (x, y) for points.  ZERO / ONE / IDENTITY are the constants of Composer::initialized.
+    Values are not given here: append_witness allocates an INPUT, and Prover.fill_inputs / prove_inputs take the input
+    values of one proof in allocation order."""
+    ZERO, ONE = 0, 1
+    IDENTITY = (0, 1)
+
+    def __init__(self):
+        self.lib = load_library()
+        h = ctypes.c_void_p()
+        self._check(self.lib.plonk_composer_create(ctypes.byref(h)))
+        self.handle = h
+
+    def _check(self, rc):
+        if rc == -10:
+            raise PointMalformed(rc, (self.lib.plonk_last_error() or b"").decode())
+        if rc != PLONK_OK:
+            raise PlonkError(rc, (self.lib.plonk_last_error() or b"").decode())
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.lib.plonk_composer_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # ---- the three recording calls
+    def append_witness(self) -> int:
+        out = ctypes.c_uint32()
+        self._check(self.lib.plonk_composer_witness(self.handle, ctypes.byref(out)))
+        return out.value
+
+    def append_gate(self, a=0, b=0, c=0, d=0, q_m=0, q_l=0, q_r=0, q_o=0, q_f=0, q_c=0, public=False, evaluate=False):
+        """one arithmetic gate; evaluate: solve it for c, allocate c and return its index (append_evaluated_output)"""
+        sel = fr_to_bytes_mont([q_m, q_l, q_r, q_o, q_f, q_c])
+        wires = (ctypes.c_uint32 * 4)(a, b, c, d)
+        out = ctypes.c_uint32()
+        self._check(self.lib.plonk_composer_gate(self.handle, sel, wires, (1 if public else 0) | (2 if evaluate else 0), ctypes.byref(out)))
+        return out.value if evaluate and out.value != 0xFFFFFFFF else None
+
+    def gadget(self, kind: str, ins=(), width: int = 0, consts=(), nout: int = 0):
+        arr = (ctypes.c_uint32 * max(len(ins), 1))(*ins)
+        cst = fr_to_bytes_mont(consts)
+        out = (ctypes.c_uint32 * max(nout, 1))()
+        got = ctypes.c_uint32()
+        self._check(self.lib.plonk_composer_gadget(self.handle, G[kind], width, arr, len(ins), cst, len(consts), out, nout, ctypes.byref(got)))
+        assert got.value == nout, (kind, got.value, nout)
+        return list(out[:nout])
+
+    # ---- composer basics
+    def append_evaluated_output(self, **kw):
+        return self.append_gate(evaluate=True, **kw)
+
+    def gate_add(self, a, b, d=0, q_l=1, q_r=1, q_f=0, q_c=0):
+        return self.append_gate(a=a, b=b, d=d, q_l=q_l, q_r=q_r, q_f=q_f, q_c=q_c, q_o=Q - 1, evaluate=True)
+
+    def gate_mul(self, a, b, d=0, q_m=1, q_f=0, q_c=0):
+        return self.append_gate(a=a, b=b, d=d, q_m=q_m, q_f=q_f, q_c=q_c, q_o=Q - 1, evaluate=True)
+
+    def append_constant(self, value: int) -> int:
+        return self.gadget("CONSTANT", consts=[value], nout=1)[0]
+
+    def append_public(self) -> int:
+        return self.gadget("PUBLIC", nout=1)[0]
+
+    def assert_equal(self, a, b):
+        self.gadget("ASSERT_EQUAL", [a, b])
+
+    def assert_equal_constant(self, a, constant: int, public: bool = False):
+        self.gadget("ASSERT_EQUAL_CONSTANT", [a], width=1 if public else 0, consts=[constant])
+
+    # ---- bits and selection
+    def component_boolean(self, a):
+        self.gadget("BOOLEAN", [a])
+
+    def component_select(self, bit, a, b) -> int:
+        return self.gadget("SELECT", [bit, a, b], nout=1)[0]
+
+    def component_select_one(self, bit, value) -> int:
+        return self.gadget("SELECT_ONE", [bit, value], nout=1)[0]
+
+    def component_select_zero(self, bit, value) -> int:
+        return self.gadget("SELECT_ZERO", [bit, value], nout=1)[0]
+
+    def component_decomposition(self, scalar, n: int) -> list:
+        return self.gadget("DECOMPOSITION", [scalar], width=n, nout=n)
+
+    # ---- range and truncation
+    def component_range_bits(self, w, bits: int):
+        self.gadget("RANGE_BITS", [w], width=bits)
+
+    def component_range(self, w, bit_pairs: int):
+        self.gadget("RANGE", [w], width=bit_pairs)
+
+    def component_truncate(self, w, n: int) -> int:
+        return self.gadget("TRUNCATE", [w], width=n, nout=1)[0]
+
+    def bind_truncation_split(self, input_w, low, num_bits: int):
+        self.gadget("BIND_TRUNCATION_SPLIT", [input_w, low], width=num_bits)
+
+    def assert_canonical_truncation(self, high, low, num_bits: int):
+        self.gadget("CANONICAL_TRUNCATION", [high, low], width=num_bits)
+
+    # ---- logic
+    def append_logic_and(self, a, b, bit_pairs: int) -> int:
+        return self.gadget("LOGIC_AND", [a, b], width=bit_pairs, nout=1)[0]
+
+    def append_logic_xor(self, a, b, bit_pairs: int) -> int:
+        return self.gadget("LOGIC_XOR", [a, b], width=bit_pairs, nout=1)[0]
+
+    # ---- points
+    def append_point(self):
+        return tuple(self.gadget("POINT", nout=2))
+
+    def append_constant_point(self, point):
+        return tuple(self.gadget("CONSTANT_POINT", consts=list(point), nout=2))
+
+    def append_public_point(self):
+        return tuple(self.gadget("PUBLIC_POINT", nout=2))
+
+    def assert_equal_point(self, a, b):
+        self.gadget("ASSERT_EQUAL_POINT", [*a, *b])
+
+    def assert_equal_public_point(self, point):
+        self.gadget("ASSERT_EQUAL_PUBLIC_POINT", list(point))
+
+    def component_neg_point(self, p):
+        return tuple(self.gadget("NEG_POINT", list(p), nout=2))
+
+    def component_sub_point(self, a, b):
+        return tuple(self.gadget("SUB_POINT", [*a, *b], nout=2))
+
+    def component_add_point(self, a, b):
+        return tuple(self.gadget("ADD_POINT", [*a, *b], nout=2))
+
+    def component_select_identity(self, bit, a):
+        return tuple(self.gadget("SELECT_IDENTITY", [bit, *a], nout=2))
+
+    def component_select_point(self, bit, a, b):
+        return tuple(self.gadget("SELECT_POINT", [bit, *a, *b], nout=2))
+
+    def assert_torsion_free_point(self, p):
+        self.gadget("TORSION_FREE", list(p))
+        return tuple(p)
+
+    # ---- scalar multiplication
+    def assert_canonical_jubjub_scalar(self, s):
+        self.gadget("CANONICAL_JUBJUB_SCALAR", [s])
+
+    def component_mul_generator(self, s, generator):
+        return tuple(self.gadget("MUL_GENERATOR", [s], consts=list(generator), nout=2))
+
+    def component_mul_point(self, s, p):
+        return tuple(self.gadget("MUL_POINT", [s, *p], nout=2))
+
+    # ---- inspection
+    def info(self) -> dict:
+        out = _ComposerSummary()
+        self._check(self.lib.plonk_composer_info(self.handle, ctypes.byref(out)))
+        return {k: getattr(out, k) for k, _ in out._fields_}
+
+    def layout(self) -> dict:
+        """what plonk_compile would be given: selectors {name: Montgomery bytes}, wires (4 lists), witnesses, plus the witness
+        slot of every input and the public-input rows"""
+        info = self.info()
+        n = info["constraints"]
+        sels = [ctypes.create_string_buffer(max(32 * n, 1)) for _ in range(11)]
+        wires = [(ctypes.c_uint32 * max(n, 1))() for _ in range(4)]
+        sp = (ctypes.c_void_p * 11)(*[ctypes.cast(b, ctypes.c_void_p) for b in sels])
+        wp = (ctypes.c_void_p * 4)(*[ctypes.cast(b, ctypes.c_void_p) for b in wires])
+        slots = (ctypes.c_uint32 * max(info["inputs"], 1))()
+        rows = (ctypes.c_uint64 * max(info["public_rows"], 1))()
+        self._check(self.lib.plonk_composer_layout(self.handle, sp, wp, slots, rows))
+        return {"selectors": {name: sels[k].raw[:32 * n] for k, name in enumerate(POLY_ORDER[:11])},
+                "wires": [list(w[:n]) for w in wires], "witnesses": info["witnesses"],
+                "input_slots": list(slots[:info["inputs"]]), "pi_rows": list(rows[:info["public_rows"]])}
+
+
 class Prover:
     """Device-resident mirror of the reference `Prover` (src/compiler/prover.rs:27-42):
     built from the 15 ProverKey polynomials + label + constraint count; `prove` takes the
@@ -1017,6 +1230,45 @@ class Prover:
         raw = bytes(values) if isinstance(values, (bytes, bytearray)) else fr_to_bytes_mont(values)
         idx, val, cnt = self._pi(public_inputs)
         return self._diagnose(lambda out, c, info: self.ctx.lib.plonk_prover_diagnose_witnesses(self.handle, raw, len(raw) // 32, idx, val, cnt, out, c, info), cap)
+
+    # ---- circuits from gadgets (plonk_compile_composer, plonk_prover_*_inputs): the witness table is filled on the device
+    @classmethod
+    def compile_composer(cls, ctx: Context, label: bytes, composer: "Composer") -> "Prover":
+        """plonk_compile on the composer's layout with its witness program attached; the composer may be closed afterwards"""
+        self = cls.__new__(cls)
+        self.ctx, self._keep, self._cb = ctx, None, None
+        h = ctypes.c_void_p()
+        ctx._check(ctx.lib.plonk_compile_composer(ctx.handle, composer.handle, label, len(label), ctypes.byref(h)))
+        self.handle = h
+        ctx._provers.add(self)
+        self.size = ctx.lib.plonk_prover_size(h)
+        info = composer.info()
+        self.composer_counts = (info["witnesses"], info["public_rows"])
+        return self
+
+    def fill_inputs(self, inputs, want_witnesses: bool = True):
+        """runs the witness program: (witness table as Montgomery bytes or None, public-input values as ints)"""
+        raw = bytes(inputs) if isinstance(inputs, (bytes, bytearray)) else fr_to_bytes_mont(inputs)
+        nw, npi = self.composer_counts
+        wit = ctypes.create_string_buffer(max(32 * nw, 1)) if want_witnesses else None
+        pi = ctypes.create_string_buffer(max(32 * npi, 1))
+        self.ctx._check(self.ctx.lib.plonk_prover_fill_inputs(self.handle, raw, len(raw) // 32, wit, pi))
+        return (wit.raw[:32 * nw] if want_witnesses else None), fr_from_bytes_mont(pi.raw[:32 * npi])
+
+    def prove_inputs(self, inputs, blinders):
+        """(proof bytes, public-input values) from the circuit's input values"""
+        raw = bytes(inputs) if isinstance(inputs, (bytes, bytearray)) else fr_to_bytes_mont(inputs)
+        bl = bytes(blinders) if isinstance(blinders, (bytes, bytearray)) else fr_to_bytes_mont(blinders)
+        assert len(bl) == 14 * 32
+        npi = self.composer_counts[1]
+        pi = ctypes.create_string_buffer(max(32 * npi, 1))
+        proof = ctypes.create_string_buffer(1008)
+        self.ctx._check(self.ctx.lib.plonk_prover_prove_inputs(self.handle, raw, len(raw) // 32, bl, proof, pi))
+        return proof.raw, fr_from_bytes_mont(pi.raw[:32 * npi])
+
+    def diagnose_inputs(self, inputs, cap: int = 64) -> Diagnosis:
+        raw = bytes(inputs) if isinstance(inputs, (bytes, bytearray)) else fr_to_bytes_mont(inputs)
+        return self._diagnose(lambda out, c, info: self.ctx.lib.plonk_prover_diagnose_inputs(self.handle, raw, len(raw) // 32, out, c, info), cap)
 
     def peek(self, which: int, offset: int, count: int) -> list[int]:
         out = ctypes.create_string_buffer(32 * count)

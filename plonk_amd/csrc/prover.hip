@@ -22,6 +22,7 @@
 #include "widgets.hpp"
 #include "permutation.hpp"
 #include "diagnose.hpp"
+#include "composer.hpp"
 
 static_assert(plonk::DQ_M == plonk::QS_M && plonk::DQ_ARITH == plonk::QS_ARITH && plonk::DQ_VAR == plonk::QS_VAR &&
               plonk::DQ_COUNT == plonk::QS_COUNT, "diagnose_core.hpp selector ids");
@@ -130,6 +131,8 @@ struct Prover {
   Fr* diag_sel = nullptr;          // [non-zero selectors][n] selector values over the proving domain
   const Fr* diag_sel_ptr[QS_COUNT] = {};   // selector id -> its slice of diag_sel (nullptr: identically zero)
   uint32_t* diag_pos = nullptr;    // [4][n] sigma_n decoded into packed wire positions (permutation.hpp)
+  // built by plonk_compile_composer: the witness program that fills wit_vals from a proof's inputs (composer.hip)
+  ComposerProgram* program = nullptr;
 };
 
 // ---- host helpers -------------------------------------------------------------------
@@ -389,6 +392,7 @@ static void prover_free(Prover* p) {
   for (void* b : {(void*)p->fold, (void*)p->Fbuf, (void*)p->send, (void*)p->recv, (void*)p->agg2, (void*)p->scratch2, (void*)p->wscal}) if (b) (void)hipFree(b);
   srs_table_release(p->c, p->lag_table, p->lag_rows, p->lag_n);   // gives the bytes back to the context's table budget
   for (void* b : {(void*)p->wire_idx, (void*)p->wit_vals, (void*)p->diag_sel, (void*)p->diag_pos}) if (b) (void)hipFree(b);
+  composer_program_free(p->program);
   for (int k = 0; k < 8; ++k) { ntt_coset_free(&p->cs_fwd[k]); ntt_coset_free(&p->cs_inv[k]); }
   if (p->ev_ready) (void)hipEventDestroy(p->ev_ready);
   if (p->ev_side) (void)hipEventDestroy(p->ev_side);
@@ -1886,6 +1890,7 @@ void plonk_prover_destroy(plonk_prover* pr) {
     std::lock_guard<std::mutex> lk(pr->ctx->c.mu);
     (void)hipSetDevice(pr->ctx->c.device);
     if (ctx_abandon(&pr->ctx->c)) {   // poisoned context, streams still busy: hipFree / hipStreamSynchronize would hang — leak the device buffers
+      composer_program_abandon(pr->p->program);
       delete pr->p;
     } else {
       (void)hipStreamSynchronize(pr->ctx->c.stream);
@@ -2317,6 +2322,121 @@ int plonk_prover_diagnose(plonk_prover* pr, const uint64_t* const wires[4], cons
   for (int k = 0; k < 4; ++k)
     HIP_TRY(hipMemcpyAsync(p->wires + k * p->n, wires[k], sizeof(Fr) * p->n, hipMemcpyHostToDevice, c->stream));
   return prover_diagnose(p, p->wires, pi_idx, (const Fr*)pi_val, pi_count, out, cap, info, t0);
+  });
+}
+
+}  // extern "C"
+
+// ---- circuits from gadgets (plonk_compile_composer, plonk_prover_*_inputs) ----------------------------------------------
+// plonk_compile on the composer's layout, with its witness program uploaded and attached; per proof the program fills the
+// prover's resident witness table (wit_vals) on the device (composer.hip) and the existing gather / prove / diagnose paths
+// run on it unchanged.  One synchronisation per fill: the error word and the public-input values come back with it.
+namespace plonk {
+static int inputs_guard(const Prover* p, const uint64_t* inputs, uint64_t count, const char* api_fn) {
+  if (!p->program) return (set_last_error("prover was not built by plonk_compile_composer: it has no witness program", api_fn, __FILE__, __LINE__), PLONK_ERR_STATE);
+  if (count != p->program->ninputs || (count && !inputs)) return (set_last_error("invalid argument", "input count differs from the composer's", __FILE__, __LINE__), PLONK_ERR_ARG);
+  return PLONK_OK;
+}
+static int inputs_fill(Prover* p, const uint64_t* inputs, const Fr** pi_vals) {
+  Ctx* c = p->c;
+  PTRY(composer_fill_queue(c, p->program, (const Fr*)inputs, p->wit_vals));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return composer_fill_result(p->program, pi_vals);
+}
+}  // namespace plonk
+
+extern "C" {
+
+int plonk_compile_composer(plonk_ctx* ctx, plonk_composer* comp, const uint8_t* label, uint64_t label_len, plonk_prover** out) {
+  const char* const api_fn = __func__;
+  return plonk::api_guard(api_fn, [&]() -> int {
+  if (!ctx || !comp || !out || (label_len && !label)) return (plonk::set_last_error("invalid argument", api_fn, __FILE__, __LINE__), PLONK_ERR_ARG);
+  CTX_ENTER(ctx->c, api_fn);
+  std::lock_guard<std::mutex> lkc(comp->mu);
+  HIP_TRY(hipSetDevice(ctx->c.device));
+  if (!ctx->c.srs_table) return PLONK_ERR_NO_SRS;
+  const plonk::Composer& cc = comp->c;
+  plonk_prover_desc d{};
+  d.constraints = cc.constraints();
+  d.label = label;
+  d.label_len = label_len;
+  CircuitSrc src;
+  for (int k = 0; k < QS_COUNT; ++k) {
+    bool any = false;
+    for (const Fr& v : cc.sel[k]) any = any || !v.is_zero();
+    src.selectors[k] = any ? cc.sel[k].data() : nullptr;
+  }
+  for (int w = 0; w < 4; ++w) src.wires[w] = cc.wires[w].data();
+  src.witnesses = cc.witnesses();
+  plonk::Prover* p = nullptr;
+  int rc = prover_build(&ctx->c, &d, &src, &p);
+  if (rc) return rc;
+  BuildGuard guard{p};   // also when the upload throws (std::bad_alloc, answered at api_guard)
+  rc = composer_program_upload(&ctx->c, cc, &p->program);
+  if (rc) return rc;
+  plonk_prover* h = new (std::nothrow) plonk_prover{p, ctx};
+  if (!h) return (plonk::set_last_error(api_fn, "out of host memory", __FILE__, __LINE__), PLONK_ERR_NOMEM);
+  guard.p = nullptr;
+  *out = h;
+  return PLONK_OK;
+  });
+}
+
+int plonk_prover_fill_inputs(plonk_prover* pr, const uint64_t* inputs, uint64_t count, uint64_t* witnesses_out, uint64_t* pi_out) {
+  const char* const api_fn = __func__;
+  return plonk::api_guard(api_fn, [&]() -> int {
+  if (!pr) return (plonk::set_last_error("invalid argument", api_fn, __FILE__, __LINE__), PLONK_ERR_ARG);
+  CTX_ENTER(pr->ctx->c, api_fn);
+  HIP_TRY(hipSetDevice(pr->ctx->c.device));
+  plonk::Prover* p = pr->p;
+  PTRY(inputs_guard(p, inputs, count, api_fn));
+  const Fr* pi = nullptr;
+  PTRY(inputs_fill(p, inputs, &pi));
+  if (pi_out && p->program->npi) memcpy(pi_out, pi, sizeof(Fr) * p->program->npi);
+  if (witnesses_out && p->witnesses) {
+    HIP_TRY(hipMemcpyAsync(witnesses_out, p->wit_vals, sizeof(Fr) * p->witnesses, hipMemcpyDeviceToHost, p->c->stream));
+    HIP_TRY(hipStreamSynchronize(p->c->stream));
+  }
+  return PLONK_OK;
+  });
+}
+
+int plonk_prover_prove_inputs(plonk_prover* pr, const uint64_t* inputs, uint64_t count, const uint64_t* blinders, uint8_t proof[1008],
+                              uint64_t* pi_out) {
+  const char* const api_fn = __func__;
+  return plonk::api_guard(api_fn, [&]() -> int {
+  if (!pr || !blinders || !proof) return (plonk::set_last_error("invalid argument", api_fn, __FILE__, __LINE__), PLONK_ERR_ARG);
+  CTX_ENTER(pr->ctx->c, api_fn);
+  HIP_TRY(hipSetDevice(pr->ctx->c.device));
+  plonk::Prover* p = pr->p;
+  Ctx* c = p->c;
+  PTRY(inputs_guard(p, inputs, count, api_fn));
+  const Fr* pi = nullptr;
+  PTRY(inputs_fill(p, inputs, &pi));
+  const ComposerProgram* pg = p->program;
+  if (pi_out && pg->npi) memcpy(pi_out, pi, sizeof(Fr) * pg->npi);
+  PTRY(poly_gather_wires(c, p->wire_idx, p->wit_vals, p->wires, p->constraints, p->n));
+  return prover_prove(p, p->wires, pg->pi_rows.data(), pi, pg->npi, (const Fr*)blinders, proof);
+  });
+}
+
+int plonk_prover_diagnose_inputs(plonk_prover* pr, const uint64_t* inputs, uint64_t count, plonk_unsat_row* out, uint64_t cap,
+                                 plonk_unsat_info* info) {
+  const char* const api_fn = __func__;
+  return plonk::api_guard(api_fn, [&]() -> int {
+  const auto t0 = std::chrono::steady_clock::now();
+  if (!pr || (cap && !out)) return (plonk::set_last_error("invalid argument", api_fn, __FILE__, __LINE__), PLONK_ERR_ARG);
+  CTX_ENTER(pr->ctx->c, api_fn);
+  HIP_TRY(hipSetDevice(pr->ctx->c.device));
+  plonk::Prover* p = pr->p;
+  Ctx* c = p->c;
+  PTRY(diagnose_guard(p, api_fn));
+  PTRY(inputs_guard(p, inputs, count, api_fn));
+  const Fr* pi = nullptr;
+  PTRY(inputs_fill(p, inputs, &pi));
+  const ComposerProgram* pg = p->program;
+  PTRY(poly_gather_wires(c, p->wire_idx, p->wit_vals, p->wires, p->constraints, p->n));
+  return prover_diagnose(p, p->wires, pg->pi_rows.data(), pi, pg->npi, out, cap, info, t0);
   });
 }
 
