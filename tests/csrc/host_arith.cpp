@@ -1,182 +1,156 @@
 // Host-side shim exposing the product's __host__ __device__ field/curve code
-// (plonk_amd/csrc/field.cuh, curve.cuh) to ctypes so it can be checked bit for
+// (plonk_amd/csrc/field.cuh, curve.cuh, ...) to ctypes so it can be checked bit for
 // bit against the big-int oracle on a CPU-only box.  Test code only.
+// The pure arithmetic bodies live in arith_cases.hpp, shared with the device twin (dev_arith.hip): the h_* entry points
+// below pack their arguments into a case record and run the same body; h_case_<family> runs a whole array of records.
 #include <cstring>
-#include "../../plonk_amd/csrc/curve.cuh"
+#include "arith_cases.hpp"
 using namespace plonk;
-extern "C" {
-void h_fr_mul(const uint32_t* a, const uint32_t* b, uint32_t* o) { Fr x, y; memcpy(&x, a, 32); memcpy(&y, b, 32); Fr r = x * y; memcpy(o, &r, 32); }
-void h_fr_add(const uint32_t* a, const uint32_t* b, uint32_t* o) { Fr x, y; memcpy(&x, a, 32); memcpy(&y, b, 32); Fr r = x + y; memcpy(o, &r, 32); }
-void h_fr_sub(const uint32_t* a, const uint32_t* b, uint32_t* o) { Fr x, y; memcpy(&x, a, 32); memcpy(&y, b, 32); Fr r = x - y; memcpy(o, &r, 32); }
-void h_fr_inv(const uint32_t* a, uint32_t* o) { Fr x; memcpy(&x, a, 32); Fr r = x.inv(); memcpy(o, &r, 32); }
-void h_fr_from_mont(const uint32_t* a, uint32_t* o) { Fr x; memcpy(&x, a, 32); Fr r = x.from_mont(); memcpy(o, &r, 32); }
-void h_fr_consts(uint32_t* o) { Fr g = fr_generator(), w = fr_root_of_unity(), one = Fr::one(); memcpy(o, &g, 32); memcpy(o + 8, &w, 32); memcpy(o + 16, &one, 32); }
-void h_fp_mul(const uint32_t* a, const uint32_t* b, uint32_t* o) { Fp x, y; memcpy(&x, a, 48); memcpy(&y, b, 48); Fp r = x * y; memcpy(o, &r, 48); }
-void h_fp_add(const uint32_t* a, const uint32_t* b, uint32_t* o) { Fp x, y; memcpy(&x, a, 48); memcpy(&y, b, 48); Fp r = x + y; memcpy(o, &r, 48); }
-void h_fp_sub(const uint32_t* a, const uint32_t* b, uint32_t* o) { Fp x, y; memcpy(&x, a, 48); memcpy(&y, b, 48); Fp r = x - y; memcpy(o, &r, 48); }
-void h_fp_inv(const uint32_t* a, uint32_t* o) { Fp x; memcpy(&x, a, 48); Fp r = x.inv(); memcpy(o, &r, 48); }
-// points: affine 96 B (x||y Montgomery); result affine 96 B + return 1, or 0 for identity
-static int out_aff(const G1& p, uint8_t* o) { G1Affine a; bool ok = p.to_affine(&a); memcpy(o, &a, 96); return ok ? 1 : 0; }
-int h_g1_add_aff(const uint8_t* a, const uint8_t* b, uint8_t* o) { G1Affine x, y; memcpy(&x, a, 96); memcpy(&y, b, 96); return out_aff(G1::from_affine(x).add_affine(y), o); }
-int h_g1_add_full(const uint8_t* a, const uint8_t* b, uint8_t* o) {
-  G1Affine x, y; memcpy(&x, a, 96); memcpy(&y, b, 96);
-  // de-normalise both operands so the general formulas are exercised
-  G1 p = G1::from_affine(x).dbl().add_affine(x).add(G1::from_affine(x).dbl().neg());   // = x, with ZZ != 1
-  G1 q = G1::from_affine(y).dbl().add_affine(y).add(G1::from_affine(y).dbl().neg());
-  return out_aff(p.add(q), o);
+using namespace arith;
+
+#define HOST_FAMILY(name, In, Out)                                                                          \
+  extern "C" int h_case_##name(const void* in, size_t in_bytes, void* out, size_t out_bytes, int n) {     \
+    if (n < 0 || in_bytes != (size_t)n * sizeof(In) || out_bytes != (size_t)n * sizeof(Out)) return -1;    \
+    for (int i = 0; i < n; ++i) {   /* through aligned copies: the caller's buffers are byte strings */    \
+      In r;                                                                                                 \
+      Out o;                                                                                                \
+      memcpy(&r, (const char*)in + (size_t)i * sizeof(In), sizeof(In));                                     \
+      case_##name(r, o);                                                                                    \
+      memcpy((char*)out + (size_t)i * sizeof(Out), &o, sizeof(Out));                                        \
+    }                                                                                                       \
+    return 0;                                                                                               \
+  }                                                                                                         \
+  extern "C" int h_record_size_##name(int which) { return (int)(which ? sizeof(Out) : sizeof(In)); }
+ARITH_FAMILIES(HOST_FAMILY)
+
+static void fr_op(uint32_t op, const uint32_t* a, const uint32_t* b, uint32_t* o) {
+  FrIn in{}; in.op = op;
+  if (a) memcpy(in.a, a, 32);
+  if (b) memcpy(in.b, b, 32);
+  FrOut out; case_fr(in, out); memcpy(o, out.r, 32);
 }
-int h_g1_mul_u32(const uint8_t* a, uint32_t k, uint8_t* o) { G1Affine x; memcpy(&x, a, 96); return out_aff(G1::from_affine(x).mul_u32(k), o); }
-int h_g1_neg_add(const uint8_t* a, uint8_t* o) { G1Affine x; memcpy(&x, a, 96); G1Affine n = x; n.y = x.y.neg(); return out_aff(G1::from_affine(x).add_affine(n), o); }
+static void fp_op(uint32_t op, const uint32_t* a, const uint32_t* b, uint32_t* o) {
+  FpIn in{}; in.op = op;
+  if (a) memcpy(in.a, a, 48);
+  if (b) memcpy(in.b, b, 48);
+  FpOut out; case_fp(in, out); memcpy(o, out.r, 48);
+}
+// points: affine 96 B (x||y Montgomery); result affine 96 B + return 1, or 0 for identity
+static int g1_op(uint32_t op, const uint8_t* a, const uint8_t* b, uint32_t k, uint8_t* o) {
+  G1In in{}; in.op = op; in.k = k;
+  if (a) memcpy(in.a, a, 96);
+  if (b) memcpy(in.b, b, 96);
+  G1Out out; case_g1(in, out); memcpy(o, out.p, 96);
+  return (int)out.rc;
+}
+extern "C" {
+void h_fr_mul(const uint32_t* a, const uint32_t* b, uint32_t* o) { fr_op(FR_MUL, a, b, o); }
+void h_fr_add(const uint32_t* a, const uint32_t* b, uint32_t* o) { fr_op(FR_ADD, a, b, o); }
+void h_fr_sub(const uint32_t* a, const uint32_t* b, uint32_t* o) { fr_op(FR_SUB, a, b, o); }
+void h_fr_inv(const uint32_t* a, uint32_t* o) { fr_op(FR_INV, a, nullptr, o); }
+void h_fr_from_mont(const uint32_t* a, uint32_t* o) { fr_op(FR_FROM_MONT, a, nullptr, o); }
+void h_fr_consts(uint32_t* o) { fr_op(FR_GENERATOR, nullptr, nullptr, o); fr_op(FR_ROOT, nullptr, nullptr, o + 8); fr_op(FR_ONE, nullptr, nullptr, o + 16); }
+void h_fp_mul(const uint32_t* a, const uint32_t* b, uint32_t* o) { fp_op(FP_MUL, a, b, o); }
+void h_fp_add(const uint32_t* a, const uint32_t* b, uint32_t* o) { fp_op(FP_ADD, a, b, o); }
+void h_fp_sub(const uint32_t* a, const uint32_t* b, uint32_t* o) { fp_op(FP_SUB, a, b, o); }
+void h_fp_inv(const uint32_t* a, uint32_t* o) { fp_op(FP_INV, a, nullptr, o); }
+int h_g1_add_aff(const uint8_t* a, const uint8_t* b, uint8_t* o) { return g1_op(G1_ADD_AFF, a, b, 0, o); }
+int h_g1_add_full(const uint8_t* a, const uint8_t* b, uint8_t* o) {
+  G1FullIn in; memcpy(in.a, a, 96); memcpy(in.b, b, 96);
+  G1FullOut out; case_g1_full(in, out); memcpy(o, out.p, 96);
+  return (int)out.rc;
+}
+int h_g1_mul_u32(const uint8_t* a, uint32_t k, uint8_t* o) { return g1_op(G1_MUL_U32, a, nullptr, k, o); }
+int h_g1_neg_add(const uint8_t* a, uint8_t* o) { return g1_op(G1_NEG_ADD, a, nullptr, 0, o); }
 }
 // ---- reduced-radix Fp (fp28.cuh) ----
-#include "../../plonk_amd/csrc/fp28.cuh"
-extern "C" {
 // inputs/outputs in the 12 x 32-bit R = 2^384 form; computation done in Fp28
-void h_fp28_mul(const uint32_t* a, const uint32_t* b, uint32_t* o) { Fp x, y; memcpy(&x, a, 48); memcpy(&y, b, 48); Fp r = Fp28::mul(Fp28::from_fp(x), Fp28::from_fp(y)).to_fp(); memcpy(o, &r, 48); }
-void h_fp28_chain(const uint32_t* a, const uint32_t* b, uint32_t* o) {
-  // exercises lazy add/sub bounds: ((a + b) * (a - b + 4p)) - (a*a) + (b*b) ... = 0 ; returns a*b + that
-  Fp x, y; memcpy(&x, a, 48); memcpy(&y, b, 48);
-  Fp28 A = Fp28::from_fp(x), Bv = Fp28::from_fp(y);
-  Fp28 s = Fp28::add(A, Bv), d = Fp28::sub<4>(A, Bv);
-  Fp28 t = Fp28::mul(s, d);                         // a^2 - b^2
-  Fp28 u = Fp28::sub<4>(t, A.sqr());                // -b^2 (+4p)
-  Fp28 v = Fp28::add(u, Bv.sqr());                  // 0 mod p, value < 8p
-  Fp28 w = Fp28::add(Fp28::mul(A, Bv), v);
-  Fp r = w.to_fp(); memcpy(o, &r, 48);
+static uint32_t fp28_op(uint32_t op, const uint32_t* a, const uint32_t* b, uint32_t* o) {
+  Fp28In in{}; in.op = op;
+  memcpy(in.a, a, 48);
+  if (b) memcpy(in.b, b, 48);
+  Fp28Out out; case_fp28(in, out);
+  if (o) memcpy(o, out.r, 48);
+  return out.flags;
 }
-int h_fp28_zero_test(const uint32_t* a) { Fp x; memcpy(&x, a, 48); Fp28 A = Fp28::from_fp(x); Fp28 z = Fp28::sub<4>(A, A); Fp28 z2 = Fp28::sub<32>(Fp28::add(Fp28::add(A, A), A.dbl().dbl()), Fp28::add(A.dbl(), A.dbl().dbl())); return (z.is_zero_mod() ? 1 : 0) | (z2.is_zero_mod() ? 2 : 0) | (A.is_zero_mod() ? 4 : 0); }
-void h_fp28_roundtrip(const uint32_t* a, uint32_t* o) { Fp x; memcpy(&x, a, 48); Fp r = Fp28::from_fp(x).to_fp(); memcpy(o, &r, 48); }
+extern "C" {
+void h_fp28_mul(const uint32_t* a, const uint32_t* b, uint32_t* o) { fp28_op(FP28_MUL, a, b, o); }
+void h_fp28_chain(const uint32_t* a, const uint32_t* b, uint32_t* o) { fp28_op(FP28_CHAIN, a, b, o); }
+int h_fp28_zero_test(const uint32_t* a) { return (int)fp28_op(FP28_ZERO_TEST, a, nullptr, nullptr); }
+void h_fp28_roundtrip(const uint32_t* a, uint32_t* o) { fp28_op(FP28_ROUNDTRIP, a, nullptr, o); }
+}
+static void fp28_raw_op(uint32_t op, const uint32_t* a, const uint32_t* b, const uint32_t* c, const uint32_t* d, uint32_t* o) {
+  Fp28RawIn in{}; in.op = op;
+  memcpy(in.a, a, 56); memcpy(in.b, b, 56);
+  if (c) memcpy(in.c, c, 56);
+  if (d) memcpy(in.d, d, 56);
+  Fp28RawOut out; case_fp28_raw(in, out); memcpy(o, out.r, 56);
 }
 // raw-limb access (14 x u32, possibly lazy): op 0 = mul(a,b), 1 = a.sqr(), 2 = mul2(a,b,c,d)
 extern "C" void h_fp28_raw(int op, const uint32_t* a, const uint32_t* b, const uint32_t* c, const uint32_t* d, uint32_t* o) {
-  Fp28 A, Bv, C, D;
-  memcpy(A.l, a, 56); memcpy(Bv.l, b, 56); memcpy(C.l, c, 56); memcpy(D.l, d, 56);
-  Fp28 r = op == 0 ? Fp28::mul(A, Bv) : op == 1 ? A.sqr() : Fp28::mul2(A, Bv, C, D);
-  memcpy(o, r.l, 56);
+  fp28_raw_op(op == 0 ? RAW_MUL : op == 1 ? RAW_SQR : RAW_MUL2, a, b, c, d, o);
 }
 // lazy helpers on normalised inputs: op 0 = sub_lazy<32>(a,b), 1 = neg_lazy<16>(b), 2 = add_lazy(a,b)
 extern "C" void h_fp28_lazy(int op, const uint32_t* a, const uint32_t* b, uint32_t* o) {
-  Fp28 A, Bv;
-  memcpy(A.l, a, 56); memcpy(Bv.l, b, 56);
-  Fp28 r = op == 0 ? Fp28::sub_lazy<32>(A, Bv) : op == 1 ? Fp28::neg_lazy<16>(Bv) : Fp28::add_lazy(A, Bv);
-  memcpy(o, r.l, 56);
+  fp28_raw_op(op == 0 ? RAW_SUB_LAZY32 : op == 1 ? RAW_NEG_LAZY16 : RAW_ADD_LAZY, a, b, nullptr, nullptr, o);
 }
 
 // ---- XYZZ over Fp28 (curve28.cuh) ----
-#include "../../plonk_amd/csrc/curve28.cuh"
+// n <= G1R_MAX_POINTS points, 96 B each in the 32-bit form; -1 when n is out of range
+static int g1r_op(uint32_t op, const uint8_t* pts, const uint8_t* neg, int n, uint32_t k, uint8_t* o, int* used_pair) {
+  if (n < 0 || n > G1R_MAX_POINTS) return -1;
+  G1rIn in{}; in.op = op; in.n = (uint32_t)n; in.k = k;
+  memcpy(in.pts, pts, 96 * (size_t)n);
+  if (neg) memcpy(in.neg, neg, (size_t)n);
+  G1rOut out; case_g1r(in, out); memcpy(o, out.p, 96);
+  if (used_pair) *used_pair = (int)out.used_pair;
+  return (int)out.rc;
+}
 extern "C" {
-static int out_aff_r(const G1R& p, uint8_t* o) { return out_aff(p.to_g1(), o); }
-// sum_{i<n} (neg[i] ? -P_i : P_i) with mixed additions, points 96 B each in the 32-bit form
-int h_g1r_accumulate(const uint8_t* pts, const uint8_t* neg, int n, uint8_t* o) {
-  G1R acc = G1R::identity();
-  for (int i = 0; i < n; ++i) {
-    G1Affine a; memcpy(&a, pts + 96 * i, 96);
-    Fp28 x = Fp28::from_fp(a.x), y = Fp28::from_fp(a.y);
-    if (neg[i]) y = Fp28::sub<4>(Fp28::zero(), y);
-    acc = acc.add_affine(x, y);
-  }
-  return out_aff_r(acc, o);
-}
+// sum_{i<n} (neg[i] ? -P_i : P_i) with mixed additions
+int h_g1r_accumulate(const uint8_t* pts, const uint8_t* neg, int n, uint8_t* o) { return g1r_op(G1R_ACCUMULATE, pts, neg, n, 0, o, nullptr); }
 // (sum of first half) + (sum of second half) via the full addition; then * k
-int h_g1r_tree(const uint8_t* pts, int n, uint32_t k, uint8_t* o) {
-  G1R a = G1R::identity(), b = G1R::identity();
-  for (int i = 0; i < n; ++i) {
-    G1Affine p; memcpy(&p, pts + 96 * i, 96);
-    Fp28 x = Fp28::from_fp(p.x), y = Fp28::from_fp(p.y);
-    if (i < n / 2) a = a.add_affine(x, y); else b = b.add_affine(x, y);
-  }
-  G1R s = a.add(b);
-  s = s.add(s);            // doubling through add()
-  return out_aff_r(s.mul_u32(k), o);
-}
-// The accumulation lanes' first step (msm.hip ACC_FIRST_PAIR): entries 0 and 1 through add_affine_pair when their x differ
-// (signs applied lazily as 4p - y, as the kernels do), then the rest through add_affine.  Returns like h_g1r_accumulate;
-// *used_pair = 1 when the pair formula ran.
+int h_g1r_tree(const uint8_t* pts, int n, uint32_t k, uint8_t* o) { return g1r_op(G1R_TREE, pts, nullptr, n, k, o, nullptr); }
+// The accumulation lanes' first step (msm.hip ACC_FIRST_PAIR); *used_pair = 1 when the pair formula ran.
 int h_g1r_accumulate_pair_first(const uint8_t* pts, const uint8_t* neg, int n, uint8_t* o, int* used_pair) {
-  auto signed_y = [](const Fp28& y, bool ng) {
-    Fp28 r;
-    for (int i = 0; i < Fp28::N; ++i) r.l[i] = ng ? Fp28::pad<4>(i) - y.l[i] : y.l[i];
-    return r;
-  };
-  G1R acc = G1R::identity();
-  int k0 = 0;
-  *used_pair = 0;
-  if (n >= 2) {
-    G1Affine a, b; memcpy(&a, pts, 96); memcpy(&b, pts + 96, 96);
-    const Fp28 xa = Fp28::from_fp(a.x), ya = Fp28::from_fp(a.y), xb = Fp28::from_fp(b.x), yb = Fp28::from_fp(b.y);
-    if (G1R::pair_distinct(xa, xb)) {
-      acc = G1R::add_affine_pair(xa, signed_y(ya, neg[0] != 0), xb, signed_y(yb, neg[1] != 0));
-      k0 = 2;
-      *used_pair = 1;
-    }
-  }
-  for (int i = k0; i < n; ++i) {
-    G1Affine a; memcpy(&a, pts + 96 * i, 96);
-    acc = acc.add_affine(Fp28::from_fp(a.x), signed_y(Fp28::from_fp(a.y), neg[i] != 0));
-  }
-  return out_aff_r(acc, o);
+  return g1r_op(G1R_PAIR_FIRST, pts, neg, n, 0, o, used_pair);
 }
-// [k] P through the endomorphism (curve28.cuh g1r_mul_glv: the group FFT's scalar multiplication); k: 8 x 32-bit limbs, canonical.
-// pre = doublings applied to P first (an operand with the bounds the FFT's butterflies hand over, not a fresh affine point)
+int h_g1r_affine_roundtrip(const uint8_t* pt, uint8_t* o) { return g1r_op(G1R_AFFINE_ROUNDTRIP, pt, nullptr, 1, 0, o, nullptr); }
+// [k] P through the endomorphism (curve28.cuh g1r_mul_glv); k: 8 x 32-bit limbs, canonical; pre = doublings applied to P first
 int h_g1r_mul_glv(const uint8_t* pt, const uint32_t* k, int pre, uint8_t* o) {
-  G1Affine p; memcpy(&p, pt, 96);
-  G1R q = G1R::from_affine(Fp28::from_fp(p.x), Fp28::from_fp(p.y));
-  for (int i = 0; i < pre; ++i) q = q.add(q);
-  return out_aff_r(g1r_mul_glv(q, k), o);
+  GlvIn in{}; in.op = GLV_MUL; in.pre = (uint32_t)pre;
+  memcpy(in.k, k, 32); memcpy(in.pt, pt, 96);
+  GlvOut out; case_glv(in, out); memcpy(o, out.p, 96);
+  return (int)out.rc;
 }
 void h_glv_split(const uint32_t* k, uint64_t* out4) {
-  const GlvScalar g = glv_split(k);
-  out4[0] = g.k1[0]; out4[1] = g.k1[1]; out4[2] = g.k2[0]; out4[3] = g.k2[1];
-}
-int h_g1r_affine_roundtrip(const uint8_t* pt, uint8_t* o) {
-  G1Affine p; memcpy(&p, pt, 96);
-  G1R q = G1R::from_affine(Fp28::from_fp(p.x), Fp28::from_fp(p.y)).dbl().dbl();
-  Fp28 x, y; g1r_to_affine(q, &x, &y);
-  G1Affine r; r.x = x.to_fp(); r.y = y.to_fp(); memcpy(o, &r, 96); return 1;
+  GlvIn in{}; in.op = GLV_SPLIT;
+  memcpy(in.k, k, 32);
+  GlvOut out; case_glv(in, out);
+  for (int i = 0; i < 4; ++i) out4[i] = (uint64_t)out.split[2 * i] | ((uint64_t)out.split[2 * i + 1] << 32);
 }
 }
 // ---- reduced-radix Fr (fr29.cuh) ----
-#include "../../plonk_amd/csrc/fr29.cuh"
+static void fr29_op(uint32_t op, uint32_t stages, const uint32_t* a, const uint32_t* b, const uint32_t* w, uint32_t* o0, uint32_t* o1) {
+  Fr29In in{}; in.op = op; in.stages = stages;
+  memcpy(in.a, a, 32); memcpy(in.b, b, 32);
+  if (w) memcpy(in.w, w, 32);
+  Fr29Out out; case_fr29(in, out);
+  memcpy(o0, out.o0, 32);
+  if (o1) memcpy(o1, out.o1, 32);
+}
 extern "C" {
 // DIF butterfly on Montgomery (R = 2^256) inputs: out0 = a + b, out1 = (a - b) * w
-void h_fr29_butterfly(const uint32_t* a, const uint32_t* b, const uint32_t* w, uint32_t* o0, uint32_t* o1) {
-  Fr x, y, t; memcpy(&x, a, 32); memcpy(&y, b, 32); memcpy(&t, w, 32);
-  Fr29 A = Fr29::from_fr(x), Bv = Fr29::from_fr(y), W = Fr29::twiddle_from_fr(t);
-  Fr r0 = Fr29::add_csub(A, Bv).to_fr();
-  Fr r1 = Fr29::mul(Fr29::sub_lazy(A, Bv), W).to_fr();
-  memcpy(o0, &r0, 32); memcpy(o1, &r1, 32);
-}
-// 9 chained stages on a vector of 2 elements: exercises the lazy ranges (sum path and product path)
-void h_fr29_chain(const uint32_t* a, const uint32_t* b, const uint32_t* w, int stages, uint32_t* o0, uint32_t* o1) {
-  Fr x, y, t; memcpy(&x, a, 32); memcpy(&y, b, 32); memcpy(&t, w, 32);
-  Fr29 A = Fr29::from_fr(x), Bv = Fr29::from_fr(y), W = Fr29::twiddle_from_fr(t);
-  for (int s = 0; s < stages; ++s) {
-    Fr29 n0 = Fr29::add_csub(A, Bv);
-    Fr29 n1 = Fr29::mul(Fr29::sub_lazy(A, Bv), W);
-    A = n0; Bv = n1;
-  }
-  Fr r0 = A.to_fr(), r1 = Bv.to_fr();
-  memcpy(o0, &r0, 32); memcpy(o1, &r1, 32);
-}
-void h_fr29_mul2(const uint32_t* a, const uint32_t* w1, const uint32_t* w2, uint32_t* o) {   // a * (w1 * w2)
-  Fr x, t1, t2; memcpy(&x, a, 32); memcpy(&t1, w1, 32); memcpy(&t2, w2, 32);
-  Fr29 W = Fr29::mul(Fr29::twiddle_from_fr(t1), Fr29::twiddle_from_fr(t2));
-  Fr r = Fr29::mul(Fr29::from_fr(x), W).to_fr(); memcpy(o, &r, 32);
-}
-}
-extern "C" void h_fr29_sub_reduce(const uint32_t* a, const uint32_t* b, uint32_t* o) {
-  Fr x, y; memcpy(&x, a, 32); memcpy(&y, b, 32);
-  // operands first pushed to the top of the lazy range: (x + 0) via add_csub keeps them, so use doubled values
-  Fr29 A = Fr29::from_fr(x), Bv = Fr29::from_fr(y);
-  Fr r = Fr29::sub_reduce(Fr29::add_csub(A, A), Fr29::add_csub(Bv, Bv)).to_fr(); memcpy(o, &r, 32);
+void h_fr29_butterfly(const uint32_t* a, const uint32_t* b, const uint32_t* w, uint32_t* o0, uint32_t* o1) { fr29_op(FR29_BUTTERFLY, 0, a, b, w, o0, o1); }
+// chained stages on a vector of 2 elements: exercises the lazy ranges (sum path and product path)
+void h_fr29_chain(const uint32_t* a, const uint32_t* b, const uint32_t* w, int stages, uint32_t* o0, uint32_t* o1) { fr29_op(FR29_CHAIN, (uint32_t)stages, a, b, w, o0, o1); }
+void h_fr29_mul2(const uint32_t* a, const uint32_t* w1, const uint32_t* w2, uint32_t* o) { fr29_op(FR29_MUL2, 0, a, w1, w2, o, nullptr); }   // a * (w1 * w2)
+void h_fr29_sub_reduce(const uint32_t* a, const uint32_t* b, uint32_t* o) { fr29_op(FR29_SUB_REDUCE, 0, a, b, nullptr, o, nullptr); }
 }
 
 // ---- host transcript (transcript.hpp): Merlin's published test protocol ----
-#include "../../plonk_amd/csrc/transcript.hpp"
 extern "C" void h_merlin_simple(uint8_t out[32]) {
-  plonk::Transcript t((const uint8_t*)"test protocol", 13);
-  t.append_message("some label", (const uint8_t*)"some data", 9);
-  t.challenge_bytes("challenge", out, 32);
+  MerlinIn in{}; MerlinOut o; case_merlin(in, o); memcpy(out, o.challenge, 32);
 }
 
 // ---- widgets.hpp: lowest 7 coefficients of the quotient from the lowest 7 of every polynomial ----
@@ -305,71 +279,36 @@ extern "C" int h_sigma_mappings(const uint32_t* a, const uint32_t* b, const uint
   return plonk::sigma_mappings(wires, constraints, n, witnesses, out) ? 0 : -1;
 }
 
-#include "../../plonk_amd/csrc/g1codec.cuh"
 // G1Affine::from_bytes on a 48-byte compressed encoding (g1codec.cuh): returns the decoder's code, out = x || y (96 B, Montgomery)
 extern "C" int h_g1_decompress48(const uint8_t* in, uint8_t* out96) {
-  G1Affine a;
-  memset(&a, 0, sizeof a);
-  const int rc = g1_decompress48(in, &a);
-  memcpy(out96, &a, 96);
-  return rc;
+  DecompressIn r; memcpy(r.enc, in, 48);
+  DecompressOut o; case_decompress(r, o); memcpy(out96, o.p, 96);
+  return (int)o.rc;
 }
 
 // ---- msm_recode.cuh: scalar -> (row, bucket, sign) digits of both recodings ----
-#include "../../plonk_amd/csrc/msm_recode.cuh"
-// canonical scalar (8 x u32) -> out[4 j .. 4 j + 3] = slot, row, bucket, sign; returns the number of digits
+// canonical scalar (8 x u32) -> out[4 j .. 4 j + 3] = slot, row, bucket, sign; returns the number of digits.
+// bitpos: 0 windows, 1 width-17 NAF, 2 the same from the strided LDS-parked form, 21 width-21 NAF, 120 / 116 even positions
 extern "C" int h_msm_recode(const uint32_t* scalar, int bitpos, uint32_t* out) {
-  Big<8> s;
-  memcpy(s.l, scalar, 32);
-  int n = 0;
-  auto emit = [&](int slot, uint32_t row, uint32_t bucket, uint32_t sign) {
-    out[4 * n] = (uint32_t)slot; out[4 * n + 1] = row; out[4 * n + 2] = bucket; out[4 * n + 3] = sign;
-    ++n;
-  };
-  if (bitpos == 120 || bitpos == 116) {   // even-position digits (half-density tables), width 20 / 16, LDS-parked form
-    uint32_t park[9 * 3];
-    for (int k = 0; k < 8; ++k) park[3 * k + 1] = s.l[k];
-    park[3 * 8 + 1] = 0;
-    if (bitpos == 120) for_each_digit_even<20>(StridedLimbs{park + 1, 3}, emit);
-    else for_each_digit_even<16>(StridedLimbs{park + 1, 3}, emit);
-    return n;
-  }
-  if (bitpos == 21) {  // the 2^19-bucket variant's digit width
-    for_each_digit_naf<21>(s, emit);
-  } else if (bitpos == 2) {   // the kernels' form: the scalar parked limb-major with a stride (StridedLimbs)
-    uint32_t park[9 * 3];
-    for (int j = 0; j < 9; ++j) { park[3 * j] = 0xdeadbeefu; park[3 * j + 1] = j < 8 ? s.l[j] : 0u; park[3 * j + 2] = 0x12345678u; }
-    for_each_digit_bitpos(StridedLimbs{park + 1, 3}, emit);
-  } else {
-    for_each_digit(s, bitpos ? MSM_ROWS_BITPOS : MSM_ROWS_WINDOW, emit);
-  }
-  return n;
+  RecodeIn r; r.mode = (uint32_t)bitpos; memcpy(r.s, scalar, 32);
+  RecodeOut o; case_recode(r, o);
+  memcpy(out, o.d, 16 * (o.n < (uint32_t)MSM_DIGITS ? o.n : (uint32_t)MSM_DIGITS));
+  return (int)o.n;
 }
 
 // ---- fp_safegcd.cuh: Bernstein-Yang inversion against Fermat (fp28_inv) and the oracle ----
-#include "../../plonk_amd/csrc/fp_safegcd.cuh"
+static void safegcd_op(uint32_t op, const uint32_t* a, uint32_t* o, size_t bytes) {
+  SafegcdIn in{}; in.op = op; memcpy(in.a, a, bytes);
+  SafegcdOut out; case_safegcd(in, out); memcpy(o, out.r, bytes);
+}
 // a: Fp (12 x u32, R = 2^384 Montgomery) -> o: its inverse in the same form, through Fp28 and the safegcd inverse
-extern "C" void h_fp_inv_gcd(const uint32_t* a, uint32_t* o) {
-  Fp x; memcpy(&x, a, 48);
-  Fp r = fp28_inv_gcd(Fp28::from_fp(x)).to_fp();
-  memcpy(o, &r, 48);
-}
+extern "C" void h_fp_inv_gcd(const uint32_t* a, uint32_t* o) { safegcd_op(GCD_FP28, a, o, 48); }
 // same input scaled lazily (value 5x + 3x = 8x as unreduced limbs < 64p): the inverse of 8x
-extern "C" void h_fp_inv_gcd_lazy(const uint32_t* a, uint32_t* o) {
-  Fp x; memcpy(&x, a, 48);
-  const Fp28 A = Fp28::from_fp(x);
-  const Fp28 A8 = Fp28::add(Fp28::add(A.dbl().dbl(), A), Fp28::add(A.dbl(), A));
-  Fp r = fp28_inv_gcd(A8).to_fp();
-  memcpy(o, &r, 48);
-}
-
+extern "C" void h_fp_inv_gcd_lazy(const uint32_t* a, uint32_t* o) { safegcd_op(GCD_FP28_LAZY, a, o, 48); }
 // Fr: a (8 x u32, R = 2^256 Montgomery) -> its inverse in the same form, through twiddle form and the safegcd inverse
-extern "C" void h_fr_inv_gcd(const uint32_t* a, uint32_t* o) {
-  Fr x; memcpy(&x, a, 32);
-  const Fr29 inv_t = fr29_inv_gcd_tw(Fr29::twiddle_from_fr(x));          // x^-1 * 2^261
-  Fr r = Fr29::mul(inv_t, Fr29::from_fr(Fr::one())).to_fr();              // * R / 2^261 = x^-1 R
-  memcpy(o, &r, 32);
-}
+extern "C" void h_fr_inv_gcd(const uint32_t* a, uint32_t* o) { safegcd_op(GCD_FR29_TW, a, o, 32); }
+// the composer's out-of-line inversion (composer_core.hpp cg_inv)
+extern "C" void h_cg_inv(const uint32_t* a, uint32_t* o) { safegcd_op(GCD_CG_INV, a, o, 32); }
 
 // ---- hostg2.hpp: validity of a compressed G2 encoding (OpeningKey::from_slice's test of h and x_h) ----
 #include "../../plonk_amd/csrc/hostg2.hpp"
@@ -384,11 +323,7 @@ extern "C" void h_fp64_inv(const uint8_t in[48], int fermat, uint8_t out[48]) {
   memcpy(out, r.l, 48);
 }
 // the Montgomery-in / Montgomery-out Fr inverse the host driver uses per proof (fp_safegcd.cuh fr_inv_gcd)
-extern "C" void h_fr_inv_gcd_mont(const uint32_t* a, uint32_t* o) {
-  Fr x; memcpy(&x, a, 32);
-  const Fr r = fr_inv_gcd(x);
-  memcpy(o, &r, 32);
-}
+extern "C" void h_fr_inv_gcd_mont(const uint32_t* a, uint32_t* o) { safegcd_op(GCD_FR_MONT, a, o, 32); }
 
 // ---- api_guard.hpp: the exception barrier every int-returning C-ABI entry point runs inside ----
 #include <cstdio>

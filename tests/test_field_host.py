@@ -1,5 +1,8 @@
 """Product field/curve code (plonk_amd/csrc/field.cuh, curve.cuh) compiled for the
-HOST and compared bit for bit with the big-int oracle.  CPU-only."""
+HOST and compared bit for bit with the big-int oracle.  CPU-only.
+
+The operand lists come from tests/arith_vectors.py, which tests/test_gpu_field_device.py runs through the device build of
+the same case bodies (tests/csrc/arith_cases.hpp)."""
 import ctypes
 import os
 import random
@@ -7,6 +10,8 @@ import subprocess
 
 import pytest
 
+import arith_vectors as V
+from arith_vectors import edge_values
 from oracle import bls12_381 as E
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -20,7 +25,8 @@ def build_host_lib():
     src = os.path.join(HERE, "csrc", "host_arith.cpp")
     hdrs = [os.path.join(HERE, "..", "plonk_amd", "csrc", h)
             for h in ("field.cuh", "curve.cuh", "fp28.cuh", "curve28.cuh", "fr29.cuh", "transcript.hpp", "widgets.hpp", "hostg1.hpp", "permutation.hpp", "g1codec.cuh",
-                      "msm_recode.cuh", "fp_safegcd.cuh", "hostg2.hpp", "api_guard.hpp", "finish_pool.hpp")]
+                      "msm_recode.cuh", "fp_safegcd.cuh", "hostg2.hpp", "api_guard.hpp", "finish_pool.hpp", "composer_core.hpp")]
+    hdrs.append(os.path.join(HERE, "csrc", "arith_cases.hpp"))
     if not os.path.exists(SO) or any(os.path.getmtime(f) > os.path.getmtime(SO) for f in [src] + hdrs):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-pthread", src, "-o", SO])
     return ctypes.CDLL(SO)
@@ -49,24 +55,61 @@ def fp_val(buf):
     return sum(int(v) << (32 * i) for i, v in enumerate(buf)) * E.FP_RINV % P
 
 
-def edge_values(mod, rnd, n=60):
-    vals = [0, 1, 2, mod - 1, mod - 2, (mod - 1) // 2, (1 << 32) - 1, 1 << 32, (1 << 255) % mod]
-    return vals + [rnd.randrange(mod) for _ in range(n)]
+@pytest.mark.parametrize("name", V.FAMILIES)
+def test_shared_vectors_on_host(lib, name):
+    """every family of tests/arith_vectors.py through the record interface (h_case_<family>): the same records, bodies and
+    checks the device back end runs, here compiled by g++"""
+    fam = V.family(name)
+    rc, out = fam.run(lib, "h_")
+    assert rc == 0
+    fam.check(out)
+
+
+def test_vector_families_have_new_operand_classes():
+    """the classes random operands never reach: sums of exactly m - 1, m, m + 1, equal operands, m - 1 against 1, 2, m - 1,
+    and limbs saturated in the 28-, 29- and 32-bit views while the value stays below the modulus"""
+    for m, views, pairs in ((Q, V.FR_VIEWS, V.fr_binary_pairs()[1]), (P, V.FP_VIEWS, V.fp_binary_pairs()[1]),
+                            (P, V.FP_VIEWS, V.fp28_cases()[1]), (Q, V.FR_VIEWS, V.fr29_sub_reduce_pairs()[1])):
+        for rbits in [0] + [r for _, _, r in views]:       # as values, and as the residues a R + b R the limbs hold
+            sums = {(a << rbits) % m + (b << rbits) % m for a, b in pairs}
+            assert {m - 1, m, m + 1} <= sums
+        assert {(m - 1, 1), (m - 1, 2), (m - 1, m - 1), (0, 0), (1, 1)} <= set(pairs)
+        for width, limbs, rbits in views:
+            full = (1 << width) - 1
+            assert any(a < m and all((a >> (width * i)) & full == full for i in range(limbs - 1)) for a, _ in pairs)
+            assert any(all(((a << rbits) % m >> (width * i)) & full == full for i in range(limbs - 1)) for a, _ in pairs)
+
+
+def test_every_vector_family_has_a_host_and_a_device_runner(lib):
+    """a family of the vector module runs on both back ends or on neither: h_case_<name> in the host build, d_case_<name> in
+    the device build (tests/_build/libdev_arith.so, built by build(); loading it needs no GPU), with equal record sizes"""
+    import re
+    src = open(os.path.join(HERE, "csrc", "arith_cases.hpp")).read()
+    listed = re.findall(r"^\s+X\((\w+),", src, re.M)
+    assert sorted(listed) == sorted(V.FAMILIES) and len(set(listed)) == len(listed)
+    dev_so = os.path.join(HERE, "_build", "libdev_arith.so")
+    assert os.path.exists(dev_so), "tests/_build/libdev_arith.so is missing: run build() of __graft_entry__.py"
+    dev = ctypes.CDLL(dev_so)
+    for name in V.FAMILIES:
+        assert hasattr(lib, "h_case_" + name), name
+        assert hasattr(dev, "d_case_" + name), name
+        fam = V.family(name)
+        for which, st in ((0, fam.in_struct), (1, fam.out_struct)):
+            assert getattr(lib, "h_record_size_" + name)(which) == st.size
+            assert getattr(dev, "d_record_size_" + name)(which) == st.size
 
 
 def test_fr_ops_match_oracle(lib):
-    rnd = random.Random(1)
-    vals = edge_values(Q, rnd)
+    old, new = V.fr_binary_pairs()
     out = (ctypes.c_uint32 * 8)()
-    for a in vals:
-        for b in vals[:12] + [rnd.randrange(Q)]:
-            lib.h_fr_mul(fr_limbs(a), fr_limbs(b), out)
-            assert fr_val(out) == a * b % Q
-            lib.h_fr_add(fr_limbs(a), fr_limbs(b), out)
-            assert fr_val(out) == (a + b) % Q
-            lib.h_fr_sub(fr_limbs(a), fr_limbs(b), out)
-            assert fr_val(out) == (a - b) % Q
-    for a in vals[1:20]:
+    for a, b in old + new:
+        lib.h_fr_mul(fr_limbs(a), fr_limbs(b), out)
+        assert fr_val(out) == a * b % Q
+        lib.h_fr_add(fr_limbs(a), fr_limbs(b), out)
+        assert fr_val(out) == (a + b) % Q
+        lib.h_fr_sub(fr_limbs(a), fr_limbs(b), out)
+        assert fr_val(out) == (a - b) % Q
+    for a in V.fr_inv_values():
         lib.h_fr_inv(fr_limbs(a), out)
         assert fr_val(out) == pow(a, -1, Q)
     lib.h_fr_from_mont(fr_limbs(12345), out)
@@ -78,7 +121,7 @@ def test_fr_results_are_canonical_limbs(lib):
     out = (ctypes.c_uint32 * 8)()
     lib.h_fr_sub(fr_limbs(0), fr_limbs(1), out)
     limbs64 = [int(out[2 * i]) | int(out[2 * i + 1]) << 32 for i in range(4)]
-    assert limbs64 == [0xfffffffd00000003, 0xfb38ec08fffb13fc, 0x99ad88181ce5880f, 0x5bc8f5f97cd877d8]
+    assert limbs64 == V.FR_MINUS_ONE_LIMBS64 == [0xfffffffd00000003, 0xfb38ec08fffb13fc, 0x99ad88181ce5880f, 0x5bc8f5f97cd877d8]
 
 
 def test_fr_constants(lib):
@@ -90,26 +133,22 @@ def test_fr_constants(lib):
 
 
 def test_fp_ops_match_oracle(lib):
-    rnd = random.Random(2)
-    vals = edge_values(P, rnd, 40)
+    old, new = V.fp_binary_pairs()
     out = (ctypes.c_uint32 * 12)()
-    for a in vals:
-        for b in vals[:10] + [rnd.randrange(P)]:
-            lib.h_fp_mul(fp_limbs(a), fp_limbs(b), out)
-            assert fp_val(out) == a * b % P
-            lib.h_fp_add(fp_limbs(a), fp_limbs(b), out)
-            assert fp_val(out) == (a + b) % P
-            lib.h_fp_sub(fp_limbs(a), fp_limbs(b), out)
-            assert fp_val(out) == (a - b) % P
-    for a in vals[1:8]:
+    for a, b in old + new:
+        lib.h_fp_mul(fp_limbs(a), fp_limbs(b), out)
+        assert fp_val(out) == a * b % P
+        lib.h_fp_add(fp_limbs(a), fp_limbs(b), out)
+        assert fp_val(out) == (a + b) % P
+        lib.h_fp_sub(fp_limbs(a), fp_limbs(b), out)
+        assert fp_val(out) == (a - b) % P
+    for a in V.fp_inv_values():
         lib.h_fp_inv(fp_limbs(a), out)
         assert fp_val(out) == pow(a, -1, P)
 
 
 def test_g1_group_law_matches_oracle(lib):
-    rnd = random.Random(3)
-    G = E.G1_GEN
-    pts = [E.g1_mul(G, rnd.randrange(1, Q)) for _ in range(6)]
+    pts = V.g1_points()
     out = (ctypes.c_uint8 * 96)()
     for a in pts:
         for b in pts:
@@ -119,7 +158,7 @@ def test_g1_group_law_matches_oracle(lib):
             ok = lib.h_g1_add_full(ra, rb, out)
             assert ok == 1 and E.g1_from_raw96(bytes(out)) == E.g1_add(a, b)
         assert lib.h_g1_neg_add(E.g1_to_raw96(a), out) == 0     # P + (-P) = identity
-        for k in (1, 2, 3, 0xFFFF, 0x80000001):
+        for k in V.G1_MUL_SCALARS:
             ok = lib.h_g1_mul_u32(E.g1_to_raw96(a), k, out)
             assert ok == 1 and E.g1_from_raw96(bytes(out)) == E.g1_mul(a, k)
         assert lib.h_g1_mul_u32(E.g1_to_raw96(a), 0, out) == 0
@@ -127,13 +166,17 @@ def test_g1_group_law_matches_oracle(lib):
 
 def test_fp28_reduced_radix_matches_oracle(lib):
     """fp28.cuh (14 x 28-bit limbs, lazy reduction) against big ints, through the 32-bit form."""
-    rnd = random.Random(9)
-    vals = edge_values(P, rnd, 60)
+    per_a, new = V.fp28_cases()
     out = (ctypes.c_uint32 * 12)()
-    for a in vals:
+    for a, b in new:
+        lib.h_fp28_mul(fp_limbs(a), fp_limbs(b), out)
+        assert fp_val(out) == a * b % P
+        lib.h_fp28_chain(fp_limbs(a), fp_limbs(b), out)
+        assert fp_val(out) == a * b % P
+    for a, bs in per_a:
         lib.h_fp28_roundtrip(fp_limbs(a), out)
         assert fp_val(out) == a
-        for b in vals[:9] + [rnd.randrange(P), rnd.randrange(P)]:
+        for b in bs:
             lib.h_fp28_mul(fp_limbs(a), fp_limbs(b), out)
             assert fp_val(out) == a * b % P
             lib.h_fp28_chain(fp_limbs(a), fp_limbs(b), out)
@@ -146,7 +189,6 @@ def test_fp28_lazy_operands_sqr_and_fused_product(lib):
     """fp28.cuh: dedicated squaring, mul2 (two products, one reduction) and lazy (un-normalised,
     limbs < 2^30) operands, checked on raw limbs incl. the all-ones patterns that maximise the
     64-bit column accumulators."""
-    rnd = random.Random(28)
     M28 = (1 << 28) - 1
     RINV = pow(1 << 392, -1, P)
     A14 = ctypes.c_uint32 * 14
@@ -168,14 +210,15 @@ def test_fp28_lazy_operands_sqr_and_fused_product(lib):
         lib.h_fp28_lazy(op, A14(*a), A14(*b), out)
         return list(out)
 
-    ones = [M28] * 13 + [0x1a010]            # < p, every low limb saturated
-    norm = [limbs(rnd.randrange(2 * P)) for _ in range(6)] + [ones, limbs(0), limbs(1), limbs(P - 1), limbs(2 * P - 1)]
+    norm = V.fp28_raw_operands()             # random < 2p, the all-ones pattern (< p, every low limb saturated), 0, 1, p - 1, 2p - 1
+    assert V.FP28_ONES in norm and limbs(2 * P - 1) in norm
     zero = limbs(0)
     for a in norm:
         for b in norm:
             # lazy minuend/subtrahend combos (values: a - b + 32p < 34p needs b < 16p: ok, b < 2p)
             la = lazy(0, a, b)
             assert max(la) < (1 << 30) and val(la) == val(a) + 32 * P - val(b)
+            assert la == [x + p - y for x, p, y in zip(a, V.FP28_PAD32, b)]
             nb = lazy(1, zero, b)
             assert val(nb) == 16 * P - val(b)
             r = run(1, la, zero, zero, zero)                       # sqr of a lazy operand, value < 34p
@@ -194,17 +237,13 @@ def test_fp28_lazy_operands_sqr_and_fused_product(lib):
 def test_g1_xyzz_over_fp28_matches_oracle(lib):
     """curve28.cuh: lazily-reduced XYZZ formulas — long accumulation chains (bounds must stay
     closed), negated operands, P + P and P + (-P) through the mixed and the full addition."""
-    rnd = random.Random(12)
-    G = E.G1_GEN
-    pts = [E.g1_mul(G, rnd.randrange(1, Q)) for _ in range(40)]
+    pts = V.g1r_points()
     raw = b"".join(E.g1_to_raw96(p) for p in pts)
     out = (ctypes.c_uint8 * 96)()
-    for n in (1, 2, 3, 17, 40):
-        neg = bytes(rnd.randrange(2) for _ in range(n))
-        ok = lib.h_g1r_accumulate(raw, neg, n, out)
-        exp = None
-        for p, s in zip(pts[:n], neg):
-            exp = E.g1_add(exp, (p[0], (E.P - p[1]) % E.P) if s else p)
+    assert [len(sel) for sel, _ in V.g1r_accumulate_cases()[:5]] == [1, 2, 3, 17, 40]
+    for sel, neg in V.g1r_accumulate_cases():
+        ok = lib.h_g1r_accumulate(b"".join(E.g1_to_raw96(p) for p in sel), bytes(neg), len(sel), out)
+        exp = V.g1r_sum(sel, neg)
         assert (ok == 1) == (exp is not None)
         if exp is not None:
             assert E.g1_from_raw96(bytes(out)) == exp
@@ -228,39 +267,35 @@ def test_g1_xyzz_over_fp28_matches_oracle(lib):
 
 def test_fr29_reduced_radix_butterflies_match_oracle(lib):
     """fr29.cuh: lazy DIF butterflies (a + b, (a - b) w) incl. 9 chained stages."""
-    rnd = random.Random(29)
-    vals = edge_values(Q, rnd, 40)
+    old, new = V.fr29_cases()
     o0, o1 = (ctypes.c_uint32 * 8)(), (ctypes.c_uint32 * 8)()
-    for a in vals:
-        for b in vals[:10] + [rnd.randrange(Q)]:
-            w = rnd.choice(vals)
-            lib.h_fr29_butterfly(fr_limbs(a), fr_limbs(b), fr_limbs(w), o0, o1)
-            assert fr_val(o0) == (a + b) % Q and fr_val(o1) == (a - b) * w % Q
-            # outputs must be canonical limbs
-            assert sum(int(v) << (32 * i) for i, v in enumerate(o0)) < Q
-            x, y = a, b
-            for _ in range(9):
-                x, y = (x + y) % Q, (x - y) * w % Q
-            lib.h_fr29_chain(fr_limbs(a), fr_limbs(b), fr_limbs(w), 9, o0, o1)
-            assert fr_val(o0) == x and fr_val(o1) == y
-            lib.h_fr29_mul2(fr_limbs(a), fr_limbs(b), fr_limbs(w), o0)
-            assert fr_val(o0) == a * b * w % Q
+    for a, b, w in old + new:
+        lib.h_fr29_butterfly(fr_limbs(a), fr_limbs(b), fr_limbs(w), o0, o1)
+        assert fr_val(o0) == (a + b) % Q and fr_val(o1) == (a - b) * w % Q
+        # outputs must be canonical limbs
+        assert sum(int(v) << (32 * i) for i, v in enumerate(o0)) < Q
+        x, y = a, b
+        for _ in range(9):
+            x, y = (x + y) % Q, (x - y) * w % Q
+        lib.h_fr29_chain(fr_limbs(a), fr_limbs(b), fr_limbs(w), 9, o0, o1)
+        assert fr_val(o0) == x and fr_val(o1) == y
+        lib.h_fr29_mul2(fr_limbs(a), fr_limbs(b), fr_limbs(w), o0)
+        assert fr_val(o0) == a * b * w % Q
 
 
 def test_fr29_sub_reduce(lib):
-    rnd = random.Random(31)
-    vals = edge_values(Q, rnd, 60)
+    old, new = V.fr29_sub_reduce_pairs()
     o = (ctypes.c_uint32 * 8)()
-    for a in vals:
-        for b in vals[:12] + [rnd.randrange(Q)]:
-            lib.h_fr29_sub_reduce(fr_limbs(a), fr_limbs(b), o)
-            assert fr_val(o) == (2 * a - 2 * b) % Q
+    for a, b in old + new:
+        lib.h_fr29_sub_reduce(fr_limbs(a), fr_limbs(b), o)
+        assert fr_val(o) == (2 * a - 2 * b) % Q
 
 
 def test_host_transcript_matches_merlin_vector(lib):
     """transcript.hpp (the C++ Merlin / STROBE-128 / Keccak-f[1600] used by prover.hip) on Merlin's
     published `equivalence_simple` vector."""
     from test_oracle_kat import MERLIN_SIMPLE
+    assert V.MERLIN_SIMPLE == MERLIN_SIMPLE
     out = (ctypes.c_uint8 * 32)()
     lib.h_merlin_simple(out)
     assert bytes(out).hex() == MERLIN_SIMPLE
@@ -309,41 +344,30 @@ def test_host_msm_finish_and_group_normalisation(lib):
 def test_g1_decompress48_matches_the_oracle(lib):
     """g1codec.cuh (the lane function of the compressed commit-key loader) against oracle g1_compress / g1_decompress:
     G1Affine::from_bytes semantics of the 48-byte encoding — both roots, the flag rules, x >= p, x^3 + 4 not a square."""
-    rnd = random.Random(11)
     out = ctypes.create_string_buffer(96)
-    pts = [E.G1_GEN] + [E.g1_mul(E.G1_GEN, rnd.randrange(1, Q)) for _ in range(24)]
-    pts += [(x, (P - y) % P) for x, y in pts[:8]]                      # the other root / sign flag
-    for pt in pts:
-        enc = E.g1_compress(pt)
-        assert lib.h_g1_decompress48(enc, out) == 0
-        assert out.raw == E.g1_to_raw96(pt)
-        assert E.g1_decompress(enc) == pt
+    cases = V.decompress_cases()
     g = E.g1_compress(E.G1_GEN)
-    assert lib.h_g1_decompress48(bytes([g[0] & 0x7F]) + g[1:], out) == 1          # compression flag missing
-    assert lib.h_g1_decompress48(bytes([0xC0]) + bytes(47), out) == 2              # the identity
-    assert lib.h_g1_decompress48(bytes([0xE0]) + bytes(47), out) == 1              # identity with the sort flag
-    assert lib.h_g1_decompress48(bytes([0xC0]) + bytes(46) + b"\x01", out) == 1    # identity with x != 0
-    assert lib.h_g1_decompress48(bytes([0x80 | (P >> 376)]) + (P & ((1 << 376) - 1)).to_bytes(47, "big"), out) == 1   # x = p
-    bad = 0
-    for x in range(1, 40):                                                          # x^3 + 4 a non-residue for about half of them
-        enc = bytes([0x80]) + x.to_bytes(47, "big")
-        rc = lib.h_g1_decompress48(enc, out)
-        on_curve = pow((x ** 3 + 4) % P, (P - 1) // 2, P) == 1
-        assert rc == (0 if on_curve else 1)
-        bad += not on_curve
-        if on_curve:                                                                # smaller root requested (flag clear)
-            y = pow((x ** 3 + 4) % P, (P + 1) // 4, P)
-            y = min(y, P - y)
-            assert out.raw == E.g1_to_raw96((x, y))
-    assert bad > 5
+    codes = {enc: rc for enc, rc, _ in cases}
+    assert codes[bytes([g[0] & 0x7F]) + g[1:]] == 1          # compression flag missing
+    assert codes[bytes([0xC0]) + bytes(47)] == 2              # the identity
+    assert codes[bytes([0xE0]) + bytes(47)] == 1              # identity with the sort flag
+    assert codes[bytes([0xC0]) + bytes(46) + b"\x01"] == 1    # identity with x != 0
+    assert codes[bytes([0x80 | (P >> 376)]) + (P & ((1 << 376) - 1)).to_bytes(47, "big")] == 1   # x = p
+    assert sum(1 for enc, rc, _ in cases if rc == 0 and enc[0] & 0x20) >= 8          # both roots
+    assert sum(1 for enc, rc, _ in cases if rc == 1 and enc[:40] == bytes([0x80]) + bytes(39)) > 5   # small x off the curve
+    for enc, rc, pt in cases:
+        assert lib.h_g1_decompress48(enc, out) == rc, enc.hex()
+        if rc == 0:
+            assert out.raw == E.g1_to_raw96(pt)
+            assert E.g1_decompress(enc) == pt
 
 
 def test_safegcd_inverse_matches_the_oracle(lib):
     """fp_safegcd.cuh (Bernstein-Yang division steps, 13 signed 30-bit limbs) through the Fp28 interface: x -> x^-1 for edge
     values and random ones, lazily reduced inputs included; 0 -> 0."""
-    rnd = random.Random(381)
     out = (ctypes.c_uint32 * 12)()
-    vals = edge_values(P, rnd, 150) + [(1 << k) % P for k in (1, 29, 30, 31, 59, 60, 380)] + [P - (1 << 30), (P + 1) // 2, 3, P - 3]
+    vals = V.safegcd_fp_values()
+    assert {0, P - (1 << 30), (P + 1) // 2} | {(1 << k) % P for k in (1, 29, 30, 31, 59, 60, 380)} <= set(vals)
     for a in vals:
         lib.h_fp_inv_gcd(fp_limbs(a), out)
         assert fp_val(out) == (pow(a, -1, P) if a else 0), hex(a)
@@ -353,10 +377,12 @@ def test_safegcd_inverse_matches_the_oracle(lib):
 
 def test_safegcd_inverse_in_fr_matches_the_oracle(lib):
     """the 9-limb instance (batch_inverse_kernel's workgroup inversion): x -> x^-1 mod q in twiddle form"""
-    rnd = random.Random(255)
     out = (ctypes.c_uint32 * 8)()
-    for a in edge_values(Q, rnd, 200) + [Q - (1 << 30), (Q + 1) // 2, 7, pow(7, (Q - 1) >> 32, Q)]:
+    for a in V.safegcd_fr_values():
         lib.h_fr_inv_gcd(fr_limbs(a), out)
+        assert fr_val(out) == (pow(a, -1, Q) if a else 0), hex(a)
+    for a in V.safegcd_cg_values():          # the composer's out-of-line call of the same inversion
+        lib.h_cg_inv(fr_limbs(a), out)
         assert fr_val(out) == (pow(a, -1, Q) if a else 0), hex(a)
 
 
@@ -452,9 +478,8 @@ def test_host_fp_inverse_safegcd_equals_fermat_and_the_oracle(lib):
 def test_host_fr_inverse_safegcd_montgomery_form(lib):
     """fp_safegcd.cuh fr_inv_gcd: x R -> x^-1 R on the 8 x 32-bit Fr — the per-proof host inversions of prover.hip
     (1 / (z (z - 1)), the public-input denominators); 0 -> 0 like Fr::inv."""
-    r = random.Random(92)
     out = (ctypes.c_uint32 * 8)()
-    for v in [0, 1, 2, Q - 1, Q - 2, (Q - 1) // 2, 1 << 254] + [r.randrange(Q) for _ in range(300)]:
+    for v in V.safegcd_fr_mont_values():
         lib.h_fr_inv_gcd_mont(fr_limbs(v), out)
         assert fr_val(out) == (pow(v, -1, Q) if v else 0), v
 
@@ -570,32 +595,26 @@ def test_first_two_entries_of_a_lane_through_the_affine_pair_formula(lib):
     """curve28.cuh add_affine_pair (msm.hip ACC_FIRST_PAIR): the sum of two affine table points with 4 products + 2 squarings,
     every sign combination (signs applied lazily as 4p - y), followed by a chain of mixed additions (the output bounds must
     be add_affine's input bounds); equal and opposite first points fall back to the general path."""
-    rnd = random.Random(6201)
-    G = E.G1_GEN
-    pts = [E.g1_mul(G, rnd.randrange(1, Q)) for _ in range(24)]
+    cases = V.g1r_pair_cases()
     out = (ctypes.c_uint8 * 96)()
     used = ctypes.c_int(0)
-    for trial in range(40):
-        n = [2, 2, 2, 2, 3, 8, 24][trial % 7]
-        sel = [pts[rnd.randrange(len(pts))] for _ in range(n)]
-        if trial % 7 == 0:
-            sel[1] = pts[(pts.index(sel[0]) + 1) % len(pts)]
-        neg = bytes([(trial >> 0) & 1, (trial >> 1) & 1] + [rnd.randrange(2) for _ in range(n - 2)])
+    assert len(cases) == 42 and {tuple(neg[:2]) for _, neg in cases[:40]} == {(0, 0), (0, 1), (1, 0), (1, 1)}
+    for trial, (sel, neg) in enumerate(cases[:40]):
         raw = b"".join(E.g1_to_raw96(p) for p in sel)
-        ok = lib.h_g1r_accumulate_pair_first(raw, neg, n, out, ctypes.byref(used))
-        exp = None
-        for p, s in zip(sel, neg):
-            exp = E.g1_add(exp, (p[0], (E.P - p[1]) % E.P) if s else p)
+        ok = lib.h_g1r_accumulate_pair_first(raw, bytes(neg), len(sel), out, ctypes.byref(used))
+        exp = V.g1r_sum(sel, neg)
         assert (ok == 1) == (exp is not None), trial
         if exp is not None:
             assert E.g1_from_raw96(bytes(out)) == exp, trial
         assert used.value == (1 if sel[0][0] != sel[1][0] else 0), trial
     # equal first points (doubling) and opposite ones (cancellation) never take the pair formula
-    rep = E.g1_to_raw96(pts[0]) * 5
+    (rep5, neg_a), (rep5b, neg_b) = cases[40:]
+    assert rep5 == rep5b == [rep5[0]] * 5 and neg_a == [0] * 5 and neg_b == [0, 1, 0, 0, 0]
+    rep = E.g1_to_raw96(rep5[0]) * 5
     assert lib.h_g1r_accumulate_pair_first(rep, bytes(5), 5, out, ctypes.byref(used)) == 1 and used.value == 0
-    assert E.g1_from_raw96(bytes(out)) == E.g1_mul(pts[0], 5)
+    assert E.g1_from_raw96(bytes(out)) == E.g1_mul(rep5[0], 5)
     assert lib.h_g1r_accumulate_pair_first(rep, bytes([0, 1, 0, 0, 0]), 5, out, ctypes.byref(used)) == 1 and used.value == 0
-    assert E.g1_from_raw96(bytes(out)) == E.g1_mul(pts[0], 3)
+    assert E.g1_from_raw96(bytes(out)) == E.g1_mul(rep5[0], 3)
 
 
 def test_scalar_multiplication_through_the_endomorphism(lib):
@@ -603,23 +622,22 @@ def test_scalar_multiplication_through_the_endomorphism(lib):
     k = k1 + k2 LAMBDA with both halves below 2^128 and r = LAMBDA^2 + LAMBDA + 1; phi(x, y) = (BETA x, y) = [LAMBDA](x, y);
     [k] P equals the oracle's double-and-add for random, small, extreme and half-empty scalars, also for an operand that
     comes out of additions (the butterflies' bounds) and for the identity's neighbours (k = 0, 1, r - 1)."""
-    lam = 0xac45a4010001a40200000000ffffffff
+    lam = V.GLV_LAMBDA
+    assert lam == 0xac45a4010001a40200000000ffffffff
     assert lam * lam + lam + 1 == Q
     beta = 0x1a0111ea397fe699ec02408663d4de85aa0d857d89759ad4897d29650fb85f9b409427eb4f49fffd8bfd00000000aaac
     G = E.G1_GEN
     assert pow(beta, 3, E.P) == 1 and (beta * G[0] % E.P, G[1]) == E.g1_mul(G, lam)
-    rnd = random.Random(6202)
-    ks = [0, 1, 2, lam - 1, lam, lam + 1, 2 * lam, lam * lam, Q - 1, Q - lam, (1 << 128) - 1, 1 << 128, (1 << 254) + 1]
-    ks += [rnd.randrange(Q) for _ in range(40)] + [rnd.randrange(1 << 64) for _ in range(4)] + [rnd.randrange(1 << 64) * lam % Q for _ in range(4)]
+    cases = V.glv_cases()
+    assert {0, 1, 2, lam - 1, lam, lam + 1, 2 * lam, lam * lam, Q - 1, Q - lam, (1 << 128) - 1, 1 << 128, (1 << 254) + 1} <= {k for k, _, _ in cases}
+    assert len(cases) == 61
     out4 = (ctypes.c_uint64 * 4)()
     out = (ctypes.c_uint8 * 96)()
-    for i, k in enumerate(ks):
+    for k, base, pre in cases:
         limbs = (ctypes.c_uint32 * 8)(*[(k >> (32 * j)) & 0xffffffff for j in range(8)])
         lib.h_glv_split(limbs, out4)
         k1, k2 = out4[0] | out4[1] << 64, out4[2] | out4[3] << 64
         assert (k1, k2) == (k % lam, k // lam), hex(k)
-        base = E.g1_mul(G, rnd.randrange(1, Q))
-        pre = i % 3
         ok = lib.h_g1r_mul_glv(E.g1_to_raw96(base), limbs, pre, out)
         exp = E.g1_mul(base, k * (1 << pre) % Q) if k else None
         assert (ok == 1) == (exp is not None), hex(k)
