@@ -451,8 +451,13 @@ def linearization_compute(prover, ch, z_ch, z_poly, ev, domain, t_polys, pub_inp
           * (ev["c"] + K2 * bz + gamma) % Q * (ev["d"] + K3 * bz + gamma) % Q * alpha) % Q
     b_ = ((ev["a"] + beta * ev["s_sigma_1"] + gamma) * (ev["b"] + beta * ev["s_sigma_2"] + gamma) % Q
           * (ev["c"] + beta * ev["s_sigma_3"] + gamma) % Q * (beta * ev["z"] % Q) * alpha) % Q
-    dom_z = EvaluationDomain(len(z_poly) - 1 - 2)                  # :162 new(z_poly.degree() - 2)
-    l1 = dom_z.first_lagrange_at(z_ch)
+    # :162 takes EvaluationDomain::new(z_poly.degree() - 2): the circuit's domain whenever the top blinder of z is not
+    # zero (degree n + 2), which is every proof the reference draws blinders for.  With zero blinders the degree drops and
+    # that L1 belongs to a smaller domain (or the subtraction underflows): a proof the reference's own verifier refuses.
+    # The verifier, the C restatement and the library take L1 of the circuit's domain; so does this
+    # (tests/test_degenerate_host.py proves the empty Composer with zero blinders).
+    assert len(z_poly) < domain.size + 3 or EvaluationDomain(len(z_poly) - 3).size == domain.size
+    l1 = domain.first_lagrange_at(z_ch)
     f2 = poly_add(poly_add(poly_scale(z_poly, a_), poly_scale(p["s_sigma_4"], (-b_) % Q)),
                   poly_scale(z_poly, l1 * alpha % Q * alpha % Q))
     n = domain.size

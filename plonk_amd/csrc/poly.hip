@@ -53,11 +53,15 @@ __global__ void fill_zero_kernel(Fr* p, uint64_t n) {
 }
 
 // blind_poly_with_blinders (prover.rs:139-152): c[i] -= b_i ; c[n + i] = b_i
+// A domain smaller than the number of blinders (n = 2, the three blinders of z) makes X^n * b_(i-n) and -X^i * b_i meet in
+// one coefficient: lane i owns coefficient i and writes b_(i-n) - b_i there; coefficient n + i is written by its own lane
+// when it has one.
 __global__ void blind_kernel(Fr* coeffs, uint64_t n, BlindArgs a) {
   const int i = threadIdx.x;
   if (i < a.count) {
-    stf(coeffs + i, ldf(coeffs + i) - a.b[i]);
-    stf(coeffs + n + i, a.b[i]);
+    const Fr low = (uint64_t)i >= n ? a.b[i - n] : ldf(coeffs + i);
+    stf(coeffs + i, low - a.b[i]);
+    if (n + i >= (uint64_t)a.count) stf(coeffs + n + i, a.b[i]);
   }
 }
 

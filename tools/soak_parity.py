@@ -4,7 +4,12 @@ C restatement of the reference's prove() — half of them built by plonk_compile
 witness table, half from coefficient forms and wire columns; every pair of 1008-byte proofs must be identical and every corrupted
 witness must be CircuitUnsatisfied on both sides.
 
-    python tools/soak_parity.py [N] [seed]
+    python tools/soak_parity.py [N] [seed] [zero-blinder share]
+
+The third argument (default 0) is the share of circuits proved with fourteen ZERO blinders — polynomials of degree below n,
+quotient parts without a blinding term, zero scalars on the blinding points of the Lagrange-form commitments: the edge
+tests/test_gpu_degenerate.py pins on tiny circuits, here on the soak's sizes.  It is drawn from a generator of its own, so a
+seed gives the same circuits with and without it.
 """
 import os
 import random
@@ -20,7 +25,10 @@ from tests import circuits as C  # noqa: E402
 
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 50
 seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 1
+zero_share = float(sys.argv[3]) if len(sys.argv) > 3 else 0.0
 rnd = random.Random(seed0)
+edge_rnd = random.Random(seed0 * 2654435761 + 1)
+zero_blinded = 0
 srs_cache = {}
 ok = unsat = 0
 t0 = time.time()
@@ -46,6 +54,9 @@ for it in range(N):
     assert gp.vk_commitments() == cp.vk(), ("vk", it)
     assert gp.describe()["quotient_domain"] == (8 if domain8 else 4), ("quotient domain not honoured", it)
     bl = C.blinders(rnd.getrandbits(32))
+    if edge_rnd.random() < zero_share:
+        bl = bytes(14 * 32)
+        zero_blinded += 1
     wires = list(case["wires"])
     corrupt = rnd.random() < 0.15
     values = cols["values"] if from_circuit else None
@@ -84,4 +95,5 @@ for it in range(N):
     gp.close()
     cp.close()
     ctx.close()
-print(f"soak_parity: {ok} identical proofs, {unsat} unsatisfied witnesses rejected by both, {N} circuits, {time.time() - t0:.0f} s, seed {seed0}")
+print(f"soak_parity: {ok} identical proofs, {unsat} unsatisfied witnesses rejected by both, {N} circuits, {time.time() - t0:.0f} s, seed {seed0}"
+      + (f", {zero_blinded} with zero blinders" if zero_share else ""))
