@@ -676,6 +676,46 @@ int plonk_kzg_batch_check(plonk_kzg_key* key, const uint64_t* points /* count x 
                           plonk_verify_info* info);
 int plonk_srs_check(plonk_kzg_key* key, const uint8_t seed32[32]);
 
+/* ---- variable-base MSM over caller-supplied points ------------------------------------------------
+ * sum_i scalars[i] * P_i for points the CALLER brings — the reference's msm_variable_base (the primitive under Proof::verify
+ * and OpeningKey::batch_check) — where plonk_msm / _batch / _dev run over the loaded commit key and its precomputed tables.
+ * No key is needed and none is touched.  A bucket method (Pippenger) on the device: every scalar is split through the
+ * curve's endomorphism into two 128-bit halves, each half into signed digits of c bits, the (point, digit) entries are
+ * grouped by (window, bucket) with a counting sort, accumulated by slices, summed per bucket, per window and over the
+ * windows.
+ *   points   m x 96 bytes x || y (the layout plonk_srs_load takes); 96 zero bytes are the identity ((0, 0) is not on the
+ *            curve).  PLONK_POINTS_COMPRESSED: m x 48 bytes, G1Affine::to_bytes, decoded on the device; the compressed
+ *            identity is legal, a point that does not decode is PLONK_ERR_POINT.  PLONK_POINTS_CHECK: every finite point is
+ *            tested for the curve equation and the prime-order subgroup, a failure is PLONK_ERR_POINT and nothing is written
+ *            to the output.  Without it raw points are trusted, as plonk_srs_load trusts its input.
+ *   scalars  m x 4 limbs, Montgomery, as plonk_msm.
+ *   out      97 bytes, as plonk_msm.  m == 0 gives the identity; m > 2^24 is PLONK_ERR_ARG.
+ *   opts     NULL or a zeroed struct with struct_size set = automatic.  PLONK_ERR_ARG for a struct_size below
+ *            sizeof(plonk_msm_points_opts), an unknown flag, window_bits outside 2..16 or slice_entries above 2^20.
+ * plonk_msm_points_dev: points, scalars and the 97 output bytes are device pointers on the context's GPU (4-byte aligned).
+ * Both forms return with the context's main stream synchronised; a context with a communicator runs the call locally.  The
+ * workspace is owned by the context, grows on demand and is freed by plonk_ctx_destroy.
+ * plonk_ctx_last_msm_points: what the last call on the context ran as (PLONK_ERR_STATE before the first): the tests assert it
+ * against the plan computed on the host (plonk_amd/csrc/msm_points_core.hpp), so a switch that is ignored fails a test. */
+enum { PLONK_POINTS_COMPRESSED = 1, PLONK_POINTS_CHECK = 2 };
+typedef struct plonk_msm_points_opts {   /* all 0 = automatic */
+  uint32_t struct_size, flags;
+  uint32_t window_bits;        /* force the digit width c (test hook; 2..16) */
+  uint32_t slice_entries;      /* force the longest run one lane accumulates serially */
+  uint32_t min_bucket_terms;   /* below this many terms use the per-term kernel; 1 forces buckets */
+  uint32_t reserved;
+} plonk_msm_points_opts;
+typedef struct plonk_msm_points_info {   /* what the last call ran as */
+  uint32_t path;               /* 0 per-term, 1 buckets */
+  uint32_t window_bits, windows, slice_entries;
+  uint64_t terms, nonzero_digits, slices, longest_bucket;
+} plonk_msm_points_info;
+int plonk_msm_points(plonk_ctx* ctx, const uint8_t* points, const uint64_t* scalars, uint64_t m,
+                     const plonk_msm_points_opts* opts /* NULL */, uint8_t out_xy_inf[97]);
+int plonk_msm_points_dev(plonk_ctx* ctx, const void* points_dev, const void* scalars_dev, uint64_t m,
+                         const plonk_msm_points_opts* opts, void* out97_dev);
+int plonk_ctx_last_msm_points(plonk_ctx* ctx, plonk_msm_points_info* out);
+
 /* ---- gadget composer: circuits from gadgets, witness generation on the device -------------------
  * What the reference's Composer does for a Circuit (src/composer.rs and src/composer/{bits,range,logic,select,truncate,
  * point,fixed_base}.rs): a plonk_composer RECORDS gadget calls and yields (a) the gate layout plonk_compile takes and
@@ -778,6 +818,8 @@ int plonk_prover_diagnose_inputs(plonk_prover* p, const uint64_t* inputs, uint64
  *   polynomials with its copies, the powers of v and every fold + evaluate launch (in the host form NOT the uploads the
  *   launches wait for, nor the polynomial commitments between them); 13 Ruffini (or the shift at the point 0); 14 the witness
  *   commitment, bit sums copied back included (its MSM kernels also count in slots 1 and 2).
+ *   plonk_msm_points / _dev, bucket path (device events): 15 load + recode (points, scalars, histogram), 22 scan + scatter,
+ *   23 slice accumulation, 30 slice sums to bucket sums, 31 window sums.
  *   Slots 0 .. 31 are valid.
  *
  * Host threads.  A context starts up to 3 helper threads (none when the process may run on fewer than 8 CPUs: sched_getaffinity) with its first

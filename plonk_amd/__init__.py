@@ -69,6 +69,7 @@ EXPORTS = [
     "plonk_composer_create", "plonk_composer_destroy", "plonk_composer_witness", "plonk_composer_gate", "plonk_composer_gadget",
     "plonk_composer_info", "plonk_composer_layout", "plonk_compile_composer",
     "plonk_prover_fill_inputs", "plonk_prover_prove_inputs", "plonk_prover_diagnose_inputs",
+    "plonk_msm_points", "plonk_msm_points_dev", "plonk_ctx_last_msm_points",
 ]
 
 # what bit f of plonk_unsat_row.families / slot f of plonk_unsat_info.family_rows stands for (include/plonk_hip.h); the
@@ -115,6 +116,25 @@ class _MsmPlan(ctypes.Structure):
         d = {k: getattr(self, k) for k, _ in self._fields_}
         d["accumulate_kernel"] = d["accumulate_kernel"].decode()
         return d
+
+
+POINTS_COMPRESSED, POINTS_CHECK = 1, 2
+
+
+class _MsmPointsOpts(ctypes.Structure):
+    """plonk_msm_points_opts (include/plonk_hip.h): zero = automatic; struct_size is filled in by the binding."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("window_bits", ctypes.c_uint32),
+                ("slice_entries", ctypes.c_uint32), ("min_bucket_terms", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+    def __init__(self, **kw):
+        super().__init__(**kw)
+        self.struct_size = ctypes.sizeof(_MsmPointsOpts)
+
+
+class _MsmPointsInfo(ctypes.Structure):
+    _fields_ = [("path", ctypes.c_uint32), ("window_bits", ctypes.c_uint32), ("windows", ctypes.c_uint32),
+                ("slice_entries", ctypes.c_uint32), ("terms", ctypes.c_uint64), ("nonzero_digits", ctypes.c_uint64),
+                ("slices", ctypes.c_uint64), ("longest_bucket", ctypes.c_uint64)]
 
 
 class _ProverInfo(ctypes.Structure):
@@ -370,6 +390,9 @@ def load_library() -> ctypes.CDLL:
     lib.plonk_prover_fill_inputs.argtypes = [vp, vp, u64, vp, vp]
     lib.plonk_prover_prove_inputs.argtypes = [vp, vp, u64, vp, vp, vp]
     lib.plonk_prover_diagnose_inputs.argtypes = [vp, vp, u64, vp, u64, vp]
+    lib.plonk_msm_points.argtypes = [vp, vp, vp, u64, ctypes.POINTER(_MsmPointsOpts), vp]
+    lib.plonk_msm_points_dev.argtypes = [vp, vp, vp, u64, ctypes.POINTER(_MsmPointsOpts), vp]
+    lib.plonk_ctx_last_msm_points.argtypes = [vp, ctypes.POINTER(_MsmPointsInfo)]
     _lib = lib
     return lib
 
@@ -610,6 +633,49 @@ class Context:
     def msm(self, scalars: Sequence[int]):
         """msm_variable_base(&powers_of_g, scalars) -> affine point or None (identity)."""
         return g1_from_raw97(self.msm_bytes(fr_to_bytes_mont(scalars), len(scalars)))
+
+    @staticmethod
+    def _msm_points_opts(compressed, check, window_bits, slice_entries, min_bucket_terms) -> "_MsmPointsOpts":
+        return _MsmPointsOpts(flags=(POINTS_COMPRESSED if compressed else 0) | (POINTS_CHECK if check else 0),
+                              window_bits=window_bits, slice_entries=slice_entries, min_bucket_terms=min_bucket_terms)
+
+    def msm_points_bytes(self, points: bytes, scalars_mont: bytes, m: int, compressed: bool = False, check: bool = False,
+                         window_bits: int = 0, slice_entries: int = 0, min_bucket_terms: int = 0) -> bytes:
+        """plonk_msm_points on marshalled input: m x 96 (or m x 48 compressed) point bytes, m x 32 Montgomery scalar bytes ->
+        the 97 result bytes"""
+        opts = self._msm_points_opts(compressed, check, window_bits, slice_entries, min_bucket_terms)
+        out = ctypes.create_string_buffer(97)
+        self._check(self.lib.plonk_msm_points(self.handle, points, scalars_mont, m, ctypes.byref(opts), out))
+        return out.raw
+
+    def msm_points(self, points, scalars: Sequence[int], compressed: bool = False, check: bool = False, window_bits: int = 0,
+                   slice_entries: int = 0, min_bucket_terms: int = 0):
+        """msm_variable_base(points, scalars) over the CALLER's points -> affine point or None (identity), as msm().  points:
+        affine pairs (None = the identity), or the marshalled bytes (m x 96 raw, m x 48 with compressed=True).  check=True
+        tests every finite point for the curve and the subgroup (PointMalformed).  window_bits / slice_entries /
+        min_bucket_terms force the plan (0 = automatic); last_msm_points() tells what ran."""
+        m = len(scalars)
+        if not isinstance(points, (bytes, bytearray)):
+            assert len(points) == m
+            if compressed:
+                points = b"".join(g1_compress(p) for p in points)
+            else:
+                points = b"".join(bytes(96) if p is None else g1_to_raw96(p) for p in points)
+        assert len(points) == (48 if compressed else 96) * m
+        return g1_from_raw97(self.msm_points_bytes(bytes(points), fr_to_bytes_mont(scalars), m, compressed, check, window_bits,
+                                                   slice_entries, min_bucket_terms))
+
+    def msm_points_dev(self, points: int, scalars: int, m: int, out97: int, compressed: bool = False, check: bool = False,
+                       window_bits: int = 0, slice_entries: int = 0, min_bucket_terms: int = 0):
+        """plonk_msm_points_dev: device pointers to the points, the Montgomery scalars and the 97 output bytes"""
+        opts = self._msm_points_opts(compressed, check, window_bits, slice_entries, min_bucket_terms)
+        self._check(self.lib.plonk_msm_points_dev(self.handle, points, scalars, m, ctypes.byref(opts), out97))
+
+    def last_msm_points(self) -> dict:
+        """what the last msm_points / msm_points_dev call on this context ran as (plonk_msm_points_info)"""
+        info = _MsmPointsInfo()
+        self._check(self.lib.plonk_ctx_last_msm_points(self.handle, ctypes.byref(info)))
+        return {k: getattr(info, k) for k, _ in info._fields_}
 
     def commit(self, coeffs: Sequence[int]):
         """CommitKey::commit (key.rs:376-388): trailing zeros trimmed like

@@ -435,6 +435,7 @@ void plonk_ctx_destroy(plonk_ctx* ctx) {
   (void)hipStreamSynchronize(c.stream);
   verify_ws_release(&c);
   kzg_ws_release(&c);
+  msm_points_ws_release(&c);
   for (auto& kv : c.ntt_tables) {
     NttTables* t = kv.second;
     (void)hipFree(t->tw_lo); (void)hipFree(t->tw_hi); (void)hipFree(t->tw_lo_scaled);

@@ -235,6 +235,9 @@ struct Ctx {
   void* finish_pool = nullptr;     // FinishPool* (finish_pool.hpp), created by the first commitment group of a prover (prover.hip), freed by finish_pool_release
   void* verify_ws = nullptr;       // MixedWork* (verify.hip): plonk_verify_mixed's grow-only device workspace, freed by verify_ws_release
   void* kzg_ws = nullptr;          // KzgWork* (kzg.hip): the grow-only workspace of the KZG10 opening calls, freed by kzg_ws_release
+  void* points_ws = nullptr;       // MpWork* (msm_points.hip): the grow-only workspace of plonk_msm_points, freed by msm_points_ws_release
+  plonk_msm_points_info last_points = {};   // of the last plonk_msm_points / _dev call (plonk_ctx_last_msm_points)
+  bool last_points_valid = false;
   // instrumentation: hipEvent pairs around the dominant kernels
   bool profile = false;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -349,6 +352,23 @@ G1Aff64 xyzz_to_aff(const H1& p);
 // The caller has reserved the MSM scratch (msm_reserve) for the largest m; returns with the stream synchronised.
 int msm_group_sums(Ctx* c, const Fr* const* scalars_dev, const uint64_t* m, int cnt, G1* sums);
 void kzg_ws_release(Ctx* c);                          // kzg.hip: frees the opening workspace of the context
+// msm_points.hip: sum_i s_i P_i over points that are not the commit key, by the bucket method (or, below
+// opts.min_bucket_terms terms, by verify.hip's per-term kernel).  The terms come in one of two layouts:
+//   caller layout   points (m x 96 raw bytes, or m x 48 compressed) + Montgomery scalars: plonk_msm_points / _dev
+//   term layout     what msm_run takes — canonical scalars (8 words each), point ids into a decoded table, its kind array —
+//                   so that the verifier and the KZG batch check can move over with a call-site change (not wired yet)
+// Everything is device memory.  *sum = the XYZZ sum (canonical coordinates) on the host; the stream is synchronised.
+struct MpInput {
+  const uint8_t* points = nullptr;     // caller layout
+  const Fr* scalars = nullptr;
+  uint32_t flags = 0;                  // PLONK_POINTS_*
+  const uint32_t* sc = nullptr;        // term layout (sc != nullptr selects it)
+  const uint32_t* ids = nullptr;
+  const G1Affine* pts = nullptr;
+  const int32_t* kind = nullptr;
+};
+int msm_points_run(Ctx* c, const MpInput& in, uint64_t m, const plonk_msm_points_opts* opts, G1* sum);
+void msm_points_ws_release(Ctx* c);
 int msm_sort_reserve_fixed(Ctx* c);
 
 }  // namespace plonk
