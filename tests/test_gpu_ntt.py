@@ -216,7 +216,8 @@ def test_empty_input_is_the_zero_polynomial(ctx, L):
 
 def test_two_level_twiddle_fallback_matches_the_oracle():
     """PLONK_NTT_DIRECT=0: the inter-pass twiddles as TWLO x TWHI products (the path taken above 2^25 or when memory is
-    short) — the same transforms, in a child process because the switch is read once."""
+    short) — the same transforms, in a child process: the switch is read when a context is created and the module's context
+    exists.  tests/test_gpu_ntt_plans.py runs the other plans and the in_len edges on a fresh context created under it."""
     import os
     import subprocess
     import sys
@@ -232,9 +233,10 @@ def test_two_level_twiddle_fallback_matches_the_oracle():
 def test_elements_per_lane_variants_match_the_oracle(elog):
     """PLONK_NTT_ELOG=3: the pass kernels with 8 elements per lane (radix-8 register rounds over 2048-element tiles, two waves
     per SIMD).  Every other test of this file runs the default, 4 elements per lane (radix-4 rounds over 1024-element tiles,
-    four waves); the 8-element kernels otherwise only run inside provers of more than 2^18 gates (side-stream transforms).
-    Same transforms, in a child process because the switch is read once.  ("2" forces the default explicitly: add it to the
-    list when the default changes.)"""
+    four waves); besides this, tests/test_gpu_ntt_plans.py runs every other plan and the in_len edges on a context created with
+    GpuConfig(ntt_elements_log2=3), and provers of more than 2^18 gates use the 8-element kernels for side-stream transforms.
+    Same transforms, in a child process: the variable is read when a context is created and the module's context exists.
+    ("2" forces the default explicitly: add it to the list when the default changes.)"""
     import os
     import subprocess
     import sys
