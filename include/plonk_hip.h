@@ -84,15 +84,20 @@ const char* plonk_last_error(void);
  *   THIS context already holds — not the memory that happens to be free — so two contexts given the same budget choose the
  *   same layouts whatever their neighbours do (until round 4: "half of what hipMemGetInfo reports free right now").
  *   Keys of at most 2^18 + 64 points always take window rows (measured faster), table_mode forces a layout.
+ *   The four layouts, bytes per point and point additions per scalar (uniform scalars, 2^19 buckets where the layout
+ *   allows them): PLONK_TABLE_BITPOS 256 rows, 32 KiB, 12.1; PLONK_TABLE_HALFPOS 128 rows, 16 KiB, 12.8;
+ *   PLONK_TABLE_QUARTERPOS 64 rows (a row per fourth bit position), 8 KiB, 13.0 (16.0 over the 2^15 buckets of MSMs of at
+ *   most 2^18 + 64 terms); PLONK_TABLE_WINDOW 16 rows, 2 KiB, 16.  The automatic rule never takes the 64-row layout: it is
+ *   for a caller who forces it (several provers, or a second large one, on one device).
  * plonk_ctx_get_config returns the EFFECTIVE values (defaults and overrides resolved); plonk_ctx_set_config replaces
  *   them for the key loads, provers and MSMs that follow (e.g. a key that is loaded only to derive another one from it:
  *   table_mode = PLONK_TABLE_WINDOW for that load).  Existing tables and provers keep what they were built with. */
-enum { PLONK_TABLE_AUTO = 0, PLONK_TABLE_WINDOW = 16, PLONK_TABLE_HALFPOS = 128, PLONK_TABLE_BITPOS = 256 };
+enum { PLONK_TABLE_AUTO = 0, PLONK_TABLE_WINDOW = 16, PLONK_TABLE_QUARTERPOS = 64, PLONK_TABLE_HALFPOS = 128, PLONK_TABLE_BITPOS = 256 };
 typedef struct plonk_gpu_config {
   uint32_t struct_size;          /* sizeof(plonk_gpu_config) of the caller (shorter = older header: missing fields default) */
   uint32_t reserved;             /* 0 */
   uint64_t table_budget_bytes;   /* 0 = 80 % of the device's total memory */
-  int32_t table_mode;            /* PLONK_TABLE_AUTO | _WINDOW | _HALFPOS | _BITPOS */
+  int32_t table_mode;            /* PLONK_TABLE_AUTO | _WINDOW | _QUARTERPOS | _HALFPOS | _BITPOS; a forced layout holds at any key size */
   int32_t msm_bucket_bits;       /* 0 = by the number of terms (2^19 buckets above 2^18 terms over bit-position rows), 15, 19 */
   int32_t quotient_domain;       /* 0 = 4: quotient on the 4n coset + de-aliasing; 8: the reference's 8n evaluation */
   int32_t wire_commit;           /* 0 = from the wire VALUES over the Lagrange-basis key; 1 = coefficient form like the reference */
@@ -118,9 +123,9 @@ int plonk_ctx_set_config(plonk_ctx* ctx, const plonk_gpu_config* config);
  * ignored fails a test. */
 enum { PLONK_PLAN_TAIL_SERIAL = 1, PLONK_PLAN_BUCKET_SUM_LANE = 2, PLONK_PLAN_ACCUMULATE_LDS = 4, PLONK_PLAN_SORT13 = 8 };
 typedef struct plonk_msm_plan {
-  uint32_t table_rows;           /* 16 window rows / 128 / 256 bit-position rows of the key */
+  uint32_t table_rows;           /* 16 window rows / 64 / 128 / 256 bit-position rows of the key */
   uint32_t bucket_bits;          /* 15 or 19 (17: opt-in A/B build) */
-  uint32_t digit_width;          /* bits of a signed digit: 16 (windows), or bucket_bits + 2 (NAF over bit positions; + 1 for half density) */
+  uint32_t digit_width;          /* bits of a signed digit: 16 (windows), or bucket_bits + 2 (NAF over bit positions; + 1 for half and quarter density: 16 / 20) */
   uint32_t slice_entries;        /* entries a lane accumulates serially */
   uint32_t ordered_lanes;        /* 1: msm_accumulate_ordered_kernel (lanes in order of slice length) */
   uint32_t wide_words;           /* 1: 64-bit sort words (rows x points above 2^27) */
@@ -185,7 +190,8 @@ int plonk_dev_d2h(plonk_ctx* ctx, void* dst_host, const void* src_dev, uint64_t 
 int plonk_dev_sync(plonk_ctx* ctx);
 void* plonk_ctx_stream(plonk_ctx* ctx); /* the hipStream_t of the context's main stream (prove() also uses a private side stream) */
 /* Rows of the commit-key tables the context holds: 256 = one row per bit position (2^r * P_i: NAF digits over 2^19 buckets,
- * ~12.1 additions per scalar), 128 = a row for every second position (12.8), 16 = window rows (2^(16 w) * P_i, 16 additions
+ * ~12.1 additions per scalar), 128 = a row for every second position (12.8), 64 = a row for every fourth position (13.0; only
+ * when table_mode forces it), 16 = window rows (2^(16 w) * P_i, 16 additions
  * per scalar), 0 = no key loaded.  Chosen from the context's table budget (plonk_gpu_config above) for keys of more than
  * 2^18 + 64 points; same results whichever; plonk_gpu_config.table_mode / .msm_bucket_bits force a layout / bucket count. */
 int plonk_ctx_table_rows(plonk_ctx* ctx);
@@ -266,7 +272,7 @@ typedef struct plonk_prover_info {
   uint64_t size;                 /* domain size n */
   uint32_t quotient_domain;      /* 4: quotient interpolated on the 4n coset and de-aliased; 8: the reference's 8n evaluation */
   uint32_t wire_commit_values;   /* 1: wire commitments from the wire VALUES over a Lagrange-basis key; 0: coefficient form */
-  uint32_t lagrange_table_rows;  /* rows of that key's tables (16 / 128 / 256), 0 without one */
+  uint32_t lagrange_table_rows;  /* rows of that key's tables (16 / 64 / 128 / 256), 0 without one */
   uint32_t shard_world, shard_rank;
   uint32_t sharded_quotient;     /* 1: quotient by residue class, rounds 4-5 by coefficient range; 0: only the MSMs are sharded */
   uint32_t quotient_classes;     /* Q: 4, or 8 for eight ranks (0 when the quotient is not sharded) */

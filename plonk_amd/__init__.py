@@ -88,6 +88,7 @@ POLY_ORDER = ["q_m", "q_l", "q_r", "q_o", "q_f", "q_c", "q_arith", "q_range", "q
 
 
 TABLE_AUTO, TABLE_WINDOW, TABLE_HALFPOS, TABLE_BITPOS = 0, 16, 128, 256
+TABLE_QUARTERPOS = 64
 PLAN_TAIL_SERIAL, PLAN_BUCKET_SUM_LANE, PLAN_ACCUMULATE_LDS, PLAN_SORT13 = 1, 2, 4, 8
 
 
@@ -776,7 +777,7 @@ class Context:
         return a.value, b.value
 
     def table_rows(self) -> int:
-        """256: one table row per bit position (width-17 NAF digits), 16: window rows, 0: no key"""
+        """256: one table row per bit position (width-17 NAF digits), 128 / 64: a row for every second / fourth position, 16: window rows, 0: no key"""
         return int(self.lib.plonk_ctx_table_rows(self.handle))
 
     def ntt_dev(self, src: int, dst: int, tmp: int, log_n: int, inverse=False, coset=False, in_len=None):

@@ -193,7 +193,7 @@ void config_resolve(const plonk_gpu_config* user, int device, Config* out) {
   g.comm_timeout_ms = u.comm_timeout_ms > 0 ? u.comm_timeout_ms : 120000;
   g.side_cus = u.side_stream_cus;
   // ---- environment overrides
-  switch (env_chr("PLONK_MSM_TABLE")) { case 'w': g.table_mode = MSM_ROWS_WINDOW; break; case 'h': g.table_mode = MSM_ROWS_HALFPOS; break; case 'b': g.table_mode = MSM_ROWS_BITPOS; break; default: break; }
+  switch (env_chr("PLONK_MSM_TABLE")) { case 'w': g.table_mode = MSM_ROWS_WINDOW; break; case 'h': g.table_mode = MSM_ROWS_HALFPOS; break; case 'q': g.table_mode = MSM_ROWS_QUARTERPOS; break; case 'b': g.table_mode = MSM_ROWS_BITPOS; break; default: break; }
   if (const int mb = env_int("PLONK_TABLE_BUDGET_MB", 0); mb > 0) g.table_budget = (uint64_t)mb << 20;
   if (const int b = env_int("PLONK_MSM_BUCKETS", 0); b) g.bucket_bits = b;
   if (env_chr("PLONK_QUOTIENT_DOMAIN") == '8') g.quotient_domain = 8;
@@ -228,7 +228,7 @@ void config_resolve(const plonk_gpu_config* user, int device, Config* out) {
   if (env_chr("PLONK_WIRE_BY_COLUMN") == '2') g.wire_by_column = 2;
   if (getenv("PLONK_HOST_THREADS")) g.host_threads = env_int("PLONK_HOST_THREADS", -1);
   // ---- resolution
-  if (g.table_mode != (int)MSM_ROWS_WINDOW && g.table_mode != (int)MSM_ROWS_HALFPOS && g.table_mode != (int)MSM_ROWS_BITPOS) g.table_mode = 0;
+  if (g.table_mode != (int)MSM_ROWS_WINDOW && g.table_mode != (int)MSM_ROWS_QUARTERPOS && g.table_mode != (int)MSM_ROWS_HALFPOS && g.table_mode != (int)MSM_ROWS_BITPOS) g.table_mode = 0;
   if (g.ntt_elog != 2 && g.ntt_elog != 3) g.ntt_elog = 0;
   if (g.side_cus < 0) g.side_cus = 0;
   if (g.host_threads < 0) {   // the CPUs this process may run on (taskset / cpuset), not the machine's: helper threads spin
@@ -252,7 +252,7 @@ static int config_check(const plonk_gpu_config* u, const char* api_fn) {
   plonk_gpu_config c{};
   memcpy(&c, u, u->struct_size < sizeof(c) ? u->struct_size : sizeof(c));
   auto bad = [&](const char* what) { set_last_error(api_fn, what, __FILE__, __LINE__); return PLONK_ERR_ARG; };
-  if (c.table_mode != PLONK_TABLE_AUTO && c.table_mode != PLONK_TABLE_WINDOW && c.table_mode != PLONK_TABLE_HALFPOS && c.table_mode != PLONK_TABLE_BITPOS) return bad("plonk_gpu_config.table_mode");
+  if (c.table_mode != PLONK_TABLE_AUTO && c.table_mode != PLONK_TABLE_WINDOW && c.table_mode != PLONK_TABLE_QUARTERPOS && c.table_mode != PLONK_TABLE_HALFPOS && c.table_mode != PLONK_TABLE_BITPOS) return bad("plonk_gpu_config.table_mode");
   if (c.msm_bucket_bits != 0 && c.msm_bucket_bits != 15 && c.msm_bucket_bits != 17 && c.msm_bucket_bits != 19) return bad("plonk_gpu_config.msm_bucket_bits");
   if (c.quotient_domain != 0 && c.quotient_domain != 4 && c.quotient_domain != 8) return bad("plonk_gpu_config.quotient_domain");
   if (c.wire_commit != 0 && c.wire_commit != 1) return bad("plonk_gpu_config.wire_commit");
@@ -402,7 +402,7 @@ int plonk_ctx_describe_msm(plonk_ctx* ctx, uint64_t m, int count, int bit_sum_ta
   std::lock_guard<std::mutex> lk(ctx->c.mu);
   Ctx& c = ctx->c;
   if (table_rows == 0) { table_rows = c.srs_rows; table_points = c.srs_n; if (!c.srs_table) return PLONK_ERR_NO_SRS; }
-  if (table_rows != MSM_ROWS_WINDOW && table_rows != MSM_ROWS_HALFPOS && table_rows != MSM_ROWS_BITPOS) return PLONK_ERR_ARG;
+  if (table_rows != MSM_ROWS_WINDOW && table_rows != MSM_ROWS_QUARTERPOS && table_rows != MSM_ROWS_HALFPOS && table_rows != MSM_ROWS_BITPOS) return PLONK_ERR_ARG;
   plonk_msm_plan_internal p;
   msm_plan(&c, table_rows, table_points, m, count, bit_sum_tail != 0, &p);
   plan_out(p, out);

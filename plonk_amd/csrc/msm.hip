@@ -120,7 +120,7 @@ __device__ __forceinline__ G1R g1r_neg(const G1R& p) {   // -P: Y -> 16p - Y (Y 
 // SRS tables
 // ---------------------------------------------------------------------------
 // T[r * n + i] = 2^(r * step) * P_i, affine, in the reduced-radix form (x, y < 2p): `rows` = 16, step = 16 (window
-// tables) or rows = 256, step = 1 (bit-position tables).  One lane per point: (rows - 1) * step doublings in XYZZ
+// tables), rows = 256, step = 1 (bit-position tables), 128 / 2 or 64 / 4 (half- and quarter-density rows).  One lane per point: (rows - 1) * step doublings in XYZZ
 // coordinates, and ONE Fp inversion for the rows - 1 normalisations (Montgomery's trick along the lane's own rows: the
 // unnormalised X, Y wait in their table slots, ZZ, ZZZ and the running product of the ZZ * ZZZ in a scratch array of
 // 3 x 64 B per row and point; one inversion per row made the inversions 4/5 of this kernel; the one that remains is the
@@ -991,7 +991,9 @@ __global__ void msm_identity_kernel(G1* out) {
 //     (ADVICE r4): bit-position rows when they take at most 60 % of the budget, every second position at most 30 %;
 //   * a prover's LAGRANGE-basis key is built last, nothing grows after it: the densest layout that fits in what is left.
 // 2^20 points: 32 GiB per key, twice per prover context, of 288 GB; 2^22: 137 GB for the commit key + 69 GB of half-density
-// rows for the Lagrange-basis key.  plonk_gpu_config.table_mode (PLONK_MSM_TABLE=window|halfpos|bitpos) forces a layout.
+// rows for the Lagrange-basis key.  plonk_gpu_config.table_mode (PLONK_MSM_TABLE=window|quarter|halfpos|bitpos) forces a layout;
+// a row per FOURTH bit position (64 rows, 8 KiB per point, for_each_digit_quad: 13.0 additions per scalar over 2^19 buckets, 16.0
+// over 2^15) is taken only when forced.
 uint64_t msm_table_bytes(uint32_t rows, uint64_t n) {
   const uint64_t scratch = sizeof(Fp28Slot) * 3 * (uint64_t)(rows - 1) * (1ull << 16);   // srs_table_kernel's per-chunk scratch
   return sizeof(G1AffineR) * (uint64_t)rows * n + (rows > MSM_ROWS_WINDOW ? scratch : 0);
@@ -1001,6 +1003,7 @@ uint32_t msm_table_rows(const Ctx* c, uint64_t n, bool last_key) {
   const int mode = c->cfg.table_mode;
   if (mode == (int)MSM_ROWS_WINDOW) return MSM_ROWS_WINDOW;
   if (mode == (int)MSM_ROWS_HALFPOS) return MSM_ROWS_HALFPOS;                          // (table_index_check refuses an oversized key)
+  if (mode == (int)MSM_ROWS_QUARTERPOS) return MSM_ROWS_QUARTERPOS;                    // forced only: the automatic rule never picks it
   if (mode == (int)MSM_ROWS_BITPOS) return index_ok(MSM_ROWS_BITPOS) ? MSM_ROWS_BITPOS : MSM_ROWS_WINDOW;
   // small keys: the saved additions do not pay for the longer recoding, the skewed top digit and — with the 2^19-bucket
   // layout — a reduction over 16x the buckets (same-box pairs, window rows vs bit-position rows: 2^16 gates 5.33 / 5.59 ms,
@@ -1060,7 +1063,7 @@ void srs_table_scratch_free(Ctx* c) {   // after the stream that ran the table k
 // stream: the launches share one scratch array and rely on stream order)
 static int srs_table_launch(Ctx* c, const G1Affine* pts_dev, G1AffineR* table, uint32_t rows, uint64_t n, uint64_t first, uint64_t count, hipStream_t st) {
   const uint64_t chunk = srs_table_chunk_points(rows);
-  const uint32_t step = rows == MSM_ROWS_BITPOS ? 1u : (rows == MSM_ROWS_HALFPOS ? 2u : (uint32_t)MSM_C);
+  const uint32_t step = rows == MSM_ROWS_BITPOS ? 1u : (rows == MSM_ROWS_HALFPOS ? 2u : (rows == MSM_ROWS_QUARTERPOS ? 4u : (uint32_t)MSM_C));
   for (uint64_t off = 0; off < count; off += chunk) {
     const uint64_t cnt = count - off < chunk ? count - off : chunk;
     const int rc = srs_table_scratch(c, 3ull * (rows - 1) * cnt);
@@ -1653,11 +1656,11 @@ int msm_reserve(Ctx* c, uint64_t m) {
 // 2^19 (same box, 2^19 gates: window rows 19.94 ms, bit-position rows over 2^15 / 2^17 / 2^19 buckets 21.31 / 19.99 / 19.20;
 // 2^18 gates: 10.94 / 10.92 / 11.01 / 11.44 — profiles/r04h) — a rank of a 2-GPU job at 2^20 gates or of an 8-GPU job at
 // 2^22 holds 2^19 points.  plonk_gpu_config.msm_bucket_bits (PLONK_MSM_BUCKETS=15 / 19) forces one wherever it is possible
-// (19 needs bit-position or half-density rows and the bit-sum tail; 17: the opt-in A/B build with the 2^17-bucket variant).
+// (19 needs bit-position, half- or quarter-density rows and the bit-sum tail; 17: the opt-in A/B build with the 2^17-bucket variant).
 void msm_plan(const Ctx* c, uint32_t table_rows, uint64_t table_n, uint64_t mmax, int count, bool bit_sums, plonk_msm_plan_internal* out) {
   (void)count;
   const int buckets_env = c->cfg.bucket_bits;
-  const bool can_large = (table_rows == MSM_ROWS_BITPOS || table_rows == MSM_ROWS_HALFPOS) && bit_sums && !c->cfg.tail_serial && !c->cfg.acc_lds;
+  const bool can_large = (table_rows == MSM_ROWS_BITPOS || table_rows == MSM_ROWS_HALFPOS || table_rows == MSM_ROWS_QUARTERPOS) && bit_sums && !c->cfg.tail_serial && !c->cfg.acc_lds;
   int nb_bits = 15;
   if (can_large) {
     if (buckets_env == 17 || buckets_env == 19) nb_bits = buckets_env;
@@ -1671,6 +1674,7 @@ void msm_plan(const Ctx* c, uint32_t table_rows, uint64_t table_n, uint64_t mmax
   p.table_rows = table_rows;
   p.bucket_bits = (uint32_t)nb_bits;
   p.digit_width = table_rows == MSM_ROWS_WINDOW ? 16u : (table_rows == MSM_ROWS_BITPOS ? (uint32_t)nb_bits + 2u : (uint32_t)nb_bits + 1u);
+  if (table_rows == MSM_ROWS_QUARTERPOS) p.digit_width &= ~3u;   // MSM_QUAD_WIDTH: bucket_bits + 1 over 2^15 and 2^19 buckets (16 over the opt-in 2^17)
   p.terms = mmax;
   bool ordered;
   if (nb_bits == 19) { p.slice_entries = nbl::msm_ksl(c, mmax); ordered = nbl::msm_acc_ordered(c, p.slice_entries); p.wide_words = nbl::msm_needs_wide_words(table_rows, table_n); }
@@ -1684,7 +1688,7 @@ void msm_plan(const Ctx* c, uint32_t table_rows, uint64_t table_n, uint64_t mmax
       {"nbm::msm_accumulate_kernel", "nbm::msm_accumulate_ordered_kernel", "nbm::msm_accumulate_lds_kernel"},
       {"nbl::msm_accumulate_kernel", "nbl::msm_accumulate_ordered_kernel", "nbl::msm_accumulate_lds_kernel"}};
   const uint64_t avg_slices = (MSM_W * mmax) / (p.slice_entries ? p.slice_entries : 1) / (1ull << nb_bits);
-  p.flags = ((nb_bits > 15 && c->cfg.sort13 == 1) ? PLONK_PLAN_SORT13 : 0u) | (c->cfg.tail_serial ? PLONK_PLAN_TAIL_SERIAL : 0u) | (c->cfg.acc_lds ? PLONK_PLAN_ACCUMULATE_LDS : 0u) |
+  p.flags = ((nb_bits > 15 && c->cfg.sort13 == 1 && table_rows != MSM_ROWS_QUARTERPOS) ? PLONK_PLAN_SORT13 : 0u) | (c->cfg.tail_serial ? PLONK_PLAN_TAIL_SERIAL : 0u) | (c->cfg.acc_lds ? PLONK_PLAN_ACCUMULATE_LDS : 0u) |
             ((c->cfg.bsum_lane || c->cfg.tail_serial || avg_slices > 8 || (nb_bits > 15 && p.ordered_lanes)) ? PLONK_PLAN_BUCKET_SUM_LANE : 0u);
   p.kernel = names[nb_bits == 19 ? 2 : (nb_bits == 17 ? 1 : 0)][c->cfg.acc_lds ? 2 : (p.ordered_lanes ? 1 : 0)];
   *out = p;
@@ -1705,7 +1709,7 @@ int msm_batch_device(Ctx* c, const Fr* const* scalars_dev, const uint64_t* m, in
   if (phase < 1 || phase > 3 || kb0 < 0 || kcount < 1 || kb0 + kcount > count || (phase == 3 && (kb0 != 0 || kcount != count)))
     return (plonk::set_last_error("invalid argument", "msm_batch_device: phase / column range", __FILE__, __LINE__), PLONK_ERR_ARG);
   if (!table) { table = c->srs_table; table_n = c->srs_n; table_rows = c->srs_rows; }
-  if (table && table_rows != MSM_ROWS_WINDOW && table_rows != MSM_ROWS_BITPOS && table_rows != MSM_ROWS_HALFPOS) return (plonk::set_last_error("invalid argument", "msm: table rows", __FILE__, __LINE__), PLONK_ERR_ARG);
+  if (table && table_rows != MSM_ROWS_WINDOW && table_rows != MSM_ROWS_BITPOS && table_rows != MSM_ROWS_HALFPOS && table_rows != MSM_ROWS_QUARTERPOS) return (plonk::set_last_error("invalid argument", "msm: table rows", __FILE__, __LINE__), PLONK_ERR_ARG);
   uint64_t mmax = 0;
   for (int k = 0; k < count; ++k) {
     if (m[k] > table_n) return PLONK_ERR_DEGREE;

@@ -1,7 +1,7 @@
 // Scalar -> table entries: the two digit recodings of the MSM (msm_sort.hip), host- and device-callable so that
 // tests/test_field_host.py checks them on the CPU against the big-int model (tests/msm_wide_model.py).
 //
-// Both produce at most MSM_W = 16 non-zero digits per scalar s < 2^255, s = sum_j d_j * 2^(row_j), and call
+// All produce at most MSM_W = 16 non-zero digits per scalar s < 2^255, s = sum_j d_j * 2^(row_j), and call
 //     f(slot j, row_j, bucket, sign)
 // for each of them in order of increasing row; a table entry T[row][i] = 2^row * P_i (bit-position tables) or
 // 2^(16 row) * P_i (window tables) then contributes sign * weight(bucket) * T[row][i].
@@ -21,7 +21,7 @@
 namespace plonk {
 
 static constexpr int MSM_DIGITS = 16;          // most non-zero digits of a scalar under either recoding (= MSM_W)
-static constexpr uint32_t MSM_ROWS_WINDOW = 16, MSM_ROWS_BITPOS = 256, MSM_ROWS_HALFPOS = 128;
+static constexpr uint32_t MSM_ROWS_WINDOW = 16, MSM_ROWS_BITPOS = 256, MSM_ROWS_HALFPOS = 128, MSM_ROWS_QUARTERPOS = 64;
 static constexpr uint32_t MSM_NAF_W = 17;      // digit width of the bit-position recoding over 2^15 buckets: odd |d| < 2^16
 
 // Signed 16-bit windows, least significant first (carry into the next window when the value exceeds 2^15).
@@ -135,10 +135,44 @@ HD void for_each_digit_even(const S& s, F&& f) {
   }
 }
 
+// Quarter-density tables: a row for every FOURTH bit position, T[r][i] = 2^(4 r) * P_i, r < 64 — 8 KiB per point, a quarter of
+// the bit-position tables, for a key that has to share the device (a second large prover, several provers on one card).  The
+// same construction as above with groups of 4 bits: a digit starts at positions p = 0 mod 4 only and is taken where the
+// remaining value (s >> p) + carry is NOT a multiple of 16, i.e. where the 4-bit group at p differs from the carry repeated
+// four times.  W bits wide (W a multiple of 4), signed: d in [-2^(W-1), 2^(W-1)], d != 0 mod 16, bucket = |d| - 1 with weight
+// bucket + 1 (the window convention again).  After a digit the run of 4-bit groups equal to the carry has mean length 1/15:
+// 254.9 / (W + 4/15) + 1/2 digits per scalar — 13.0 for W = 20 over 2^19 buckets, 16.0 for W = 16 over 2^15 (window rows: 16).
+// The last two digits share the remaining bits in widths that are multiples of 4, and as above no digit that reaches bit 255
+// comes out negative or leaves a carry (s < 2^255).
+template <uint32_t W, class S, class F>
+HD void for_each_digit_quad(const S& s, F&& f) {
+  static_assert(W % 4 == 0 && W >= 4 && W <= 20, "digit width: a multiple of 4");
+  uint32_t p = 0, carry = 0;
+#pragma unroll
+  for (int j = 0; j < MSM_DIGITS; ++j) {
+    const uint32_t flip = 0u - carry;
+    while (p < 256) {                                  // next 4-bit group that differs from (carry, carry, carry, carry)
+      const uint32_t x = bits32_at(s, p) ^ flip;
+      if (x) { p += (uint32_t)__builtin_ctz(x) & ~3u; break; }
+      p += 32;
+    }
+    if (p >= 256) break;
+    const uint32_t rem = 256u - p;                     // a multiple of 4
+    const uint32_t w = (rem > W && rem <= 2 * W) ? ((rem / 2 + 3) & ~3u) : W;     // a multiple of 4, >= rem / 2, <= W
+    const uint32_t v = (bits32_at(s, p) & ((1u << w) - 1u)) + carry;   // in [1, 2^w), not a multiple of 16
+    const uint32_t neg = v > (1u << (w - 1)) ? 1u : 0u;                // the digit is v - 2^w
+    const uint32_t mag = neg ? (1u << w) - v : v;                      // in [1, 2^(w-1)]
+    f(j, p >> 2, mag - 1u, neg);
+    carry = neg;
+    p += w;
+  }
+}
+
 template <class S, class F>
 HD void for_each_digit(const S& s, uint32_t rows, F&& f) {
   if (rows == MSM_ROWS_BITPOS) for_each_digit_bitpos(s, f);
   else if (rows == MSM_ROWS_HALFPOS) for_each_digit_even<16>(s, f);
+  else if (rows == MSM_ROWS_QUARTERPOS) for_each_digit_quad<16>(s, f);
   else for_each_digit_window(s, f);
 }
 

@@ -107,11 +107,14 @@ __device__ __forceinline__ Fr scalar_canonical(const Fr& mont) {
 
 // ---- level 1a: coarse histogram -------------------------------------------------------------------
 // MODE: how the scalars are recoded (msm_recode.cuh) — 0 signed 16-bit windows (window tables, 2^15 buckets only), 1 width-w NAF
-// (a table row per bit position), 2 even-position digits (a row for every second bit position, round 4)
+// (a table row per bit position), 2 even-position digits (a row for every second bit position, round 4), 3 digits at every
+// fourth position (quarter-density rows)
 static constexpr uint32_t MSM_EVEN_WIDTH = (MSM_NB_BITS + 1) & ~1u;   // even-position digits: |d| <= 2^(width - 1) <= 2^NB_BITS, bucket = |d| - 1
+static constexpr uint32_t MSM_QUAD_WIDTH = (MSM_NB_BITS + 1) & ~3u;   // digits at every fourth position: 16 (2^15 / 2^17 buckets) or 20 (2^19), same bound
+static_assert(MSM_QUAD_WIDTH >= 4 && (1u << (MSM_QUAD_WIDTH - 1)) <= MSM_NB, "a quarter-density digit fits the buckets");
 template <int MODE>
 __global__ void __launch_bounds__(SORT_T) msm_hist_kernel(MsmBatch bt, uint32_t* __restrict__ coarse_cnt_all) {
-  constexpr bool BITPOS = MODE != 0;                   // the scalar is parked in LDS for the run-time bit positions of modes 1 and 2
+  constexpr bool BITPOS = MODE != 0;                   // the scalar is parked in LDS for the run-time bit positions of modes 1, 2 and 3
   __shared__ uint32_t hist[COARSE];
   __shared__ uint32_t park[BITPOS ? 9 * SORT_T : 1];   // bit-position recoding: the canonical scalar, limb-major, + a zero limb (StridedLimbs)
   const int kb = (int)blockIdx.y + bt.kb0;
@@ -138,7 +141,8 @@ __global__ void __launch_bounds__(SORT_T) msm_hist_kernel(MsmBatch bt, uint32_t*
 #pragma unroll
         for (int j = 0; j < 8; ++j) park[j * SORT_T + t] = s.l[j];   // read back by this lane only: no barrier
         park[8 * SORT_T + t] = 0;
-        if (MODE == 2) for_each_digit_even<MSM_EVEN_WIDTH>(StridedLimbs{park + t, SORT_T}, count);
+        if (MODE == 3) for_each_digit_quad<MSM_QUAD_WIDTH>(StridedLimbs{park + t, SORT_T}, count);
+        else if (MODE == 2) for_each_digit_even<MSM_EVEN_WIDTH>(StridedLimbs{park + t, SORT_T}, count);
         else for_each_digit_naf<MSM_NAF_WIDTH>(StridedLimbs{park + t, SORT_T}, count);
       } else if constexpr (MSM_NB_BITS == 15) {
         for_each_digit_window(s, count);
@@ -268,7 +272,8 @@ __global__ void __launch_bounds__(SORT_T) msm_partition_kernel(MsmBatch bt, uint
 #pragma unroll
         for (int j = 0; j < 8; ++j) park[j * SORT_T + t] = s.l[j];
         park[8 * SORT_T + t] = 0;
-        if (MODE == 2) for_each_digit_even<MSM_EVEN_WIDTH>(StridedLimbs{park + t, SORT_T}, put);
+        if (MODE == 3) for_each_digit_quad<MSM_QUAD_WIDTH>(StridedLimbs{park + t, SORT_T}, put);
+        else if (MODE == 2) for_each_digit_even<MSM_EVEN_WIDTH>(StridedLimbs{park + t, SORT_T}, put);
         else for_each_digit_naf<MSM_NAF_WIDTH>(StridedLimbs{park + t, SORT_T}, put);
       } else if constexpr (MSM_NB_BITS == 15) {
         for_each_digit_window(s, put);
@@ -343,7 +348,7 @@ __global__ void __launch_bounds__(P2_T, 4) msm_partition2_kernel(MsmBatch bt, ui
                                                                   const uint32_t* __restrict__ coarse_off_all,
                                                                   uint32_t* __restrict__ coarse_cur_all,
                                                                   void* __restrict__ tmp_all) {
-  static_assert(MODE != 0, "bit-position / half-density recodings only");
+  static_assert(MODE == 1 || MODE == 2, "bit-position / half-density recodings only (quarter-density rows take msm_partition_kernel)");
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
   uint32_t* stage = lds;                          // P2_TILE * P2_W
   uint32_t* hist = lds + P2_TILE * P2_W;          // COARSE
@@ -818,7 +823,7 @@ static int msm_group_sort_t(Ctx* c, const MsmBatch& bt, uint64_t mmax) {
   hipLaunchKernelGGL(msm_hist_kernel<MODE>, dim3(htiles, bt.count), dim3(SORT_T), 0, st, bt, w.coarse_cnt);
   hipLaunchKernelGGL(msm_coarse_scan_kernel, dim3(bt.count), dim3(SORT_T), 0, st, w.coarse_cnt, w.coarse_off, w.coarse_cur, w.big_off, kb0);
 #if PLONK_MSM_NB_BITS >= 19
-  if constexpr (MODE != 0) {
+  if constexpr (MODE == 1 || MODE == 2) {   // (not extended to quarter-density rows: measured slower, they always take msm_partition_kernel)
     if (c->cfg.sort13 == 1) {   // round 5 A/B: two half-size partition workgroups per CU (13 digit slots of 1024 scalars)
       const uint32_t tiles2 = (uint32_t)((mmax + P2_TILE - 1) / P2_TILE);
       smem_opt_in(c, (const void*)msm_partition2_kernel<MODE, WordT>, PARTITION2_LDS);
@@ -826,7 +831,7 @@ static int msm_group_sort_t(Ctx* c, const MsmBatch& bt, uint64_t mmax) {
                          w.coarse_off, w.coarse_cur, tmp);
     }
   }
-  if (MODE == 0 || c->cfg.sort13 != 1) {
+  if (MODE == 0 || MODE == 3 || c->cfg.sort13 != 1) {
 #else
   {
 #endif
@@ -883,6 +888,7 @@ int msm_group_sort(Ctx* c, const MsmBatch& bt, uint64_t mmax) {
     return (set_last_error("commit key too large for the bucket sort", "table rows * points must be <= 2^31", __FILE__, __LINE__), PLONK_ERR_ARG);
   if (bt.rows == MSM_ROWS_BITPOS) return bt.wide ? msm_group_sort_t<1, uint64_t>(c, bt, mmax) : msm_group_sort_t<1, uint32_t>(c, bt, mmax);
   if (bt.rows == MSM_ROWS_HALFPOS) return bt.wide ? msm_group_sort_t<2, uint64_t>(c, bt, mmax) : msm_group_sort_t<2, uint32_t>(c, bt, mmax);
+  if (bt.rows == MSM_ROWS_QUARTERPOS) return bt.wide ? msm_group_sort_t<3, uint64_t>(c, bt, mmax) : msm_group_sort_t<3, uint32_t>(c, bt, mmax);
 #if PLONK_MSM_NB_BITS == 15
   return bt.wide ? msm_group_sort_t<0, uint64_t>(c, bt, mmax) : msm_group_sort_t<0, uint32_t>(c, bt, mmax);
 #else

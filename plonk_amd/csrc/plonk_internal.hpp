@@ -100,7 +100,7 @@ struct MsmBatch {   // one commitment group: up to MSM_MAX_BATCH MSMs over the s
   uint64_t cap_m, cap_slices;
   const void* table;   // tables the entries index: the context's commit key, or a prover's Lagrange-basis key
   uint64_t table_n;    // points per row of `table`
-  uint32_t rows;       // MSM_ROWS_WINDOW (16), MSM_ROWS_BITPOS (256) or MSM_ROWS_HALFPOS (128): which recoding the entries come from
+  uint32_t rows;       // MSM_ROWS_WINDOW (16), MSM_ROWS_BITPOS (256), MSM_ROWS_HALFPOS (128) or MSM_ROWS_QUARTERPOS (64): which recoding the entries come from
   uint32_t ordered;    // lanes of the accumulation in order of slice length: the sort also writes full_off / part_list
   uint32_t wide;       // the coarse-partitioned words are 64-bit (rows * table_n above 2^27)
   uint32_t heavy_thresh;   // a bucket with more slices than this is "heavy" (msm_slices_kernel lists it, msm.hip sums it by segments)
@@ -153,7 +153,7 @@ struct MsmWork {   // per-context scratch, grown on demand
 struct Config {
   // public fields (include/plonk_hip.h)
   uint64_t table_budget = 0;        // bytes all point tables of the context may take together (resolved: never 0)
-  int table_mode = 0;               // 0 auto, else MSM_ROWS_WINDOW / _HALFPOS / _BITPOS
+  int table_mode = 0;               // 0 auto, else MSM_ROWS_WINDOW / _QUARTERPOS / _HALFPOS / _BITPOS
   int bucket_bits = 0;              // 0 by the number of terms, 15, 17 (A/B build), 19
   int quotient_domain = 4;          // 4 or 8
   int wire_commit_coeff = 0;        // 1: coefficient-form wire commitments
@@ -215,7 +215,7 @@ struct Ctx {
   Fr* ntt_tmp = nullptr;
   uint64_t ntt_cap = 0;
   // SRS
-  void* srs_table = nullptr;       // [srs_rows][npoints] 128-B affine entries (Fp28): 2^(16 w) * P_i (16 rows), 2^r * P_i (256 rows) or 4^r * P_i (128 rows)
+  void* srs_table = nullptr;       // [srs_rows][npoints] 128-B affine entries (Fp28): 2^(16 w) * P_i (16 rows), 2^r * P_i (256 rows), 4^r * P_i (128 rows) or 16^r * P_i (64 rows)
   uint32_t srs_rows = 0;
   void* table_scratch = nullptr;   // srs_table_kernel's per-window ZZ / ZZZ / running products, alive during a key load
   uint64_t table_scratch_pts = 0;
