@@ -518,7 +518,8 @@ int plonk_verifier_to_bytes(plonk_prover* p, const uint8_t* opening_key, uint64_
  * calls (up to the aggregation's soundness error, <= K / q per check; DESIGN.md, "Proof verification").  The call holds
  * the context for its whole duration, bisection included: a batch of K proofs that are ALL bad costs 2K - 1 checks (each one
  * MSM launch and one pairing, ~10 ms at small sizes), so a caller verifying untrusted batches on a context it also proves
- * on should bound K.
+ * on should bound K.  For untrusted batches plonk_verify_each (below) gives the same verdicts with one pairing per proof
+ * on the device, at a cost that does not depend on how many proofs are bad.
  * plonk_verifier_last reports the last plonk_verify: msm_terms counts the terms of both sums of its FIRST check,
  * pairing_checks all checks (1 for a valid batch), the phase times are host wall-clock milliseconds. */
 typedef struct plonk_verifier plonk_verifier;
@@ -561,6 +562,28 @@ int plonk_verifier_last(plonk_verifier* v, plonk_verify_info* out);
  * (may be NULL) the same way instead; ms_scalars covers the replay kernel, the rho derivation and the weighting. */
 int plonk_verify_mixed(plonk_verifier* const* verifiers, uint32_t nverifiers, const uint32_t* circuit, const uint8_t* proofs,
                        const uint64_t* pi, uint64_t pi_total, uint64_t count, int32_t* verdicts, plonk_verify_info* info);
+/* plonk_verify_each: the arguments of plonk_verify_mixed (circuit == NULL: every proof belongs to verifiers[0]), but every
+ * proof is checked ON ITS OWN: decode, device replay and statuses as plonk_verify_mixed, then per proof its own 2 + 27 terms
+ * (L: W_z with 1 and W_zw with u; R: the 15 VK points of its circuit, g and its 11 commitments, unweighted), one wave per
+ * proof for the two sums and ONE PAIRING CHECK PER PROOF in one lane of a device kernel.  No rho, no
+ * batch transcript, no bisection, no K / q soundness term: verdict k equals exactly what a count == 1 plonk_verify of proof k
+ * with its own verifier and version returns, and the cost does not depend on how many proofs are bad.  verdicts is
+ * required (count entries; there is no NULL form); a malformed proof (PLONK_ERR_POINT, PLONK_ERR_DATA) never stops the
+ * others from being decided.  Returns PLONK_OK iff every verdict is, PLONK_ERR_VERIFY otherwise, PLONK_ERR_ARG for
+ * everything plonk_verify_mixed refuses.  info (may be NULL): proofs = count, pairing_checks = the proofs that reached the
+ * pairing kernel (never more than count), msm_terms = 29 per such proof, rejected = verdicts other than PLONK_OK, the phase
+ * times host wall clock around the phases (ms_scalars: replay and packing, ms_msm: the per-proof sums, ms_pairing: the
+ * pairing kernel).  Writes nothing into any verifier's plonk_verifier_last; the line tables of (x_h, h) for the pairing
+ * kernel (about 47 KB of device memory) are made by the first call that uses a verifier's opening key and freed with that
+ * verifier.  When to use it (measured on an MI355X at 2^12 gates): a device pairing check is about
+ * 28 ms of latency whatever the count (8192 checks: 29 ms), so a VALID batch costs 1.8x (K = 1024) to 3.4x (K = 1) what
+ * plonk_verify_mixed costs (K = 8192: 79 ms against 39 ms) — keep that call for input expected to be valid.  A bad proof
+ * costs the bisection about 2 log2 K further checks of 6 to 10 ms (K = 8192 with 8 bad proofs: 1875 ms against 80 ms here;
+ * K = 256 all bad: 3.0 s against 39 ms), so from K = 64 on, one expected bad proof per batch already makes this the cheaper
+ * call, and it is the one whose cost an adversary cannot raise.  Below about 4 proofs, count == 1 calls of plonk_verify
+ * are cheaper. */
+int plonk_verify_each(plonk_verifier* const* verifiers, uint32_t nverifiers, const uint32_t* circuit, const uint8_t* proofs,
+                      const uint64_t* pi, uint64_t pi_total, uint64_t count, int32_t* verdicts, plonk_verify_info* info);
 typedef struct {
   uint64_t size, constraints;
   uint64_t label_off, label_len;
@@ -652,7 +675,7 @@ int plonk_srs_load_public_parameters(plonk_ctx* ctx, const uint8_t* bytes, uint6
  *     of the openings could predict (a constant, a counter, anything fixed before the batch is) VOIDS the check.
  *   PLONK_OK; PLONK_ERR_VERIFY for a failing batch and for count == 0 (key.rs:667); PLONK_ERR_POINT for a commitment that is
  *   not a valid compressed G1 point (the identity is legal); PLONK_ERR_DATA for a non-canonical scalar.  No bisection: a
- *   caller who wants per-item answers calls with count == 1.  info (may be NULL) is filled as plonk_verify_mixed fills it.
+ *   caller who wants per-item answers calls plonk_kzg_check_each (or this with count == 1).  info (may be NULL) is filled as plonk_verify_mixed fills it.
  * plonk_srs_check: is the commit key the key's context holds (N points P_i) [tau^i] g for the tau of THIS opening key?
  *     P_0 == g  and  e(sum_{i < N-1} r^i P_(i+1), h) == e(sum_{i < N-1} r^i P_i, x_h),
  *   r = challenge_scalar("r") of a Merlin transcript "plonk-srs-check-v1" over append_message("seed", seed32),
@@ -681,6 +704,27 @@ int plonk_kzg_batch_check(plonk_kzg_key* key, const uint64_t* points /* count x 
                           const uint8_t* label, uint64_t label_len, const uint64_t* u_override /* 4 limbs or NULL */,
                           plonk_verify_info* info);
 int plonk_srs_check(plonk_kzg_key* key, const uint8_t seed32[32]);
+/* Per-item verdicts in one pass: one pairing check per item on the device, where
+ * plonk_kzg_batch_check answers for the whole batch.  Exact: no challenge u, so nothing can cancel between items.
+ * plonk_kzg_pairing_check_each: verdicts[k] = PLONK_OK iff e(A_k, x_h) == e(B_k, h), computed as e(-A_k, x_h) e(B_k, h) == 1
+ *   for the key's (h, x_h); a48 / b48: count x 48 bytes, compressed G1.  (O, O) passes, a pair with exactly one identity
+ *   fails.  With consecutive points of a powers-of-tau file (A_i = P_i, B_i = P_(i+1)) the failing pairs name the wrong
+ *   point, which plonk_srs_check cannot.
+ * plonk_kzg_check_each: OpeningKey::check of every opening proofs[k] at points[k] on its own: L_k = W_k, R_k = C_k + z_k W_k -
+ *   v_k g (terms packed and summed on the device, one wave per opening).  Each verdict equals what plonk_kzg_batch_check
+ *   with count == 1 returns for that item.
+ * Both: verdicts (count entries, required) are PLONK_OK, PLONK_ERR_VERIFY, PLONK_ERR_POINT (a point that does not decode or
+ * is outside the subgroup; the compressed identity is legal) or PLONK_ERR_DATA (a non-canonical scalar; looked at before the
+ * points, as plonk_kzg_batch_check does); a malformed item never stops the others from being decided.  Return PLONK_OK iff
+ * every verdict is, PLONK_ERR_VERIFY otherwise, PLONK_ERR_ARG for a NULL argument, count == 0 or count > 2^24.  info (may be
+ * NULL): proofs = count, pairing_checks = items that reached the pairing kernel, msm_terms = 4 per such opening (0 for the
+ * bare pairing call), rejected = verdicts other than PLONK_OK, phase times as plonk_verify_each.  The workspace is owned by
+ * the context and grows on demand; the key's line tables (about 47 KB of device memory) are made by the first call and freed
+ * with the key.  The calls leave the context, its commit key, tables and provers as they found them. */
+int plonk_kzg_pairing_check_each(plonk_kzg_key* key, const uint8_t* a48, const uint8_t* b48, uint64_t count, int32_t* verdicts,
+                                 plonk_verify_info* info /* may be NULL */);
+int plonk_kzg_check_each(plonk_kzg_key* key, const uint64_t* points /* count x 4 */, const plonk_kzg_proof* proofs, uint64_t count,
+                         int32_t* verdicts, plonk_verify_info* info);
 
 /* ---- variable-base MSM over caller-supplied points ------------------------------------------------
  * sum_i scalars[i] * P_i for points the CALLER brings — the reference's msm_variable_base (the primitive under Proof::verify

@@ -70,6 +70,7 @@ EXPORTS = [
     "plonk_composer_info", "plonk_composer_layout", "plonk_compile_composer",
     "plonk_prover_fill_inputs", "plonk_prover_prove_inputs", "plonk_prover_diagnose_inputs",
     "plonk_msm_points", "plonk_msm_points_dev", "plonk_ctx_last_msm_points",
+    "plonk_kzg_pairing_check_each", "plonk_kzg_check_each", "plonk_verify_each",
 ]
 
 # what bit f of plonk_unsat_row.families / slot f of plonk_unsat_info.family_rows stands for (include/plonk_hip.h); the
@@ -379,6 +380,10 @@ def load_library() -> ctypes.CDLL:
     lib.plonk_kzg_batch_check.argtypes = [vp, vp, vp, u64, vp, u64, vp, vp]
     lib.plonk_srs_check.argtypes = [vp, vp]
     lib.plonk_test_kzg_last.argtypes = [vp, vp, vp]   # test hook of kzg.hip, not in the header
+    lib.plonk_kzg_pairing_check_each.argtypes = [vp, vp, vp, u64, vp, vp]
+    lib.plonk_kzg_check_each.argtypes = [vp, vp, vp, u64, vp, vp]
+    lib.plonk_verify_each.argtypes = [vp, u32, vp, vp, vp, u64, u64, vp, vp]
+    lib.plonk_test_pairing_each.argtypes = [vp, vp, vp, u64, vp]   # test hook of kzg.hip, not in the header
     lib.plonk_composer_create.argtypes = [ctypes.POINTER(vp)]
     lib.plonk_composer_destroy.argtypes = [vp]
     lib.plonk_composer_destroy.restype = None
@@ -1405,6 +1410,23 @@ class Verifier:
             self.ctx._check(rc)
         return verdicts
 
+    def verify_each(self, proofs, public_inputs) -> list:
+        """plonk_verify_each with circuit == NULL: every proof of this circuit checked on its own, one pairing per proof
+        on the device; per-proof verdict codes as verify_batch, at a cost that does not depend on how many are bad."""
+        proofs, pis = [bytes(p) for p in proofs], [list(p) for p in public_inputs]
+        if not proofs or len(proofs) != len(pis):
+            raise ValueError("a non-empty batch with one public-input list per proof")
+        if any(len(p) != 1008 for p in proofs):
+            raise ValueError("a proof is 1008 bytes")
+        flat = [v for p in pis for v in p]
+        handles = (ctypes.c_void_p * 1)(self.handle)
+        verdicts = (ctypes.c_int32 * len(proofs))()
+        rc = self.ctx.lib.plonk_verify_each(handles, 1, None, b"".join(proofs), fr_to_bytes_mont(flat) if flat else None, len(flat),
+                                            len(proofs), verdicts, None)
+        if rc not in (PLONK_OK, -12):
+            self.ctx._check(rc)
+        return [int(v) for v in verdicts]
+
     def last(self) -> dict:
         """plonk_verifier_last: what the last verification ran (proofs, msm_terms, pairing_checks, rejected, phase times)"""
         info = _VerifyInfo()
@@ -1475,6 +1497,50 @@ class KzgKey:
             self.ctx._check(rc)
         return rc == PLONK_OK
 
+    def pairing_check_each_info(self, a, b):
+        """(verdict codes, plonk_verify_info as a dict) of plonk_kzg_pairing_check_each: verdict k is 0 iff
+        e(a[k], x_h) == e(b[k], h); a, b: 48-byte compressed G1 points.  -10 (PLONK_ERR_POINT) for an item with a point that
+        does not decode or is outside the subgroup; the compressed identity is legal."""
+        a, b = [bytes(x) for x in a], [bytes(x) for x in b]
+        if len(a) != len(b) or not a or any(len(x) != 48 for x in a + b):
+            raise ValueError("two non-empty lists of 48-byte points, one pair per check")
+        verdicts = (ctypes.c_int32 * len(a))()
+        info = _VerifyInfo()
+        rc = self.ctx.lib.plonk_kzg_pairing_check_each(self.handle, b"".join(a), b"".join(b), len(a), verdicts, ctypes.byref(info))
+        if rc not in (PLONK_OK, -12):
+            self.ctx._check(rc)
+        return [int(v) for v in verdicts], {k: getattr(info, k) for k, _ in info._fields_}
+
+    def pairing_check_each(self, a, b) -> list:
+        return self.pairing_check_each_info(a, b)[0]
+
+    def check_each_info(self, points, proofs):
+        """(verdict codes, plonk_verify_info as a dict) of plonk_kzg_check_each: OpeningKey::check of every opening on its
+        own (0 valid, -12 PLONK_ERR_VERIFY, -10 PLONK_ERR_POINT, -9 PLONK_ERR_DATA).  `points` may hold Montgomery bytes
+        (32 each) in place of ints, for the non-canonical cases."""
+        points, proofs = list(points), list(proofs)
+        if len(points) != len(proofs) or not proofs:
+            raise ValueError("a non-empty batch with one point per proof")
+        arr = (KzgProof * len(proofs))(*proofs)
+        pts = b"".join(p if isinstance(p, (bytes, bytearray)) else fr_to_bytes_mont([p]) for p in points)
+        verdicts = (ctypes.c_int32 * len(proofs))()
+        info = _VerifyInfo()
+        rc = self.ctx.lib.plonk_kzg_check_each(self.handle, pts, arr, len(proofs), verdicts, ctypes.byref(info))
+        if rc not in (PLONK_OK, -12):
+            self.ctx._check(rc)
+        return [int(v) for v in verdicts], {k: getattr(info, k) for k, _ in info._fields_}
+
+    def check_each(self, points, proofs) -> list:
+        return self.check_each_info(points, proofs)[0]
+
+    def _pairing_each_values(self, a, b):
+        """TEST HOOK: per check the final-exponentiated Fp12 value of e(-a, x_h) e(b, h) as 12 integers (tower order), from
+        the device pairing kernel.  Not part of the C API."""
+        a, b = [bytes(x) for x in a], [bytes(x) for x in b]
+        out = (ctypes.c_uint64 * (72 * len(a)))()
+        self.ctx._check(self.ctx.lib.plonk_test_pairing_each(self.handle, b"".join(a), b"".join(b), len(a), out))
+        return [[sum(int(out[72 * k + 6 * i + j]) << (64 * j) for j in range(6)) for i in range(12)] for k in range(len(a))]
+
     def _last_challenges(self):
         u, r = ctypes.create_string_buffer(32), ctypes.create_string_buffer(32)
         self.ctx._check(self.ctx.lib.plonk_test_kzg_last(self.handle, u, r))
@@ -1530,3 +1596,23 @@ def verify_mixed(items):
     if rc not in (PLONK_OK, -12):
         ctx._check(rc)
     return [int(x) for x in verdicts], {k: getattr(info, k) for k, _ in info._fields_}
+
+
+def verify_each_info(items):
+    """plonk_verify_each: every proof checked on its own, one pairing per proof on the device — no batch challenge and no
+    bisection, so the cost does not depend on how many proofs are bad.  items as verify_mixed takes them; returns
+    (verdicts, info) in the same form.  Raises on argument errors (PLONK_ERR_ARG), never for a bad item."""
+    items = list(items)
+    args = _mixed_args(items)
+    ctx = items[0][0].ctx
+    verdicts = (ctypes.c_int32 * len(items))()
+    info = _VerifyInfo()
+    rc = ctx.lib.plonk_verify_each(*args, verdicts, ctypes.byref(info))
+    if rc not in (PLONK_OK, -12):
+        ctx._check(rc)
+    return [int(x) for x in verdicts], {k: getattr(info, k) for k, _ in info._fields_}
+
+
+def verify_each(items) -> list:
+    """the verdict codes of verify_each_info"""
+    return verify_each_info(items)[0]

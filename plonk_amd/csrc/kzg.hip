@@ -45,7 +45,8 @@ namespace plonk {
 static constexpr uint64_t KZG_STAGE_MIN = 1ull << 16;   // coefficients a staging buffer holds at least
 
 struct KzgWork {
-  enum { DESC, VPOW, EVALS, PARTIAL, FOLD, SCRATCH, TOTALS, STAGE0, STAGE1, PTS, KIND, COMP, SC, IDS, PART, POWERS, NBUF };
+  enum { DESC, VPOW, EVALS, PARTIAL, FOLD, SCRATCH, TOTALS, STAGE0, STAGE1, PTS, KIND, COMP, SC, IDS, PART, POWERS,
+         E_POINTS, E_PROOFS, E_PAIRS, E_PRE, E_VERDICT, E_VALUES, NBUF };   // E_*: the per-item checks (pairing.hip)
   void* p[NBUF] = {};
   uint64_t cap[NBUF] = {};
   hipEvent_t up[2] = {nullptr, nullptr}, done[2] = {nullptr, nullptr};
@@ -296,6 +297,8 @@ struct KzgKey {
   G2Prepared h, x_h;
   G1Affine g_aff;        // g as decoded on the device
   Fr last_u, last_r;     // the challenges of the last batch_check / srs_check (test hook)
+  void* pair_tables = nullptr;   // device: the lines of x_h and h for the pairing kernel, made by the first per-item call
+  ~KzgKey() { (void)hipFree(pair_tables); }
 };
 
 static int check_reserve(KzgWork& w, uint64_t npts, uint64_t nterms) {
@@ -321,11 +324,162 @@ static void compress_h1(const H1& s, uint8_t out48[48]) {
   g1_compress97(raw, out48);
 }
 
+// ---- per-item verdicts (pairing.hip) ----------------------------------------------------------------------------------
+static void each_info(plonk_verify_info* info, uint64_t count, uint64_t terms_per_item, uint32_t checked, uint32_t rejected,
+                      double ms_decode, double ms_scalars, double ms_msm, double ms_pairing) {
+  if (!info) return;
+  info->proofs = count;
+  info->msm_terms = terms_per_item * checked;
+  info->pairing_checks = checked;
+  info->rejected = rejected;
+  info->ms_decode = ms_decode;
+  info->ms_scalars = ms_scalars;
+  info->ms_msm = ms_msm;
+  info->ms_pairing = ms_pairing;
+}
+
+// plonk_kzg_pairing_check_each and its test hook (values != NULL: 72 words per check)
+static int pairing_each_body(plonk_kzg_key* key, const uint8_t* a48, const uint8_t* b48, uint64_t count, int32_t* verdicts,
+                             plonk_verify_info* info, uint64_t* values) {
+  KzgKey* kk = key->k;
+  Ctx& c = *kk->c;
+  KzgWork& w = kzg_work(&c);
+  PTRY_K(pairing_tables_create(&c, kk->x_h, kk->h, &kk->pair_tables));
+  const uint64_t npts = 2 * count;
+  PTRY_K(check_reserve(w, npts, 1));
+  PTRY_K(w.need(KzgWork::E_PAIRS, sizeof(G1) * npts));
+  PTRY_K(w.need(KzgWork::E_PRE, 4 * count));
+  PTRY_K(w.need(KzgWork::E_VERDICT, 4 * count));
+  if (values) PTRY_K(w.need(KzgWork::E_VALUES, 8 * 72 * count));
+  const auto t0 = std::chrono::steady_clock::now();
+  std::vector<uint8_t> comp(48 * npts);
+  for (uint64_t k = 0; k < count; ++k) {
+    memcpy(comp.data() + 96 * k, a48 + 48 * k, 48);
+    memcpy(comp.data() + 96 * k + 48, b48 + 48 * k, 48);
+  }
+  std::vector<int32_t> st;
+  PTRY_K(decode_points(&c, comp.data(), (uint32_t)npts, w.at<uint8_t>(KzgWork::COMP), w.at<G1Affine>(KzgWork::PTS),
+                       w.at<int32_t>(KzgWork::KIND), &st));
+  const auto t1 = std::chrono::steady_clock::now();
+  PTRY_K(each_pairs_launch(&c, w.at<const G1Affine>(KzgWork::PTS), w.at<const int32_t>(KzgWork::KIND), count,
+                           w.at<G1>(KzgWork::E_PAIRS), w.at<int32_t>(KzgWork::E_PRE)));
+  PTRY_K(pairing_each_launch(&c, kk->pair_tables, w.at<const G1>(KzgWork::E_PAIRS), w.at<const int32_t>(KzgWork::E_PRE), count,
+                             w.at<int32_t>(KzgWork::E_VERDICT), values ? w.at<uint64_t>(KzgWork::E_VALUES) : nullptr));
+  if (values) HIP_TRY(hipMemcpyAsync(values, w.p[KzgWork::E_VALUES], 8 * 72 * count, hipMemcpyDeviceToHost, c.stream));
+  uint32_t checked = 0, rejected = 0;
+  PTRY_K(each_finish(&c, w.at<const int32_t>(KzgWork::E_VERDICT), w.at<const int32_t>(KzgWork::E_PRE), count, verdicts, &checked,
+                     &rejected));
+  const auto t2 = std::chrono::steady_clock::now();
+  each_info(info, count, 0, checked, rejected, ms_between(t0, t1), 0, 0, ms_between(t1, t2));
+  return rejected ? PLONK_ERR_VERIFY : PLONK_OK;
+}
+
+static int kzg_check_each_body(plonk_kzg_key* key, const uint64_t* points, const plonk_kzg_proof* proofs, uint64_t count,
+                               int32_t* verdicts, plonk_verify_info* info) {
+  KzgKey* kk = key->k;
+  Ctx& c = *kk->c;
+  KzgWork& w = kzg_work(&c);
+  PTRY_K(pairing_tables_create(&c, kk->x_h, kk->h, &kk->pair_tables));
+  const uint64_t npts = 1 + 2 * count, nterms = KZG_EACH_TERMS * count;
+  PTRY_K(check_reserve(w, npts, nterms));
+  PTRY_K(w.need(KzgWork::E_POINTS, 32 * count));
+  PTRY_K(w.need(KzgWork::E_PROOFS, sizeof(plonk_kzg_proof) * count));
+  PTRY_K(w.need(KzgWork::E_PAIRS, sizeof(G1) * 2 * count));
+  PTRY_K(w.need(KzgWork::E_PRE, 4 * count));
+  PTRY_K(w.need(KzgWork::E_VERDICT, 4 * count));
+  const auto t0 = std::chrono::steady_clock::now();
+  // the point table [g | C_0 W_0 | C_1 W_1 ...], as plonk_kzg_batch_check's
+  std::vector<uint8_t> comp(48 * npts);
+  memcpy(comp.data(), kk->opening_key, 48);
+  for (uint64_t k = 0; k < count; ++k) {
+    memcpy(comp.data() + 48 * (1 + 2 * k), proofs[k].commitment, 48);
+    memcpy(comp.data() + 48 * (2 + 2 * k), proofs[k].witness, 48);
+  }
+  std::vector<int32_t> st;
+  PTRY_K(decode_points(&c, comp.data(), (uint32_t)npts, w.at<uint8_t>(KzgWork::COMP), w.at<G1Affine>(KzgWork::PTS),
+                       w.at<int32_t>(KzgWork::KIND), &st));
+  const auto t1 = std::chrono::steady_clock::now();
+  HIP_TRY(hipMemcpyAsync(w.p[KzgWork::E_POINTS], points, 32 * count, hipMemcpyHostToDevice, c.stream));
+  HIP_TRY(hipMemcpyAsync(w.p[KzgWork::E_PROOFS], proofs, sizeof(plonk_kzg_proof) * count, hipMemcpyHostToDevice, c.stream));
+  PTRY_K(kzg_each_pack_launch(&c, w.at<const uint64_t>(KzgWork::E_POINTS), w.at<const plonk_kzg_proof>(KzgWork::E_PROOFS),
+                              w.at<const int32_t>(KzgWork::KIND), count, w.at<uint32_t>(KzgWork::SC), w.at<uint32_t>(KzgWork::IDS),
+                              w.at<int32_t>(KzgWork::E_PRE)));
+  HIP_TRY(hipStreamSynchronize(c.stream));
+  const auto t2 = std::chrono::steady_clock::now();
+  PTRY_K(each_sums_launch(&c, w.at<const uint32_t>(KzgWork::SC), w.at<const uint32_t>(KzgWork::IDS), 1, 3, count,
+                          w.at<const G1Affine>(KzgWork::PTS), w.at<const int32_t>(KzgWork::KIND), w.at<const int32_t>(KzgWork::E_PRE),
+                          w.at<G1>(KzgWork::E_PAIRS)));
+  HIP_TRY(hipStreamSynchronize(c.stream));
+  const auto t3 = std::chrono::steady_clock::now();
+  PTRY_K(pairing_each_launch(&c, kk->pair_tables, w.at<const G1>(KzgWork::E_PAIRS), w.at<const int32_t>(KzgWork::E_PRE), count,
+                             w.at<int32_t>(KzgWork::E_VERDICT), nullptr));
+  uint32_t checked = 0, rejected = 0;
+  PTRY_K(each_finish(&c, w.at<const int32_t>(KzgWork::E_VERDICT), w.at<const int32_t>(KzgWork::E_PRE), count, verdicts, &checked,
+                     &rejected));
+  const auto t4 = std::chrono::steady_clock::now();
+  each_info(info, count, KZG_EACH_TERMS, checked, rejected, ms_between(t0, t1), ms_between(t1, t2), ms_between(t2, t3),
+            ms_between(t3, t4));
+  return rejected ? PLONK_ERR_VERIFY : PLONK_OK;
+}
+
 }  // namespace plonk
 
 using namespace plonk;
 
 extern "C" {
+
+int plonk_kzg_pairing_check_each(plonk_kzg_key* key, const uint8_t* a48, const uint8_t* b48, uint64_t count, int32_t* verdicts,
+                                 plonk_verify_info* info) {
+  const char* const api_fn = __func__;
+  return plonk::api_guard(api_fn, [&]() -> int {
+  if (!key || !a48 || !b48 || !verdicts) KZG_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
+  if (count == 0 || count > KZG_MAX_BATCH) KZG_FAIL(PLONK_ERR_ARG, "invalid argument: count must be in [1, 2^24]");
+  if (info) memset(info, 0, sizeof *info);
+  Ctx& c = *key->k->c;
+  CTX_ENTER(c, api_fn);
+  HIP_TRY(hipSetDevice(c.device));
+  const int rc = pairing_each_body(key, a48, b48, count, verdicts, info, nullptr);
+  if (rc != PLONK_OK && rc != PLONK_ERR_VERIFY) (void)hipStreamSynchronize(c.stream);   // nothing of the call stays queued
+  if (rc == PLONK_ERR_VERIFY) set_last_error(api_fn, "at least one pairing check fails", __FILE__, __LINE__);
+  return rc;
+  });
+}
+
+int plonk_kzg_check_each(plonk_kzg_key* key, const uint64_t* points, const plonk_kzg_proof* proofs, uint64_t count,
+                         int32_t* verdicts, plonk_verify_info* info) {
+  const char* const api_fn = __func__;
+  return plonk::api_guard(api_fn, [&]() -> int {
+  if (!key || !points || !proofs || !verdicts) KZG_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
+  if (count == 0 || count > KZG_MAX_BATCH) KZG_FAIL(PLONK_ERR_ARG, "invalid argument: count must be in [1, 2^24]");
+  if (info) memset(info, 0, sizeof *info);
+  Ctx& c = *key->k->c;
+  CTX_ENTER(c, api_fn);
+  HIP_TRY(hipSetDevice(c.device));
+  const int rc = kzg_check_each_body(key, points, proofs, count, verdicts, info);
+  if (rc != PLONK_OK && rc != PLONK_ERR_VERIFY) (void)hipStreamSynchronize(c.stream);
+  if (rc == PLONK_ERR_VERIFY) set_last_error(api_fn, "at least one opening does not verify", __FILE__, __LINE__);
+  return rc;
+  });
+}
+
+// Test hook (not in include/plonk_hip.h, not part of the API): plonk_kzg_pairing_check_each that also writes each check's
+// final-exponentiated Fp12 value as 12 canonical integers of 6 words (tower order: put_f12 of tests/csrc/host_verify.cpp; zeros
+// for an item that did not reach the pairing).  The binding's KzgKey._pairing_each_values calls it for
+// tests/test_gpu_pairing_each.py.
+int plonk_test_pairing_each(plonk_kzg_key* key, const uint8_t* a48, const uint8_t* b48, uint64_t count, uint64_t* out) {
+  const char* const api_fn = __func__;
+  return plonk::api_guard(api_fn, [&]() -> int {
+  if (!key || !a48 || !b48 || !out) KZG_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
+  if (count == 0 || count > (1ull << 16)) KZG_FAIL(PLONK_ERR_ARG, "invalid argument: count must be in [1, 2^16]");
+  Ctx& c = *key->k->c;
+  CTX_ENTER(c, api_fn);
+  HIP_TRY(hipSetDevice(c.device));
+  std::vector<int32_t> verdicts(count);
+  const int rc = pairing_each_body(key, a48, b48, count, verdicts.data(), nullptr, out);
+  if (rc != PLONK_OK && rc != PLONK_ERR_VERIFY) (void)hipStreamSynchronize(c.stream);
+  return rc == PLONK_ERR_VERIFY ? PLONK_OK : rc;
+  });
+}
 
 int plonk_kzg_open(plonk_ctx* ctx, const uint64_t* const* polys, const uint64_t* lens, uint64_t count, const uint64_t point[4],
                    const uint64_t* v_challenge, uint64_t* evaluations, uint8_t* commitments, uint8_t witness48[48]) {

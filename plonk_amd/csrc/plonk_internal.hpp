@@ -351,6 +351,30 @@ G1Aff64 xyzz_to_aff(const H1& p);
 // finished on the host (plonk_msm / plonk_msm_batch / the KZG opening calls): sums[k] = the commitment as an XYZZ point.
 // The caller has reserved the MSM scratch (msm_reserve) for the largest m; returns with the stream synchronised.
 int msm_group_sums(Ctx* c, const Fr* const* scalars_dev, const uint64_t* m, int cnt, G1* sums);
+// pairing.hip: per-item verdicts (plonk_kzg_pairing_check_each, plonk_kzg_check_each, plonk_verify_each).  Everything is
+// device memory and queued on the context's stream; only each_finish and pairing_tables_create synchronise it.
+static constexpr int EACH_LANES = 64;             // verify_each_sums_kernel: one wave per item, L terms in lanes [0, 32), R in [32, 64)
+static constexpr uint32_t KZG_EACH_TERMS = 4;     // per opening: {W: 1} and {C: 1, W: z, g: -v}
+static constexpr uint32_t VERIFY_EACH_TERMS = 29; // per proof: {W_z: 1, W_zw: u} and the 15 VK points, g, 11 commitments
+// the Frobenius constants and the prepared lines of (x_h, h) as Fp28 limbs on the device (about 47 KB); *out_dev != NULL: kept
+int pairing_tables_create(Ctx* c, const G2Prepared& x_h, const G2Prepared& h, void** out_dev);
+// decoded points [A_0 B_0 A_1 B_1 ...] -> pairs[2 count] and pre[count] (PLONK_ERR_POINT for an item with a bad point)
+int each_pairs_launch(Ctx* c, const G1Affine* pts, const int32_t* kind, uint64_t count, G1* pairs, int32_t* pre);
+// per opening its KZG_EACH_TERMS terms over the table [g | C_0 W_0 | C_1 W_1 ...] and its non-pairing verdict
+int kzg_each_pack_launch(Ctx* c, const uint64_t* points, const plonk_kzg_proof* proofs, const int32_t* kind, uint64_t count,
+                         uint32_t* sc, uint32_t* ids, int32_t* pre);
+// per proof its VERIFY_EACH_TERMS terms from the replay's ProofScalars over the table [15 per slot | g | 11 per proof]
+int verify_each_pack_launch(Ctx* c, const void* proof_scalars, const uint32_t* slot, uint32_t pt_g, uint32_t pt_proof0,
+                            uint64_t count, uint32_t* sc, uint32_t* ids, int32_t* pre);
+// sums[2 k] / sums[2 k + 1] = the L / R sum of item k (nL + nR consecutive terms per item, msm_run's term layout)
+int each_sums_launch(Ctx* c, const uint32_t* sc, const uint32_t* ids, uint32_t nL, uint32_t nR, uint64_t count,
+                     const G1Affine* pts, const int32_t* kind, const int32_t* pre, G1* sums);
+// verdict[k] = pre[k], or for pre[k] == 0: e(-pairs[2 k], x_h) e(pairs[2 k + 1], h) == 1 ? PLONK_OK : PLONK_ERR_VERIFY;
+// values (may be NULL): 72 words per check, the final-exponentiated value as canonical integers
+int pairing_each_launch(Ctx* c, const void* tables, const G1* pairs, const int32_t* pre, uint64_t count, int32_t* verdict,
+                        uint64_t* values);
+int each_finish(Ctx* c, const int32_t* verdict_dev, const int32_t* pre_dev, uint64_t count, int32_t* verdicts, uint32_t* checked,
+                uint32_t* rejected);
 void kzg_ws_release(Ctx* c);                          // kzg.hip: frees the opening workspace of the context
 // msm_points.hip: sum_i s_i P_i over points that are not the commit key, by the bucket method (or, below
 // opts.min_bucket_terms terms, by verify.hip's per-term kernel).  The terms come in one of two layouts:

@@ -256,9 +256,10 @@ struct Verifier {
   G1* part = nullptr;
   uint64_t cap_proofs = 0, cap_terms = 0;
   plonk_verify_info last;
+  void* pair_tables = nullptr;   // the lines of x_h and h for the pairing kernel (pairing.hip), made by the first plonk_verify_each
   ~Verifier() {
     (void)hipFree(pts); (void)hipFree(kind); (void)hipFree(comp);
-    (void)hipFree(sc); (void)hipFree(ids); (void)hipFree(part);
+    (void)hipFree(sc); (void)hipFree(ids); (void)hipFree(part); (void)hipFree(pair_tables);
   }
   int reserve(uint64_t proofs) {
     if (proofs > cap_proofs) {   // the decoded VK points and g ([0, 16)) move to the larger buffers
@@ -465,7 +466,7 @@ static void replay_task(void* arg, int index) {
 // The context's grow-only workspace of mixed calls (Ctx::verify_ws): a call whose sizes fit an earlier one allocates nothing.
 struct MixedWork {
   enum { PTS, KIND, COMP, PROOFS, SLOT, PI_OFF, PI, SLOTS, PI_ROOT, STATUS, SCALARS, DIGEST, WHICH, ORDER, SEG, SEG_PT,
-         WV, GPART, SC, IDS, PART, NBUF };
+         WV, GPART, SC, IDS, PART, E_PRE, E_SUMS, E_VERDICT, NBUF };   // E_*: plonk_verify_each (pairing.hip)
   void* p[NBUF] = {};
   uint64_t cap[NBUF] = {};
   ~MixedWork() {
@@ -911,6 +912,75 @@ int plonk_verify_mixed(plonk_verifier* const* verifiers, uint32_t nverifiers, co
     info->ms_pairing = b.ms_pairing;
   }
   if (rc != PLONK_OK) plonk::set_last_error(api_fn, "proof verification failed (Error::ProofVerificationError)", __FILE__, __LINE__);
+  return rc;
+  });
+}
+
+int plonk_verify_each(plonk_verifier* const* verifiers, uint32_t nverifiers, const uint32_t* circuit, const uint8_t* proofs,
+                      const uint64_t* pi, uint64_t pi_total, uint64_t count, int32_t* verdicts, plonk_verify_info* info) {
+  const char* const api_fn = __func__;
+  return plonk::api_guard(api_fn, [&]() -> int {
+  std::vector<uint32_t> all_first;   // circuit == NULL: every proof belongs to verifiers[0]
+  if (!circuit && count > 0 && count <= (1ull << 24)) {
+    all_first.assign(count, 0);
+    circuit = all_first.data();
+  }
+  if (!circuit && (count == 0 || count > (1ull << 24)))
+    return (plonk::set_last_error(api_fn, "invalid argument: count must be in [1, 2^24]", __FILE__, __LINE__), PLONK_ERR_ARG);
+  PTRY_V(plonk::mixed_args(api_fn, verifiers, nverifiers, circuit, proofs, pi, pi_total, count));
+  if (!verdicts) return (plonk::set_last_error(api_fn, "invalid argument: verdicts is NULL", __FILE__, __LINE__), PLONK_ERR_ARG);
+  if (info) memset(info, 0, sizeof *info);
+  CTX_ENTER(verifiers[0]->ctx->c, api_fn);
+  plonk::MixedState b;
+  b.c = &verifiers[0]->ctx->c;
+  Ctx* c = b.c;
+  HIP_TRY(hipSetDevice(c->device));
+  auto body = [&]() -> int {
+    PTRY_V(plonk::mixed_front(b, verifiers, nverifiers, circuit, proofs, pi, pi_total, count));
+    plonk::Verifier* v0 = verifiers[b.used[0]]->v;   // every verifier of the call has the same (g, h, x_h)
+    PTRY_V(plonk::pairing_tables_create(c, v0->x_h, v0->h, &v0->pair_tables));
+    plonk::MixedWork& w = *b.w;
+    const uint64_t nterms = (uint64_t)plonk::VERIFY_EACH_TERMS * count;
+    PTRY_V(w.need(plonk::MixedWork::SC, 32 * nterms));
+    PTRY_V(w.need(plonk::MixedWork::IDS, 4 * nterms));
+    PTRY_V(w.need(plonk::MixedWork::E_PRE, 4 * count));
+    PTRY_V(w.need(plonk::MixedWork::E_SUMS, sizeof(G1) * 2 * count));
+    PTRY_V(w.need(plonk::MixedWork::E_VERDICT, 4 * count));
+    const auto t0 = std::chrono::steady_clock::now();
+    PTRY_V(plonk::verify_each_pack_launch(c, w.p[plonk::MixedWork::SCALARS], w.at<const uint32_t>(plonk::MixedWork::SLOT), b.pt_g,
+                                          b.pt_proof0, count, w.at<uint32_t>(plonk::MixedWork::SC), w.at<uint32_t>(plonk::MixedWork::IDS),
+                                          w.at<int32_t>(plonk::MixedWork::E_PRE)));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const double ms_pack = plonk::ms_since(t0);
+    const auto t1 = std::chrono::steady_clock::now();
+    PTRY_V(plonk::each_sums_launch(c, w.at<const uint32_t>(plonk::MixedWork::SC), w.at<const uint32_t>(plonk::MixedWork::IDS), 2,
+                                   plonk::VERIFY_EACH_TERMS - 2, count, w.at<const G1Affine>(plonk::MixedWork::PTS),
+                                   w.at<const int32_t>(plonk::MixedWork::KIND), w.at<const int32_t>(plonk::MixedWork::E_PRE),
+                                   w.at<G1>(plonk::MixedWork::E_SUMS)));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const double ms_msm = plonk::ms_since(t1);
+    const auto t2 = std::chrono::steady_clock::now();
+    PTRY_V(plonk::pairing_each_launch(c, v0->pair_tables, w.at<const G1>(plonk::MixedWork::E_SUMS),
+                                      w.at<const int32_t>(plonk::MixedWork::E_PRE), count, w.at<int32_t>(plonk::MixedWork::E_VERDICT),
+                                      nullptr));
+    uint32_t checked = 0, rejected = 0;
+    PTRY_V(plonk::each_finish(c, w.at<const int32_t>(plonk::MixedWork::E_VERDICT), w.at<const int32_t>(plonk::MixedWork::E_PRE), count,
+                              verdicts, &checked, &rejected));
+    if (info) {
+      info->proofs = count;
+      info->msm_terms = (uint64_t)plonk::VERIFY_EACH_TERMS * checked;
+      info->pairing_checks = checked;
+      info->rejected = rejected;
+      info->ms_decode = b.ms_decode;
+      info->ms_scalars = b.ms_replay + ms_pack;
+      info->ms_msm = ms_msm;
+      info->ms_pairing = plonk::ms_since(t2);
+    }
+    return rejected ? PLONK_ERR_VERIFY : PLONK_OK;
+  };
+  const int rc = body();
+  if (rc != PLONK_OK && rc != PLONK_ERR_VERIFY) (void)hipStreamSynchronize(c->stream);   // nothing of the call stays queued
+  if (rc == PLONK_ERR_VERIFY) plonk::set_last_error(api_fn, "proof verification failed (Error::ProofVerificationError)", __FILE__, __LINE__);
   return rc;
   });
 }

@@ -7,7 +7,12 @@ With --circuits C, C circuits of different sizes (2^log_n, 2^(log_n - 1), ...) a
 compiled from one SRS and their proofs interleaved (proof k of circuit k mod C); each K prints a plonk_verify_mixed line
 and, for C = 1, a plonk_verify line on the same batch, the two alternating in this process (best of --reps each).
 
-    python tools/verify_bench.py [--log-n 12] [--ks 1,64,1024,8192] [--reps 3] [--circuits 1]
+With --each, plonk_verify_each (one pairing check per proof on the device) alternates with the other
+calls on every batch, every line carries best / median / max of the repetitions (at least 5, after a warm-up), and four more
+legs run: K = 1024 all valid against all bad (plonk_verify_each; the bisection's all-bad case at K = 256), plonk_kzg_check_each
+against sampled count == 1 plonk_kzg_batch_check calls, and the pairing kernel alone (plonk_kzg_pairing_check_each).
+
+    python tools/verify_bench.py [--log-n 12] [--ks 1,64,1024,8192] [--reps 3] [--circuits 1] [--each]
 """
 import argparse
 import json
@@ -43,7 +48,10 @@ def main():
     ap.add_argument("--ks", default="1,64,1024,8192")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--circuits", type=int, default=1)
+    ap.add_argument("--each", action="store_true")
     args = ap.parse_args()
+    if args.each:
+        args.reps = max(args.reps, 5)
     ks = [int(k) for k in args.ks.split(",")]
     import plonk_amd
     from oracle import bls12_381 as E
@@ -81,24 +89,100 @@ def main():
             v = batch[0][0]
             verdicts = v.verify_batch([p for _, p, _ in batch], [x for _, _, x in batch])
             info = v.last()
+        elif call == "plonk_verify_each":
+            verdicts, info = plonk_amd.verify_each_info(batch)
         else:
             verdicts, info = plonk_amd.verify_mixed(batch)
         return (time.perf_counter() - t) * 1e3, info, verdicts
 
-    def run(batch, label):
-        calls = ["plonk_verify_mixed"] + (["plonk_verify"] if args.circuits == 1 else [])
-        best = {}
-        for _ in range(args.reps):   # the calls alternate, so both see the same state of the machine
+    def spread(times):
+        times = sorted(times)
+        return {"wall_ms": round(times[0], 3), "median_ms": round(times[len(times) // 2], 3), "max_ms": round(times[-1], 3),
+                "reps": len(times)}
+
+    def run(batch, label, calls=None, reps=None):
+        if calls is None:
+            calls = ["plonk_verify_mixed"] + (["plonk_verify"] if args.circuits == 1 else []) + (["plonk_verify_each"] if args.each else [])
+        best, times = {}, {c: [] for c in calls}
+        if args.each:
+            for call in calls:   # warm-up: workspace growth, the lazily made line tables
+                one(batch, call)
+        for _ in range(reps or args.reps):   # the calls alternate, so all see the same state of the machine
             for call in calls:
                 r = one(batch, call)
+                times[call].append(r[0])
                 if call not in best or r[0] < best[call][0]:
                     best[call] = r
         for call in calls:
             ms, info, verdicts = best[call]
             out = {"run": label, "call": call, "circuits": args.circuits, "K": len(batch), "wall_ms": round(ms, 3),
                    "proofs_per_s": round(len(batch) / ms * 1e3, 1), "rejected": sum(v != 0 for v in verdicts)}
+            if args.each:
+                out.update(spread(times[call]))
             out.update({k: (round(v, 3) if isinstance(v, float) else v) for k, v in info.items()})
             print(json.dumps(out), flush=True)
+
+    def flip(item):
+        v, p, x = item
+        b = bytearray(p)
+        b[528:560] = ((int.from_bytes(b[528:560], "little") + 1) % E.Q).to_bytes(32, "little")
+        return v, bytes(b), x
+
+    def each_legs():
+        from tests import kzg_ref as K
+        # the work of plonk_verify_each does not depend on the verdicts: all valid against all bad
+        k = min(1024, kmax)
+        run(items[:k], "all valid", ["plonk_verify_each"])
+        run([flip(it) for it in items[:k]], "all bad", ["plonk_verify_each"])
+        k = min(256, kmax)
+        run([flip(it) for it in items[:k]], "all bad (bisection: 2K - 1 checks)", ["plonk_verify_mixed", "plonk_verify_each"], reps=2)
+        # KZG openings: 64 distinct honest openings of short polynomials, repeated to the count (the work is per item)
+        import random
+        rnd = random.Random(77)
+        key = plonk_amd.KzgKey(ctx, opening_key)
+        points = [rnd.randrange(E.Q) for _ in range(64)]
+        proofs = []
+        for z in points:
+            ev, cm, wit = ctx.kzg_open([[rnd.randrange(E.Q) for _ in range(8)]], z, None)
+            proofs.append(plonk_amd.KzgProof.make(cm[0], ev[0], wit))
+        single = []
+        for z, p in zip(points, proofs):   # 64 count == 1 calls of plonk_kzg_batch_check, scaled to the count below
+            t = time.perf_counter()
+            assert key.batch_check_code([z], [p])[0] == 0
+            single.append((time.perf_counter() - t) * 1e3)
+        single_ms = sorted(single)[len(single) // 2]
+        for count in (64, 1024, 8192):
+            pts, prs = [points[i % 64] for i in range(count)], [proofs[i % 64] for i in range(count)]
+            key.check_each_info(pts, prs)
+            times, info = [], None
+            for _ in range(args.reps):
+                t = time.perf_counter()
+                verdicts, info = key.check_each_info(pts, prs)
+                times.append((time.perf_counter() - t) * 1e3)
+                assert verdicts == [0] * count
+            out = {"run": "kzg", "call": "plonk_kzg_check_each", "count": count, "single_call_median_ms": round(single_ms, 3),
+                   "count_single_calls_ms": round(single_ms * count, 1)}
+            out.update(spread(times))
+            out.update({k: (round(v, 3) if isinstance(v, float) else v) for k, v in info.items()})
+            print(json.dumps(out), flush=True)
+        # the pairing kernel alone: ms_pairing is host wall clock around the kernel and its synchronisation
+        host_ms = plonk_amd.verify_mixed(items[:1])[1]["ms_pairing"]
+        for count in (64, 8192):
+            a = [bytes(proofs[i % 64].witness) for i in range(count)]
+            b = [bytes(proofs[i % 64].commitment) for i in range(count)]
+            key.pairing_check_each_info(a, b)
+            times, wall = [], []
+            for _ in range(args.reps):
+                t = time.perf_counter()
+                _, info = key.pairing_check_each_info(a, b)
+                wall.append((time.perf_counter() - t) * 1e3)
+                times.append(info["ms_pairing"])
+            out = {"run": "pairing kernel", "call": "plonk_kzg_pairing_check_each", "count": count,
+                   "host_pairing_ms": round(host_ms, 3), "count_host_pairings_ms": round(host_ms * count, 1),
+                   "kernel_ms": spread(times)}
+            out.update(spread(wall))
+            print(json.dumps(out), flush=True)
+        key.close()
 
     for k in ks:
         run(items[:k], "valid")
@@ -111,6 +195,8 @@ def main():
         b[528:560] = val.to_bytes(32, "little")
         bad[j] = (v, bytes(b), x)
     run(bad, "one bad per 1024")
+    if args.each:
+        each_legs()
     for prover, verifier, _, _ in circs:
         verifier.close()
         prover.close()
