@@ -9,34 +9,13 @@ import subprocess
 
 import pytest
 
-from msm_wide_model import bit_sums, host_finish
+from msm_wide_model import bit_sums, host_finish, quad_digits
 from oracle import bls12_381 as E
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SO = os.path.join(HERE, "_build", "libhost_msm_quad.so")
 Q = E.Q
 WIDTHS = ((16, 16), (20, 13))            # (digit width, most digits of a scalar)
-
-
-def quad_digits(s: int, w: int):
-    """[(row, d)]: a digit starts at positions p = 0 mod 4 only, where the remaining value (s >> p) + carry is not a multiple
-    of 16; it is w bits wide and signed, d = v - 2^w when v > 2^(w-1); row = p / 4; sum d * 16^row = s.  When more than w and
-    at most 2 w bits remain below bit 256 the last two digits share them in widths that are multiples of 4."""
-    assert w % 4 == 0 and 0 <= s < (1 << 255)
-    out, p, carry = [], 0, 0
-    while (s >> p) + carry:
-        if ((s >> p) + carry) % 16 == 0:
-            p += 4
-            continue
-        rem = 256 - p
-        wd = ((rem // 2 + 3) & ~3) if w < rem <= 2 * w else w
-        v = ((s >> p) & ((1 << wd) - 1)) + carry
-        d = v - (1 << wd) if v > (1 << (wd - 1)) else v
-        carry = 1 if d < 0 else 0
-        out.append((p >> 2, d))
-        p += wd
-    assert sum(d << (4 * r) for r, d in out) == s
-    return out
 
 
 def quad_msm_model(points, scalars, w: int):
