@@ -726,6 +726,56 @@ int plonk_kzg_pairing_check_each(plonk_kzg_key* key, const uint8_t* a48, const u
 int plonk_kzg_check_each(plonk_kzg_key* key, const uint64_t* points /* count x 4 */, const plonk_kzg_proof* proofs, uint64_t count,
                          int32_t* verdicts, plonk_verify_info* info);
 
+/* ---- KZG10 openings over a whole domain ---------------------------------------------------------------
+ * One polynomial opened at EVERY point of its evaluation domain: the n = 2^log_n witnesses pi_i = commit((f - f(w^i)) / (X - w^i))
+ * by group FFTs (Feist-Khovratovich) — O(n log n) scalar multiplications where n calls of plonk_kzg_open cost n MSMs of n terms.
+ * w is the generator plonk_ntt uses for size n.  With s_l = [tau^l] g the commit key and N = 2n:
+ *     A = DFT_N(s_0 .. s_(n-2), O ...) (per handle);  G = NTT_N(f_(n-1), f_(n-2) .. f_1, 0 ...);  P_i = [G_i] A_i;
+ *     c = DFT_N^-1(P);  h_k = c_(n-2-k) (k <= n-2), h_(n-1) = O;  pi = DFT_n(h)                       
+ * plonk_kzg_domain_create: A and the split twiddles for (the context's commit key, log_n): 2n x 256 + n x 32 bytes of device
+ *   memory.  log_n in [1, 20], else PLONK_ERR_ARG; PLONK_ERR_STATE on a context with a communicator (it holds only a range of
+ *   the key, as for plonk_kzg_open); PLONK_ERR_NO_SRS before a key is loaded; PLONK_ERR_DEGREE for a key of fewer than n points.
+ *   The handle remembers the key it was built on: once the context's key is reloaded every call on the handle except
+ *   plonk_kzg_domain_destroy returns PLONK_ERR_STATE.  Destroy the handle before its context.
+ * plonk_kzg_domain_points: out[i] = w^i, i < n (n x 4 limbs, Montgomery): the point witness i and evaluation i belong to.
+ * plonk_kzg_open_domain: `count` polynomials in coefficient form (host pointers; lengths may differ; count <= 65536, else
+ *   PLONK_ERR_ARG; count == 0 is PLONK_OK and writes nothing):
+ *     evaluations[j][i] = p_j(w^i) (count x n x 4 limbs, Montgomery);  witnesses48[j][i] = pi_i of p_j (count x n x 48 bytes,
+ *     compressed G1, encoded on the device: 48 bytes per witness cross PCIe);  commitments48[j] = commit(p_j) (count x 48, NULL
+ *     skips them) through the ordinary commitment path.
+ *   A caller builds plonk_kzg_proof items from the three arrays and hands them to plonk_kzg_check_each / plonk_kzg_batch_check
+ *   with the points of plonk_kzg_domain_points.  Lengths are judged WITHOUT trailing zeros, as plonk_kzg_open judges them: more
+ *   than n is PLONK_ERR_DEGREE; a coefficient that is not a canonical residue is PLONK_ERR_DATA.  A zero or constant polynomial
+ *   has n compressed identities (0xC0 00 ..) as witnesses.  Every check is made before anything is queued or written: an
+ *   error leaves nothing queued and no output touched.  The polynomials are processed in chunks so that the point workspace
+ *   (2n slots of 256 bytes per polynomial of a chunk, owned by the handle, grown on demand) stays under
+ *   workspace_cap_bytes (2 GiB; a chunk of one polynomial is always allowed, and a chunk never exceeds 4096 polynomials).
+ *   The calls leave the context, its tables and its provers as they found them.
+ * plonk_kzg_open_domain_dev: polys_dev is a HOST array of `count` device pointers; the three outputs are device pointers on
+ *   the context's GPU.
+ * plonk_kzg_domain_last: what the last open call on the handle ran as (count == 0 before the first): the tests assert it
+ *   against the plan computed on the host (plonk_amd/csrc/kzg_domain_core.hpp). */
+typedef struct plonk_kzg_domain plonk_kzg_domain;   /* A and the split twiddles for one (commit key, log_n), bound to a context */
+typedef struct plonk_kzg_domain_info {
+  uint32_t log_n;
+  uint32_t chunks;                 /* chunks the polynomials of the last call were processed in */
+  uint64_t count;                  /* polynomials of the last call */
+  uint64_t device_bytes;           /* device memory the handle holds: A, twiddles and its workspace */
+  uint64_t workspace_cap_bytes;    /* the cap on the point workspace */
+  uint64_t chunk_polys;            /* polynomials per chunk (the last chunk may be shorter) */
+  uint64_t stage_launches;         /* group-FFT stage launches: (2 log_n + 1) per chunk */
+  uint64_t scalar_muls;            /* full-width scalar multiplications issued: 2n pointwise + the butterflies whose twiddle is not 1 */
+} plonk_kzg_domain_info;
+int plonk_kzg_domain_create(plonk_ctx* ctx, uint32_t log_n, plonk_kzg_domain** out);
+void plonk_kzg_domain_destroy(plonk_kzg_domain* domain);
+int plonk_kzg_domain_points(plonk_kzg_domain* domain, uint64_t* out /* n x 4, Montgomery: w^i */);
+int plonk_kzg_open_domain(plonk_kzg_domain* domain, const uint64_t* const* polys, const uint64_t* lens, uint64_t count,
+                          uint64_t* evaluations /* count x n x 4 */, uint8_t* witnesses48 /* count x n x 48 */,
+                          uint8_t* commitments48 /* count x 48, or NULL */);
+int plonk_kzg_open_domain_dev(plonk_kzg_domain* domain, const void* const* polys_dev, const uint64_t* lens, uint64_t count,
+                              void* evaluations_dev, void* witnesses48_dev, void* commitments48_dev /* or NULL */);
+int plonk_kzg_domain_last(plonk_kzg_domain* domain, plonk_kzg_domain_info* out);
+
 /* ---- variable-base MSM over caller-supplied points ------------------------------------------------
  * sum_i scalars[i] * P_i for points the CALLER brings — the reference's msm_variable_base (the primitive under Proof::verify
  * and OpeningKey::batch_check) — where plonk_msm / _batch / _dev run over the loaded commit key and its precomputed tables.

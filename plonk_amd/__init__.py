@@ -9,6 +9,8 @@ libplonk_hip.so (include/plonk_hip.h):
   Context.msm / commit   CommitKey::commit -> msm_variable_base (key.rs:376-388)
   Context.kzg_open / kzg_flatten, KzgKey.batch_check   compute_aggregate_witness + commit, AggregateProof::flatten,
                      OpeningKey::batch_check (key.rs:394-417, 661-707; proof.rs:69-109)
+  KzgDomain.open     the n witnesses, n evaluations and the commitment of a polynomial over a whole evaluation domain
+                     (open_single at every root of unity, by group FFTs)
 
 There is NO CPU fallback: if the HIP library or a GPU is missing every call
 raises.  Nothing in this package imports `oracle/`.
@@ -71,6 +73,8 @@ EXPORTS = [
     "plonk_prover_fill_inputs", "plonk_prover_prove_inputs", "plonk_prover_diagnose_inputs",
     "plonk_msm_points", "plonk_msm_points_dev", "plonk_ctx_last_msm_points",
     "plonk_kzg_pairing_check_each", "plonk_kzg_check_each", "plonk_verify_each",
+    "plonk_kzg_domain_create", "plonk_kzg_domain_destroy", "plonk_kzg_domain_points", "plonk_kzg_open_domain",
+    "plonk_kzg_open_domain_dev", "plonk_kzg_domain_last",
 ]
 
 # what bit f of plonk_unsat_row.families / slot f of plonk_unsat_info.family_rows stands for (include/plonk_hip.h); the
@@ -137,6 +141,13 @@ class _MsmPointsInfo(ctypes.Structure):
     _fields_ = [("path", ctypes.c_uint32), ("window_bits", ctypes.c_uint32), ("windows", ctypes.c_uint32),
                 ("slice_entries", ctypes.c_uint32), ("terms", ctypes.c_uint64), ("nonzero_digits", ctypes.c_uint64),
                 ("slices", ctypes.c_uint64), ("longest_bucket", ctypes.c_uint64)]
+
+
+class _KzgDomainInfo(ctypes.Structure):
+    """plonk_kzg_domain_info (include/plonk_hip.h)"""
+    _fields_ = [("log_n", ctypes.c_uint32), ("chunks", ctypes.c_uint32), ("count", ctypes.c_uint64),
+                ("device_bytes", ctypes.c_uint64), ("workspace_cap_bytes", ctypes.c_uint64), ("chunk_polys", ctypes.c_uint64),
+                ("stage_launches", ctypes.c_uint64), ("scalar_muls", ctypes.c_uint64)]
 
 
 class _ProverInfo(ctypes.Structure):
@@ -399,6 +410,14 @@ def load_library() -> ctypes.CDLL:
     lib.plonk_msm_points.argtypes = [vp, vp, vp, u64, ctypes.POINTER(_MsmPointsOpts), vp]
     lib.plonk_msm_points_dev.argtypes = [vp, vp, vp, u64, ctypes.POINTER(_MsmPointsOpts), vp]
     lib.plonk_ctx_last_msm_points.argtypes = [vp, ctypes.POINTER(_MsmPointsInfo)]
+    lib.plonk_kzg_domain_create.argtypes = [vp, u32, ctypes.POINTER(vp)]
+    lib.plonk_kzg_domain_destroy.argtypes = [vp]
+    lib.plonk_kzg_domain_destroy.restype = None
+    lib.plonk_kzg_domain_points.argtypes = [vp, vp]
+    lib.plonk_kzg_open_domain.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(u64), u64, vp, vp, vp]
+    lib.plonk_kzg_open_domain_dev.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(u64), u64, vp, vp, vp]
+    lib.plonk_kzg_domain_last.argtypes = [vp, ctypes.POINTER(_KzgDomainInfo)]
+    lib.plonk_test_kzg_domain_set_cap.argtypes = [vp, u64]   # test hook of kzg_domain.hip, not in the header
     _lib = lib
     return lib
 
@@ -1550,6 +1569,79 @@ class KzgKey:
         if getattr(self, "handle", None):
             if getattr(self.ctx, "handle", None):
                 self.ctx.lib.plonk_kzg_key_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class KzgDomain:
+    """plonk_kzg_domain: the commit key of `ctx` prepared for openings at EVERY point of the size-2^log_n domain (group FFTs,
+    include/plonk_hip.h).  `open` returns per polynomial its n evaluations and n witnesses; witness i and evaluation i belong
+    to `points()[i]`.  Destroyed before its context, like a KzgKey."""
+
+    def __init__(self, ctx: Context, log_n: int):
+        self.ctx, self.log_n, self.n = ctx, log_n, 1 << max(log_n, 0)
+        h = ctypes.c_void_p()
+        ctx._check(ctx.lib.plonk_kzg_domain_create(ctx.handle, log_n, ctypes.byref(h)))
+        self.handle = h
+        ctx._provers.add(self)
+
+    def points(self) -> list:
+        out = ctypes.create_string_buffer(32 * self.n)
+        self.ctx._check(self.ctx.lib.plonk_kzg_domain_points(self.handle, out))
+        return fr_from_bytes_mont(out.raw)
+
+    def open_bytes(self, polys_bytes, commitments: bool = True):
+        """plonk_kzg_open_domain on Montgomery bytes (32 per coefficient) -> (evaluation bytes, witness bytes, commitment
+        bytes or None), each the concatenation over the polynomials"""
+        bufs = [bytes(b) for b in polys_bytes]
+        count = len(bufs)
+        keep = [ctypes.create_string_buffer(b, len(b)) if b else None for b in bufs]
+        parr = (ctypes.c_void_p * max(count, 1))(*[ctypes.cast(k, ctypes.c_void_p).value if k is not None else None for k in keep])
+        larr = (ctypes.c_uint64 * max(count, 1))(*[len(b) // 32 for b in bufs])
+        ev = ctypes.create_string_buffer(max(32 * self.n * count, 1))
+        wit = ctypes.create_string_buffer(max(48 * self.n * count, 1))
+        cm = ctypes.create_string_buffer(max(48 * count, 1)) if commitments else None
+        self.ctx._check(self.ctx.lib.plonk_kzg_open_domain(self.handle, parr, larr, count, ev, wit, cm))
+        return ev.raw[:32 * self.n * count], wit.raw[:48 * self.n * count], cm.raw[:48 * count] if commitments else None
+
+    def open(self, polys, commitments: bool = True):
+        """polys: coefficient lists of ints, or Montgomery bytes -> (evaluations[j][i], witnesses[j][i] (48 bytes each),
+        commitments[j] or None)"""
+        bufs = [p if isinstance(p, (bytes, bytearray)) else fr_to_bytes_mont(p) for p in polys]
+        ev, wit, cm = self.open_bytes(bufs, commitments)
+        n, count = self.n, len(bufs)
+        evs = fr_from_bytes_mont(ev)
+        return ([evs[j * n:(j + 1) * n] for j in range(count)],
+                [[wit[48 * (j * n + i):48 * (j * n + i + 1)] for i in range(n)] for j in range(count)],
+                [cm[48 * j:48 * j + 48] for j in range(count)] if commitments else None)
+
+    def open_dev(self, ptrs, lens, evaluations: int, witnesses: int, commitments: "int | None" = None):
+        """plonk_kzg_open_domain_dev: polynomials resident in HBM (device pointers, coefficients each); the outputs are device
+        pointers (count x n x 32, count x n x 48, count x 48 bytes or None)"""
+        ptrs, lens = list(ptrs), list(lens)
+        count = len(lens)
+        parr = (ctypes.c_void_p * max(count, 1))(*ptrs)
+        larr = (ctypes.c_uint64 * max(count, 1))(*lens)
+        self.ctx._check(self.ctx.lib.plonk_kzg_open_domain_dev(self.handle, parr, larr, count, evaluations, witnesses, commitments))
+
+    def last(self) -> dict:
+        info = _KzgDomainInfo()
+        self.ctx._check(self.ctx.lib.plonk_kzg_domain_last(self.handle, ctypes.byref(info)))
+        return {k: getattr(info, k) for k, _ in info._fields_}
+
+    def _set_workspace_cap(self, nbytes: int):
+        """TEST HOOK: the cap on the point workspace (0 = default), to force several chunks.  Not part of the C API."""
+        self.ctx._check(self.ctx.lib.plonk_test_kzg_domain_set_cap(self.handle, nbytes))
+
+    def close(self):
+        if getattr(self, "handle", None):
+            if getattr(self.ctx, "handle", None):
+                self.ctx.lib.plonk_kzg_domain_destroy(self.handle)
             self.handle = None
 
     def __del__(self):

@@ -1,0 +1,30 @@
+// Launchers of kzg_domain.hip: the batched group transform on XYZZ slots and the kernels around it.  Shared with the doors of
+// the per-kernel tests (tests/csrc/dev_kzg_domain.hip).  Every pointer is device memory, everything is queued on the
+// context's stream, nothing synchronises.  A "slot" is one XYZZ point over Fp28, KZD_SLOT_BYTES (256) bytes, 16-byte aligned;
+// polynomial b of a batch lives at slots + b * stride (in slots).
+#pragma once
+#include "plonk_internal.hpp"
+#include "curve28.cuh"
+#include "kzg_domain_core.hpp"
+
+namespace plonk {
+
+// w^e as GLV halves, e < 2^(tw_log - 1), w the 2^tw_log-th root of unity plonk_ntt uses; the caller frees *out_dev (hipFree)
+int kzd_twiddles_create(Ctx* c, uint32_t tw_log, GlvScalar** out_dev);
+// size 2^size_log per polynomial, `batch` polynomials (grid.y); tw: a table of kzd_twiddles_create for tw_log >= size_log.
+// forward: decimation in frequency, natural order in, bit-reversed out.  inverse: decimation in time, bit-reversed in, natural
+// out, WITHOUT the 1/size factor.  stage_launches / scalar_muls (may be NULL) are added to.
+int kzd_transform(Ctx* c, void* slots, uint64_t stride, uint32_t size_log, uint32_t batch, bool inverse, const GlvScalar* tw,
+                  uint32_t tw_log, uint64_t* stage_launches, uint64_t* scalar_muls);
+// out[b][p] = [G[b][rev(p)] * scale] A[p], p < 2^size_log (A is shared by the batch; a zero scalar gives the identity)
+int kzd_pointwise(Ctx* c, const void* A, const Fr* G, uint64_t g_stride, void* out_slots, uint64_t stride, uint32_t size_log,
+                  uint32_t batch, const Fr& scale);
+// slots[b][n + k] = slots[b][n - 2 - k] for k <= n - 2, the identity for k = n - 1 (n = 2^log_n, 2n slots per polynomial)
+int kzd_extract(Ctx* c, void* slots, uint64_t stride, uint32_t log_n, uint32_t batch);
+// out48[b][i] = the 48-byte compressed encoding of slots[b][offset + (bitrev ? rev(i) : i)], i < 2^log_n
+int kzd_finish(Ctx* c, const void* slots, uint64_t stride, uint64_t offset, uint32_t log_n, uint32_t batch, bool bitrev,
+               uint8_t* out48);
+// slots[i] = the affine point xy96[i] (Montgomery x || y, 96 zero bytes = the identity), i < count
+int kzd_load_raw(Ctx* c, const G1Affine* xy96, uint64_t count, void* slots);
+
+}  // namespace plonk
