@@ -260,8 +260,7 @@ __global__ void __launch_bounds__(BI_T) batch_inverse_kernel(Fr* __restrict__ v,
 // ---------------------------------------------------------------------------
 // scans over Fr with op = mul (prefix products) or add (suffix sums), 3 phases
 // ---------------------------------------------------------------------------
-static constexpr int SCAN_T = 256;
-static constexpr int SCAN_E = 8;
+static constexpr int SCAN_E = 8;   // (SCAN_T, SCAN_MAXPER: poly.hpp)
 static constexpr int SCAN_BLOCK = SCAN_T * SCAN_E;
 
 template <bool MUL>
@@ -314,7 +313,6 @@ __global__ void __launch_bounds__(SCAN_T) scan_block_kernel(Fr* __restrict__ dat
 
 // single-block inclusive scan of the block totals (nb <= SCAN_T * SCAN_MAXPER); each thread owns
 // a contiguous run of `per` totals.
-static constexpr int SCAN_MAXPER = 64;
 template <bool MUL>
 __global__ void __launch_bounds__(SCAN_T) scan_totals_kernel(Fr* __restrict__ totals, uint32_t nb, uint32_t per) {
   __shared__ Fr sh[SCAN_T];

@@ -162,6 +162,11 @@ void quotient_data(const Fr& c, uint32_t out[9]);
 int poly_eval(Ctx* c, EvalArgs& a, int count, uint64_t max_len, Fr* out_dev);
 int poly_lincomb(Ctx* c, const LinCombArgs& a);
 int poly_ruffini(Ctx* c, const Fr* src, Fr* dst, uint64_t len, const Fr& z, const Fr& zinv, Fr* scratch, Fr* totals);
+// The scans (and poly_ruffini, which runs one) leave their block totals in `totals`: SCAN_TOTALS elements, a buffer per
+// stream that scans.  Workgroups of SCAN_T lanes; one of them scans the totals, SCAN_MAXPER per lane at the most.
+static constexpr int SCAN_T = 256;
+static constexpr int SCAN_MAXPER = 64;
+static constexpr uint64_t SCAN_TOTALS = SCAN_T * SCAN_MAXPER + 1;
 int scan_prefix_product(Ctx* c, Fr* data, uint64_t n, Fr* totals);
 // the same scan in two steps for a RANGE of a longer product (sharded grand product): _local leaves the inclusive products of
 // the range's blocks in totals (the range's own product, twiddle form, at totals[scan_prefix_blocks(n) - 1]); _apply multiplies

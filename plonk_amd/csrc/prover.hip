@@ -111,6 +111,7 @@ struct Prover {
   Fr* wscal = nullptr;             // [11] the wire blinders (8) and z's (3) on the device: tail scalars of the Lagrange-key MSMs
   Fr* agg2 = nullptr;              // [np] second linear combination (W_zw numerator)
   Fr* scratch2 = nullptr;          // [np + 1]
+  Fr* totals2 = nullptr;           // scan block totals of the side stream (W_zw's division on one GPU)
   plonk_allgather_fn allgather = nullptr;
   void* allgather_user = nullptr;
   Fr* ev_host = nullptr;           // pinned 16 Fr
@@ -389,7 +390,7 @@ static void prover_free(Prover* p) {
                   p->tparts, p->agg, p->wit, p->wit2, p->scratch, p->totals, p->evpart, p->evout, p->res, p->len_dev,
                   p->flag_dev, p->pi_idx_dev, p->pi_val_dev};
   for (void* b : bufs) if (b) (void)hipFree(b);
-  for (void* b : {(void*)p->fold, (void*)p->Fbuf, (void*)p->send, (void*)p->recv, (void*)p->agg2, (void*)p->scratch2, (void*)p->wscal}) if (b) (void)hipFree(b);
+  for (void* b : {(void*)p->fold, (void*)p->Fbuf, (void*)p->send, (void*)p->recv, (void*)p->agg2, (void*)p->scratch2, (void*)p->totals2, (void*)p->wscal}) if (b) (void)hipFree(b);
   srs_table_release(p->c, p->lag_table, p->lag_rows, p->lag_n);   // gives the bytes back to the context's table budget
   for (void* b : {(void*)p->wire_idx, (void*)p->wit_vals, (void*)p->diag_sel, (void*)p->diag_pos}) if (b) (void)hipFree(b);
   composer_program_free(p->program);
@@ -560,7 +561,8 @@ static int prover_build(Ctx* c, const plonk_prover_desc* d, const CircuitSrc* ci
   ALLOC(p->wit, np);
   ALLOC(p->wit2, np);
   ALLOC(p->scratch, 2 * np);
-  ALLOC(p->totals, 256 * 64 + 1);   // scan block totals (poly.hip: SCAN_T * SCAN_MAXPER)
+  ALLOC(p->totals, SCAN_TOTALS);
+  ALLOC(p->totals2, SCAN_TOTALS);
   p->ev_max_blocks = (uint32_t)((np + 1023) / 1024);   // poly_eval: 2^10 coefficients per workgroup for small polynomials, 2^12 above
   ALLOC(p->evpart, 16 * (uint64_t)p->ev_max_blocks);
   ALLOC(p->evout, 16);
@@ -843,7 +845,6 @@ static bool quotient_identity_holds(const Fr& numerator_at_z, const Evals& ev, c
   for (int k = 0; k < 11; ++k) expect = expect + vp[k + 1] * *evs[k];
   return numerator_at_z == expect;
 }
-// the sparse public inputs -> dense evaluation vector -> PI(X) in coefficient form, on the current stream
 // the sparse public inputs on the device (p->pi_idx_dev / pi_val_dev), on the current stream
 static int public_input_stage(Prover* p, const uint64_t* pi_idx, const Fr* pi_val, uint64_t pi_count) {
   Ctx* c = p->c;
@@ -859,11 +860,237 @@ static int public_input_stage(Prover* p, const uint64_t* pi_idx, const Fr* pi_va
   HIP_TRY(hipMemcpyAsync(p->pi_val_dev, pi_val, sizeof(Fr) * pi_count, hipMemcpyHostToDevice, c->stream));
   return PLONK_OK;
 }
-static int public_input_polynomial(Prover* p, const uint64_t* pi_idx, const Fr* pi_val, uint64_t pi_count, Fr* ntt_tmp) {
+// the sparse public inputs -> dense evaluation vector -> PI(X) in coefficient form, on the current stream, and its lowest
+// coefficients for quotient_low (ev_pi).  *pi_len: n, or left at 0 without public inputs (PI(X) = 0)
+static int public_input_polynomial(Prover* p, const uint64_t* pi_idx, const Fr* pi_val, uint64_t pi_count, Fr* ntt_tmp, uint64_t* pi_len) {
   Ctx* c = p->c;
-  PTRY(public_input_stage(p, pi_idx, pi_val, pi_count));
-  PTRY(poly_scatter_pi(c, p->pipoly, p->pi_idx_dev, p->pi_val_dev, pi_count));
-  return ntt_device(c, p->pipoly, p->pipoly, ntt_tmp, p->logn, true, false, p->n);
+  PTRY(poly_fill_zero(c, p->pipoly, p->np));
+  if (pi_count) {
+    PTRY(public_input_stage(p, pi_idx, pi_val, pi_count));
+    PTRY(poly_scatter_pi(c, p->pipoly, p->pi_idx_dev, p->pi_val_dev, pi_count));
+    PTRY(ntt_device(c, p->pipoly, p->pipoly, ntt_tmp, p->logn, true, false, p->n));
+    *pi_len = p->n;
+  }
+  HIP_TRY(hipMemcpyAsync(p->low_host + 35, p->pipoly, 7 * sizeof(Fr), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipEventRecord(p->ev_pi, c->stream));
+  return PLONK_OK;
+}
+// a commitment group reaches the transcript: fetch_commitments, then each under its label (prover.rs:462-465,498,570-573)
+static int absorb_commitments(Prover* p, Transcript& tr, int first, int count, uint8_t (*comm)[48]) {
+  static const char* const label[9] = {"a_comm", "b_comm", "c_comm", "d_comm", "z_comm",
+                                       "t_low_comm", "t_mid_comm", "t_high_comm", "t_fourth_comm"};
+  PTRY(fetch_commitments(p, first, count, comm + first));
+  for (int k = first; k < first + count; ++k) tr.append_commitment(label[k], comm[k]);
+  return PLONK_OK;
+}
+
+// ---- the steps of the five rounds that both paths run.  Launches go to the CURRENT stream.  Rounds 4-5 of a rank work on
+// the coefficient range [lo, hi) of every polynomial; one GPU passes lo = 0 and hi = np, which clamps nothing.
+struct Challenges {   // filled as the transcript produces them
+  Fr beta, gamma;                                   // round 2
+  Fr alpha, range_ch, logic_ch, fixed_ch, var_ch;   // round 3
+};
+static uint64_t own_len(uint64_t len, uint64_t lo, uint64_t hi) {   // coefficients of a length-`len` polynomial inside [lo, hi)
+  const uint64_t e = len < hi ? len : hi;
+  return e > lo ? e - lo : 0;
+}
+// iNTT + blinding of the wire columns k0 .. k1 - 1 and their lowest coefficients (quotient_low)
+static int wire_polynomials(Prover* p, const Fr* wires_dev, const Fr* bl, Fr* ntt_tmp, int k0, int k1) {
+  Ctx* c = p->c;
+  const uint64_t n = p->n, np = p->np;
+  prof_begin(c, 4);   // slot 4: the polynomial work of rounds 1-2 (replicated on every rank of a multi-GPU run)
+  for (int k = k0; k < k1; ++k) {
+    Fr* wp = p->wpoly + k * np;
+    if (p->wires_pending) HIP_TRY(hipStreamWaitEvent(c->stream, p->ev_wire[k], 0));   // column k has arrived
+    PTRY(ntt_device(c, wires_dev + k * n, wp, ntt_tmp, p->logn, true, false, n));
+    BlindArgs ba;
+    ba.count = 2;
+    ba.b[0] = bl[2 * k];
+    ba.b[1] = bl[2 * k + 1];
+    PTRY(poly_fill_zero(c, wp + n, np - n));
+    PTRY(poly_blind(c, wp, n, ba));
+  }
+  prof_end(c, 4);
+  for (int k = k0; k < k1; ++k)
+    HIP_TRY(hipMemcpyAsync(p->low_host + 7 * k, p->wpoly + k * np, 7 * sizeof(Fr), hipMemcpyDeviceToHost, c->stream));
+  return PLONK_OK;
+}
+// the grand product's terms (permutation.rs:213-294) over all n evaluation indices: a rank that takes a share sets first / count
+static PermArgs perm_args(const Prover* p, const Fr* wires_dev, const Challenges& ch, const NttTables* tbn) {
+  const uint32_t L = p->logn;
+  PermArgs pa;
+  pa.n = p->n;
+  for (int k = 0; k < 4; ++k) { pa.wires[k] = wires_dev + k * p->n; pa.sigma[k] = p->sigma_n + k * p->n; }
+  pa.beta = ch.beta; pa.gamma = ch.gamma;
+  pa.ks[0] = Fr::one(); pa.ks[1] = fr_small(7); pa.ks[2] = fr_small(13); pa.ks[3] = fr_small(17);
+  pa.tw_lo29 = tbn->tw_lo29; pa.tw_hi29 = tbn->tw_hi29; pa.lobits = L < 13 ? L : 13; pa.use_hi = L > 13;
+  pa.num = p->scratch; pa.den = p->scratch + p->np;
+  return pa;
+}
+// z(X) in coefficient form from its n evaluations: inverse transform, blinded with bl[8..10]
+static int blind_z(Prover* p, const Fr* evals, const Fr* bl, Fr* ntt_tmp) {
+  Ctx* c = p->c;
+  const uint64_t n = p->n;
+  PTRY(ntt_device(c, evals, p->zpoly, ntt_tmp, p->logn, true, false, n));
+  BlindArgs ba;
+  ba.count = 3;
+  ba.b[0] = bl[8]; ba.b[1] = bl[9]; ba.b[2] = bl[10];
+  PTRY(poly_fill_zero(c, p->zpoly + n, p->np - n));
+  return poly_blind(c, p->zpoly, n, ba);
+}
+// everything of the point-wise quotient pass (quotient_poly.rs:20-137) that does not depend on the residue class: the 6 + 17
+// evaluation arrays (column stride qn) from element `off` on, the challenges and their constants.  n8, rot, k.vinv and out
+// are the caller's.
+static QuotientArgs quotient_args(const Prover* p, const Challenges& ch, uint64_t off, uint64_t pi_len) {
+  const uint64_t qn = p->qn;
+  QuotientArgs q;
+  const Fr* co = p->cos + off;
+  q.z = co; q.a = co + qn; q.b = co + 2 * qn; q.c = co + 3 * qn; q.d = co + 4 * qn; q.pi = pi_len ? co + 5 * qn : nullptr;
+  const Fr* e = p->evals8 + off;
+  q.q_m = e + P_QM * qn; q.q_l = e + P_QL * qn; q.q_r = e + P_QR * qn; q.q_o = e + P_QO * qn; q.q_f = e + P_QF * qn;
+  q.q_c = e + P_QC * qn; q.q_arith = e + P_QARITH * qn; q.q_range = e + P_QRANGE * qn; q.q_logic = e + P_QLOGIC * qn;
+  q.q_fixed = e + P_QFIXED * qn; q.q_var = e + P_QVAR * qn;
+  q.s1 = e + P_S1 * qn; q.s2 = e + P_S2 * qn; q.s3 = e + P_S3 * qn; q.s4 = e + P_S4 * qn;
+  q.linear = e + P_COUNT * qn; q.l1 = e + (P_COUNT + 1) * qn;
+  for (int s = 0; s < QS_COUNT; ++s) q.has[s] = p->has[s];
+  q.range_ch = ch.range_ch; q.logic_ch = ch.logic_ch; q.fixed_ch = ch.fixed_ch; q.var_ch = ch.var_ch;
+  q.edwards_d = p->edwards_d;
+  q.inv32 = p->inv32;
+  quotient_data(ch.gamma, q.k.gamma);
+  quotient_data(Fr::one(), q.k.one);
+  const Fr ks[4] = {Fr::one(), fr_small(7), fr_small(13), fr_small(17)};
+  for (int k = 0; k < 4; ++k) quotient_const(ch.beta * ks[k], 0, q.k.beta_k[k]);
+  quotient_const(ch.alpha, 20, q.k.alpha_pos);
+  quotient_const(ch.alpha.neg(), 20, q.k.alpha_neg);
+  quotient_const(ch.alpha.sqr(), 0, q.k.alpha_sq);
+  return q;
+}
+// what quotient_low needs for the 7 lowest coefficients of t (the 4n quotient domain's de-aliasing, widgets.hpp)
+static QuotientLowIn quotient_low_in(const Prover* p, const Challenges& ch) {
+  QuotientLowIn qi;
+  qi.low = p->low_host;
+  qi.alpha = ch.alpha; qi.beta = ch.beta; qi.gamma = ch.gamma;
+  qi.range_ch = ch.range_ch; qi.logic_ch = ch.logic_ch; qi.fixed_ch = ch.fixed_ch; qi.var_ch = ch.var_ch;
+  qi.edwards_d = p->edwards_d; qi.omega = p->omega; qi.n_inv = p->n_inv;
+  return qi;
+}
+// round 4 (prover.rs:591-676): the 15 evaluations, in the order unpack_evals reads them; items 4-6 and 14 at z omega.
+// Returns the longest clamped length.
+static uint64_t eval_items(const Prover* p, const Fr& z_ch, const Fr& zw, uint64_t lo, uint64_t hi, EvalArgs* ea) {
+  const uint64_t n = p->n, np = p->np;
+  ea->partial = p->evpart;
+  ea->max_blocks = p->ev_max_blocks;
+  const Fr* P = p->polys;
+  const Fr* pol[15] = {p->wpoly, p->wpoly + np, p->wpoly + 2 * np, p->wpoly + 3 * np,
+                       p->wpoly, p->wpoly + np, p->wpoly + 3 * np,
+                       P + P_QARITH * np, P + P_QC * np, P + P_QL * np, P + P_QR * np,
+                       P + P_S1 * np, P + P_S2 * np, P + P_S3 * np, p->zpoly};
+  const uint64_t len[15] = {n + 2, n + 2, n + 2, n + 2, n + 2, n + 2, n + 2,
+                            p->poly_len[P_QARITH], p->poly_len[P_QC], p->poly_len[P_QL], p->poly_len[P_QR],
+                            p->poly_len[P_S1], p->poly_len[P_S2], p->poly_len[P_S3], n + 3};
+  uint64_t max_len = 1;
+  for (int k = 0; k < 15; ++k) {
+    ea->items[k].poly = pol[k] + lo;
+    ea->items[k].len = own_len(len[k], lo, hi);
+    ea->items[k].x = (k >= 4 && k <= 6) || k == 14 ? zw : z_ch;
+    if (ea->items[k].len > max_len) max_len = ea->items[k].len;
+  }
+  return max_len;
+}
+static Evals unpack_evals(const Fr* h) {
+  Evals ev;
+  ev.a = h[0]; ev.b = h[1]; ev.c = h[2]; ev.d = h[3]; ev.a_w = h[4]; ev.b_w = h[5]; ev.d_w = h[6];
+  ev.q_arith = h[7]; ev.q_c = h[8]; ev.q_l = h[9]; ev.q_r = h[10]; ev.s1 = h[11]; ev.s2 = h[12]; ev.s3 = h[13]; ev.z = h[14];
+  return ev;
+}
+// round 5 (prover.rs:678-739): the host scalars of the two openings
+struct Opening {
+  Fr z_n, zh;               // z^n, z^n - 1 (evaluate_vanishing_polynomial)
+  Fr inv_z, inv_zm1;        // 1/z, 1/(z - 1)
+  Fr l1_z;                  // evaluate_all_lagrange_coefficients(z)[0]
+  Fr lin_a, lin_b;          // permutation linearisation scalars (permutation/proverkey.rs:127-269)
+  Fr c_range, c_logic, c_fixed, c_var;
+  Fr nzh;                   // z_h_eval = -(z^n - 1)
+  Fr vp[12];                // v^0 .. v^11
+  Fr pi_eval;
+};
+// ... in two steps, because W_zw needs nothing but the first: one GPU queues it on the side stream before the host goes on
+// with the second.  1/z and 1/(z - 1) come from one shared inversion.
+static int opening_point(const Prover* p, const Fr& z_ch, const Fr& zw, Opening* op) {
+  const Fr one = Fr::one();
+  if (z_ch.is_zero() || zw.is_zero()) return PLONK_ERR_STATE;   // probability 2^-255; (X - 0) division is a shift — not worth a code path
+  op->z_n = z_ch.pow_u64(p->n);
+  op->zh = op->z_n - one;
+  const Fr zm1 = z_ch - one;
+  const Fr b = zm1.is_zero() ? one : zm1;
+  const Fr iab = fr_inv_gcd(z_ch * b);
+  op->inv_z = iab * b;
+  op->inv_zm1 = iab * z_ch;
+  return PLONK_OK;
+}
+static void opening_scalars(const Prover* p, const Evals& ev, const Challenges& ch, const Fr& z_ch, const Fr& v,
+                            const uint64_t* pi_idx, const Fr* pi_val, uint64_t pi_count, Opening* op) {
+  const Fr one = Fr::one();
+  const Fr &beta = ch.beta, &gamma = ch.gamma, &alpha = ch.alpha;
+  op->pi_eval = public_input_eval(p, pi_idx, pi_val, pi_count, z_ch, op->zh);
+  const Fr bz = beta * z_ch;
+  op->lin_a = (ev.a + bz + gamma) * (ev.b + fr_small(7) * bz + gamma) * (ev.c + fr_small(13) * bz + gamma) *
+              (ev.d + fr_small(17) * bz + gamma) * alpha;
+  op->lin_b = (ev.a + beta * ev.s1 + gamma) * (ev.b + beta * ev.s2 + gamma) * (ev.c + beta * ev.s3 + gamma) *
+              (beta * ev.z) * alpha;
+  if (op->z_n == one) op->l1_z = (z_ch == one) ? one : Fr::zero();
+  else op->l1_z = op->zh * p->n_inv * op->inv_zm1;
+  op->c_range = range_identity(ch.range_ch, ev) * ch.range_ch;
+  op->c_logic = logic_identity(ch.logic_ch, ev) * ch.logic_ch;
+  op->c_fixed = fixed_identity(ch.fixed_ch, ev, p->edwards_d) * ch.fixed_ch;
+  op->c_var = var_identity(ch.var_ch, ev, p->edwards_d) * ch.var_ch;
+  op->nzh = op->zh.neg();
+  op->vp[0] = one;
+  for (int k = 1; k < 12; ++k) op->vp[k] = op->vp[k - 1] * v;
+}
+// W_z numerator = r + v a + v^2 b + v^3 c + v^4 d + v^5 s1 + v^6 s2 + v^7 s3 + v^8 q_arith + v^9 q_c
+//                 + v^10 q_l + v^11 q_r  (prover.rs:706-726) with r expanded into its terms
+static void numerator_terms(const Prover* p, const Evals& ev, const Challenges& ch, const Opening& op, const Fr* t4, uint64_t t4_len,
+                            uint64_t lo, uint64_t hi, LinCombArgs* la) {
+  const uint64_t n = p->n, np = p->np;
+  const Fr* P = p->polys;
+  const Fr* vp = op.vp;
+  int k = 0;
+  auto term = [&](const Fr* ptr, uint64_t len, const Fr& s) { la->t[k].p = ptr + lo; la->t[k].len = own_len(len, lo, hi); la->t[k].s = s; ++k; };
+  term(P + P_QM * np, p->poly_len[P_QM], ev.q_arith * ev.a * ev.b);
+  term(P + P_QL * np, p->poly_len[P_QL], ev.q_arith * ev.a + vp[10]);
+  term(P + P_QR * np, p->poly_len[P_QR], ev.q_arith * ev.b + vp[11]);
+  term(P + P_QO * np, p->poly_len[P_QO], ev.q_arith * ev.c);
+  term(P + P_QF * np, p->poly_len[P_QF], ev.q_arith * ev.d);
+  term(P + P_QC * np, p->poly_len[P_QC], ev.q_arith + vp[9]);
+  term(P + P_QARITH * np, p->poly_len[P_QARITH], vp[8]);
+  term(P + P_QRANGE * np, p->poly_len[P_QRANGE], op.c_range);
+  term(P + P_QLOGIC * np, p->poly_len[P_QLOGIC], op.c_logic);
+  term(P + P_QFIXED * np, p->poly_len[P_QFIXED], op.c_fixed);
+  term(P + P_QVAR * np, p->poly_len[P_QVAR], op.c_var);
+  term(P + P_S1 * np, p->poly_len[P_S1], vp[5]);
+  term(P + P_S2 * np, p->poly_len[P_S2], vp[6]);
+  term(P + P_S3 * np, p->poly_len[P_S3], vp[7]);
+  term(P + P_S4 * np, p->poly_len[P_S4], op.lin_b.neg());
+  term(p->zpoly, n + 3, op.lin_a + op.l1_z * ch.alpha.sqr());
+  term(p->wpoly, n + 2, vp[1]);
+  term(p->wpoly + np, n + 2, vp[2]);
+  term(p->wpoly + 2 * np, n + 2, vp[3]);
+  term(p->wpoly + 3 * np, n + 2, vp[4]);
+  term(p->tparts, n + 1, op.nzh);
+  term(p->tparts + np, n + 1, op.nzh * op.z_n);
+  term(p->tparts + 2 * np, n + 1, op.nzh * op.z_n.sqr());
+  term(t4, t4_len, op.nzh * op.z_n.sqr() * op.z_n);
+  la->count = k;
+}
+// W_zw numerator = z + v_w a + v_w^2 b + v_w^3 d (prover.rs:727-739)
+static void wzw_terms(const Prover* p, const Fr& v_w, uint64_t lo, uint64_t hi, LinCombArgs* la) {
+  const uint64_t n = p->n, np = p->np;
+  la->t[0].p = p->zpoly + lo; la->t[0].len = own_len(n + 3, lo, hi); la->t[0].s = Fr::one();
+  la->t[1].p = p->wpoly + lo; la->t[1].len = own_len(n + 2, lo, hi); la->t[1].s = v_w;
+  la->t[2].p = p->wpoly + np + lo; la->t[2].len = own_len(n + 2, lo, hi); la->t[2].s = v_w.sqr();
+  la->t[3].p = p->wpoly + 3 * np + lo; la->t[3].len = own_len(n + 2, lo, hi); la->t[3].s = v_w.sqr() * v_w;
+  la->count = 4;
 }
 
 static int prover_prove_sharded(Prover* p, const Fr* wires_dev, const uint64_t* pi_idx, const Fr* pi_val, uint64_t pi_count,
@@ -881,7 +1108,7 @@ static int prover_prove(Prover* p, const Fr* wires_dev, const uint64_t* pi_idx, 
   const uint32_t L = p->logn;
   NttTables* tbn;
   PTRY(ntt_tables(c, L, false, &tbn));
-  const Fr omega = omega_of(L);
+  const Fr omega = p->omega;
 
   // transcript_for_version(V3) = Transcript::base_v3 (transcript.rs:131-145, widget.rs:218-258)
   Transcript tr((const uint8_t*)p->label.data(), p->label.size());
@@ -892,25 +1119,6 @@ static int prover_prove(Prover* p, const Fr* wires_dev, const uint64_t* pi_idx, 
   GapScope gap_scope(&gap);
   // ---- round 1 (prover.rs:444-479)
   const bool lag = p->lag_on;
-  // iNTT + blinding of the four columns and their lowest coefficients (quotient_low), on the CURRENT stream
-  auto wire_polynomials = [&](Fr* ntt_tmp, int k0 = 0, int k1 = 4) -> int {
-    prof_begin(c, 4);   // slot 4: the polynomial work of rounds 1-2 (replicated on every rank of a multi-GPU run)
-    for (int k = k0; k < k1; ++k) {
-      Fr* wp = p->wpoly + k * np;
-      if (p->wires_pending) HIP_TRY(hipStreamWaitEvent(c->stream, p->ev_wire[k], 0));   // column k has arrived
-      PTRY(ntt_device(c, wires_dev + k * n, wp, ntt_tmp, L, true, false, n));
-      BlindArgs ba;
-      ba.count = 2;
-      ba.b[0] = bl[2 * k];
-      ba.b[1] = bl[2 * k + 1];
-      PTRY(poly_fill_zero(c, wp + n, np - n));
-      PTRY(poly_blind(c, wp, n, ba));
-    }
-    prof_end(c, 4);
-    for (int k = k0; k < k1; ++k)
-      HIP_TRY(hipMemcpyAsync(p->low_host + 7 * k, p->wpoly + k * np, 7 * sizeof(Fr), hipMemcpyDeviceToHost, c->stream));
-    return PLONK_OK;
-  };
   // Up to 2^19 gates the wire polynomials (needed from round 3 on) ride on the side stream under the commitment pipeline,
   // started after the group's accumulation (side_defer below): they fill its latency-bound reduction tail.  At 2^20 the
   // accumulation owns the VALU and its register file (two waves of 256 VGPRs per SIMD: no transform wave fits beside
@@ -929,7 +1137,7 @@ static int prover_prove(Prover* p, const Fr* wires_dev, const uint64_t* pi_idx, 
   // commitment), under the next columns' copies; the latency-bound reduction tail still runs once for the group (phase 2).
   // Same additions, same bucket sums, same bytes.  Resident columns (plonk_prover_prove_dev, what `value` times) keep the
   // grouped launch: four launches have four ramp-downs.
-  if (!polys_on_side && !by_column) PTRY(wire_polynomials(p->tmp8));
+  if (!polys_on_side && !by_column) PTRY(wire_polynomials(p, wires_dev, bl, p->tmp8, 0, 4));
   if (lag && by_column) {
     HIP_TRY(hipMemcpyAsync(p->wscal, bl, 8 * sizeof(Fr), hipMemcpyHostToDevice, c->stream));
   } else if (lag) {
@@ -956,16 +1164,10 @@ static int prover_prove(Prover* p, const Fr* wires_dev, const uint64_t* pi_idx, 
     // quotient_poly.rs:139-157,177: coset FFTs of a, b, c, d and of the public-input polynomial
     // (prover.rs:520-521) need no challenge -> side stream, overlapped with the commitments; with the
     // Lagrange key the wire polynomials themselves are only needed from round 3 on and move there too
-    if (polys_on_side) PTRY(wire_polynomials(p->tmp8b));
+    if (polys_on_side) PTRY(wire_polynomials(p, wires_dev, bl, p->tmp8b, 0, 4));
     for (int k = 0; k < 4; ++k)
       PTRY(ntt_device(c, p->wpoly + k * np, p->cos + (1 + k) * n8, p->tmp8b, L + p->lq, false, true, n + 2));
-    PTRY(poly_fill_zero(c, p->pipoly, np));
-    if (pi_count) {
-      PTRY(public_input_polynomial(p, pi_idx, pi_val, pi_count, p->tmp8b));
-      pi_len = n;
-    }
-    HIP_TRY(hipMemcpyAsync(p->low_host + 35, p->pipoly, 7 * sizeof(Fr), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipEventRecord(p->ev_pi, c->stream));
+    PTRY(public_input_polynomial(p, pi_idx, pi_val, pi_count, p->tmp8b, &pi_len));
     if (pi_len) PTRY(ntt_device(c, p->pipoly, p->cos + 5 * n8, p->tmp8b, L + p->lq, false, true, pi_len));   // no public inputs: PI(X) = 0, nothing to transform or read
     return PLONK_OK;
   };
@@ -989,7 +1191,7 @@ static int prover_prove(Prover* p, const Fr* wires_dev, const uint64_t* pi_idx, 
     p->last_wire_launches = (uint32_t)nparts;
     for (int q = 0; q < nparts; ++q) {
       const int k0 = nparts == 4 ? q : parts[q][0], kc = nparts == 4 ? 1 : parts[q][1];
-      PTRY(wire_polynomials(p->tmp8, k0, k0 + kc));   // waits for the columns' copies, then their inverse transforms + blinding
+      PTRY(wire_polynomials(p, wires_dev, bl, p->tmp8, k0, k0 + kc));   // waits for the columns' copies, then their inverse transforms + blinding
       if (k0 + kc == 4 && !side_defer) {              // all four polynomials exist: their coset transforms go to the side stream
         SideScope side(c, p->ev_ready);
         PTRY(side_round1());
@@ -1016,25 +1218,16 @@ static int prover_prove(Prover* p, const Fr* wires_dev, const uint64_t* pi_idx, 
     SideScopeAfter side(c, p->ev_acc);
     PTRY(side_round1());
   }
-  PTRY(fetch_commitments(p, 0, 4, comm));
-  tr.append_commitment("a_comm", comm[0]);
-  tr.append_commitment("b_comm", comm[1]);
-  tr.append_commitment("c_comm", comm[2]);
-  tr.append_commitment("d_comm", comm[3]);
+  PTRY(absorb_commitments(p, tr, 0, 4, comm));
 
   // ---- round 2 (prover.rs:481-505)
-  const Fr beta = tr.challenge_scalar("beta");
-  tr.append_scalar("beta", beta);
-  const Fr gamma = tr.challenge_scalar("gamma");
+  Challenges ch;
+  ch.beta = tr.challenge_scalar("beta");
+  tr.append_scalar("beta", ch.beta);
+  ch.gamma = tr.challenge_scalar("gamma");
   {
     prof_begin(c, 4);
-    PermArgs pa;
-    pa.n = n;
-    for (int k = 0; k < 4; ++k) { pa.wires[k] = wires_dev + k * n; pa.sigma[k] = p->sigma_n + k * n; }
-    pa.beta = beta; pa.gamma = gamma;
-    pa.ks[0] = Fr::one(); pa.ks[1] = fr_small(7); pa.ks[2] = fr_small(13); pa.ks[3] = fr_small(17);
-    pa.tw_lo29 = tbn->tw_lo29; pa.tw_hi29 = tbn->tw_hi29; pa.lobits = L < 13 ? L : 13; pa.use_hi = L > 13;
-    pa.num = p->scratch; pa.den = p->scratch + np;
+    const PermArgs pa = perm_args(p, wires_dev, ch, tbn);
     gap.launching();
     HIP_TRY(hipMemsetAsync(p->flag_dev, 0, sizeof(int), c->stream));
     PTRY(poly_perm_terms(c, pa));
@@ -1042,112 +1235,69 @@ static int prover_prove(Prover* p, const Fr* wires_dev, const uint64_t* pi_idx, 
     PTRY(poly_batch_inverse(c, pa.den, n, true));
     PTRY(poly_mul_arrays(c, pa.num, pa.den, n, p->flag_dev));
     PTRY(scan_prefix_product(c, pa.num, n, p->totals));
-    if (!z_from_evals) {
-      PTRY(ntt_device(c, pa.num, p->zpoly, p->tmp8, L, true, false, n));
-      BlindArgs ba;
-      ba.count = 3;
-      ba.b[0] = bl[8]; ba.b[1] = bl[9]; ba.b[2] = bl[10];
-      PTRY(poly_fill_zero(c, p->zpoly + n, np - n));
-      PTRY(poly_blind(c, p->zpoly, n, ba));
-    }
+    if (!z_from_evals) PTRY(blind_z(p, pa.num, bl, p->tmp8));
     prof_end(c, 4);
   }
-  // z(X) in coefficient form (needed from round 3 on), its lowest coefficients and its coset transform, on the CURRENT stream
-  auto z_polynomial = [&](Fr* ntt_tmp) -> int {
-    PTRY(ntt_device(c, p->scratch, p->zpoly, ntt_tmp, L, true, false, n));
-    BlindArgs ba;
-    ba.count = 3;
-    ba.b[0] = bl[8]; ba.b[1] = bl[9]; ba.b[2] = bl[10];
-    PTRY(poly_fill_zero(c, p->zpoly + n, np - n));
-    PTRY(poly_blind(c, p->zpoly, n, ba));
+  // Round 6, second session: z(X) = sum_i z_i L_i(X) + (b0 + b1 X + b2 X^2)(X^n - 1), so — like the wires — its commitment is
+  // an MSM of the n EVALUATIONS the scan just wrote and the three blinders over the Lagrange-basis key and its blinding
+  // points: the inverse transform, the blinding and the copy of the low coefficients leave the critical path (the side
+  // stream runs them before z's coset transform; `scratch` keeps the evaluations until round 5 reuses it).  Up to 2^17 gates
+  // only: same-box A/B 2^12 2.04 -> 2.01 ms, 2^16 4.09 -> 4.03, 2^17 5.88 -> 5.86 (even in a later
+  // five-repetition pair); at 2^18 the coefficient form is 1 % ahead (9.88 against 10.00 ms, mid_sizes_ab.jsonl), at 2^19 too, and
+  // at 2^20 the transform that left the main stream competes with the commitment's sort on the side stream instead (32.2 against
+  // 32.3), so larger circuits keep the coefficient form (profiles/r06b/zcommit_ab.jsonl).
+  // The side stream's share of either form: z's coset transform and, in front of it, what the evaluation form took off the
+  // main stream — z(X) in coefficient form (needed from round 3 on) and its lowest coefficients.
+  auto side_round2 = [&]() -> int {
+    if (z_from_evals) {
+      PTRY(blind_z(p, p->scratch, bl, p->tmp8b));
+      HIP_TRY(hipMemcpyAsync(p->low_host + 28, p->zpoly, 7 * sizeof(Fr), hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(hipEventRecord(p->ev_zlow, c->stream));
+    }
+    PTRY(ntt_device(c, p->zpoly, p->cos, p->tmp8b, L + p->lq, false, true, n + 3));   // z's coset FFT only needs z(X): overlap with its commitment
+    HIP_TRY(hipEventRecord(p->ev_side, c->side_stream));
     return PLONK_OK;
   };
   if (z_from_evals) {
-    // Round 6, second session: z(X) = sum_i z_i L_i(X) + (b0 + b1 X + b2 X^2)(X^n - 1), so — like the wires — its commitment is
-    // an MSM of the n EVALUATIONS the scan just wrote and the three blinders over the Lagrange-basis key and its blinding
-    // points: the inverse transform, the blinding and the copy of the low coefficients leave the critical path (the side
-    // stream runs them before z's coset transform; `scratch` keeps the evaluations until round 5 reuses it).  Up to 2^17 gates
-    // only: same-box A/B 2^12 2.04 -> 2.01 ms, 2^16 4.09 -> 4.03, 2^17 5.88 -> 5.86 (even in a later
-    // five-repetition pair); at 2^18 the coefficient form is 1 % ahead (9.88 against 10.00 ms, mid_sizes_ab.jsonl), at 2^19 too, and
-    // at 2^20 the transform that left the main stream competes with the commitment's sort on the side stream instead (32.2 against
-    // 32.3), so larger circuits keep the coefficient form (profiles/r06b/zcommit_ab.jsonl).
     HIP_TRY(hipMemcpyAsync(p->wscal + 8, bl + 8, 3 * sizeof(Fr), hipMemcpyHostToDevice, c->stream));
-    if (!side_defer_z) {
-      SideScope side(c, p->ev_ready);
-      PTRY(z_polynomial(p->tmp8b));
-      HIP_TRY(hipMemcpyAsync(p->low_host + 28, p->zpoly, 7 * sizeof(Fr), hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(hipEventRecord(p->ev_zlow, c->stream));
-      PTRY(ntt_device(c, p->zpoly, p->cos, p->tmp8b, L + p->lq, false, true, n + 3));
-      HIP_TRY(hipEventRecord(p->ev_side, c->side_stream));
-    }
-    {
-      AccMark mark(c, side_defer_z ? p->ev_acc : nullptr);
+  } else {
+    HIP_TRY(hipMemcpyAsync(p->low_host + 28, p->zpoly, 7 * sizeof(Fr), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipEventRecord(p->ev_zlow, c->stream));
+  }
+  if (!side_defer_z) {
+    SideScope side(c, p->ev_ready);
+    PTRY(side_round2());
+  }
+  {
+    AccMark mark(c, side_defer_z ? p->ev_acc : nullptr);
+    if (z_from_evals) {
       const Fr* sc[1] = {p->scratch};
       const Fr* tl[1] = {p->wscal + 8};
       const uint64_t ms[1] = {n + 3}, sp[1] = {n};
       PTRY(msm_group(p, sc, ms, 1, 4, p->lag_table, p->lag_n, tl, sp));
+    } else {
+      PTRY(msm_to(p, p->zpoly, n + 3, 4));
     }
-    if (side_defer_z) {
-      SideScopeAfter side(c, p->ev_acc);
-      PTRY(z_polynomial(p->tmp8b));
-      HIP_TRY(hipMemcpyAsync(p->low_host + 28, p->zpoly, 7 * sizeof(Fr), hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(hipEventRecord(p->ev_zlow, c->stream));
-      PTRY(ntt_device(c, p->zpoly, p->cos, p->tmp8b, L + p->lq, false, true, n + 3));
-      HIP_TRY(hipEventRecord(p->ev_side, c->side_stream));
-    }
-  } else {
-  HIP_TRY(hipMemcpyAsync(p->low_host + 28, p->zpoly, 7 * sizeof(Fr), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipEventRecord(p->ev_zlow, c->stream));
-  if (!side_defer_z) {
-    SideScope side(c, p->ev_ready);   // z's coset FFT only needs z(X): overlap with its commitment
-    PTRY(ntt_device(c, p->zpoly, p->cos, p->tmp8b, L + p->lq, false, true, n + 3));
-    HIP_TRY(hipEventRecord(p->ev_side, c->side_stream));
-  }
-  {
-    AccMark mark(c, side_defer_z ? p->ev_acc : nullptr);
-    PTRY(msm_to(p, p->zpoly, n + 3, 4));
   }
   if (side_defer_z) {
     SideScopeAfter side(c, p->ev_acc);
-    PTRY(ntt_device(c, p->zpoly, p->cos, p->tmp8b, L + p->lq, false, true, n + 3));
-    HIP_TRY(hipEventRecord(p->ev_side, c->side_stream));
+    PTRY(side_round2());
   }
-  }
-  PTRY(fetch_commitments(p, 4, 1, comm + 4));
-  tr.append_commitment("z_comm", comm[4]);
+  PTRY(absorb_commitments(p, tr, 4, 1, comm));
 
   // ---- round 3 (prover.rs:507-589)
-  const Fr alpha = tr.challenge_scalar("alpha");
-  const Fr range_ch = tr.challenge_scalar("range separation challenge");
-  const Fr logic_ch = tr.challenge_scalar("logic separation challenge");
-  const Fr fixed_ch = tr.challenge_scalar("fixed base separation challenge");
-  const Fr var_ch = tr.challenge_scalar("variable base separation challenge");
-  const Fr edwards_d = p->edwards_d;
+  ch.alpha = tr.challenge_scalar("alpha");
+  ch.range_ch = tr.challenge_scalar("range separation challenge");
+  ch.logic_ch = tr.challenge_scalar("logic separation challenge");
+  ch.fixed_ch = tr.challenge_scalar("fixed base separation challenge");
+  ch.var_ch = tr.challenge_scalar("variable base separation challenge");
   // quotient (quotient_poly.rs:20-137): the 6 coset FFTs on 8n were issued on the side stream in
   // rounds 1-2; point-wise pass, then coset iFFT
   HIP_TRY(hipStreamWaitEvent(c->main_stream, p->ev_side, 0));
   {
-    QuotientArgs q;
+    QuotientArgs q = quotient_args(p, ch, 0, pi_len);
     q.n8 = n8;
     q.rot = p->qf;
-    q.z = p->cos; q.a = p->cos + n8; q.b = p->cos + 2 * n8; q.c = p->cos + 3 * n8; q.d = p->cos + 4 * n8; q.pi = pi_len ? p->cos + 5 * n8 : nullptr;
-    const Fr* e = p->evals8;
-    q.q_m = e + P_QM * n8; q.q_l = e + P_QL * n8; q.q_r = e + P_QR * n8; q.q_o = e + P_QO * n8; q.q_f = e + P_QF * n8;
-    q.q_c = e + P_QC * n8; q.q_arith = e + P_QARITH * n8; q.q_range = e + P_QRANGE * n8; q.q_logic = e + P_QLOGIC * n8;
-    q.q_fixed = e + P_QFIXED * n8; q.q_var = e + P_QVAR * n8;
-    q.s1 = e + P_S1 * n8; q.s2 = e + P_S2 * n8; q.s3 = e + P_S3 * n8; q.s4 = e + P_S4 * n8;
-    q.linear = e + P_COUNT * n8; q.l1 = e + (P_COUNT + 1) * n8;
-    for (int s = 0; s < QS_COUNT; ++s) q.has[s] = p->has[s];
-    q.range_ch = range_ch; q.logic_ch = logic_ch; q.fixed_ch = fixed_ch; q.var_ch = var_ch;
-    q.edwards_d = edwards_d;
-    q.inv32 = p->inv32;
-    quotient_data(gamma, q.k.gamma);
-    quotient_data(Fr::one(), q.k.one);
-    const Fr ks[4] = {Fr::one(), fr_small(7), fr_small(13), fr_small(17)};
-    for (int k = 0; k < 4; ++k) quotient_const(beta * ks[k], 0, q.k.beta_k[k]);
-    quotient_const(alpha, 20, q.k.alpha_pos);
-    quotient_const(alpha.neg(), 20, q.k.alpha_neg);
-    quotient_const(alpha.sqr(), 0, q.k.alpha_sq);
     for (int i = 0; i < 8; ++i) quotient_const(p->vinv[i], 0, q.k.vinv[i]);
     q.out = p->tbuf;
     gap.launching();
@@ -1157,13 +1307,8 @@ static int prover_prove(Prover* p, const Fr* wires_dev, const uint64_t* pi_idx, 
   if (p->qf == 4) {   // de-alias the 4n interpolation with the host-computed low coefficients (see quotient_low)
     HIP_TRY(hipEventSynchronize(p->ev_pi));   // wire lows were complete at the round-1 synchronisation
     HIP_TRY(hipEventSynchronize(p->ev_zlow)); // z's come from the side stream when z is committed from its evaluations
-    QuotientLowIn qi;
-    qi.low = p->low_host;
-    qi.alpha = alpha; qi.beta = beta; qi.gamma = gamma;
-    qi.range_ch = range_ch; qi.logic_ch = logic_ch; qi.fixed_ch = fixed_ch; qi.var_ch = var_ch;
-    qi.edwards_d = edwards_d; qi.omega = omega; qi.n_inv = p->n_inv;
     Fr tlow[7];
-    quotient_low(p->key_low, p->has, qi, tlow);
+    quotient_low(p->key_low, p->has, quotient_low_in(p, ch), tlow);
     PTRY(poly_dealias(c, p->tbuf, n8, tlow, p->gq_inv));
   }
   HIP_TRY(hipMemcpyAsync(p->flag_host, p->flag_dev, sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -1197,12 +1342,8 @@ static int prover_prove(Prover* p, const Fr* wires_dev, const uint64_t* pi_idx, 
     const uint64_t ms[4] = {n + 1, n + 1, n + 1, t4_len};
     PTRY(msm_group(p, sc, ms, 4, 5));
   }
-  PTRY(fetch_commitments(p, 5, 4, comm + 5));
+  PTRY(absorb_commitments(p, tr, 5, 4, comm));
   if (*p->flag_host) return (plonk::set_last_error("invalid argument", __func__, __FILE__, __LINE__), PLONK_ERR_ARG);   // "permutation denominator must be nonzero" (permutation.rs:231-234)
-  tr.append_commitment("t_low_comm", comm[5]);
-  tr.append_commitment("t_mid_comm", comm[6]);
-  tr.append_commitment("t_high_comm", comm[7]);
-  tr.append_commitment("t_fourth_comm", comm[8]);
 
   // ---- round 4 (prover.rs:591-676): 15 evaluations
   const Fr z_ch = tr.challenge_scalar("z_challenge");
@@ -1210,129 +1351,51 @@ static int prover_prove(Prover* p, const Fr* wires_dev, const uint64_t* pi_idx, 
   Evals ev;
   {
     EvalArgs ea;
-    ea.partial = p->evpart;
-    ea.max_blocks = p->ev_max_blocks;
-    const Fr* P = p->polys;
-    const Fr* pol[15] = {p->wpoly, p->wpoly + np, p->wpoly + 2 * np, p->wpoly + 3 * np,
-                         p->wpoly, p->wpoly + np, p->wpoly + 3 * np,
-                         P + P_QARITH * np, P + P_QC * np, P + P_QL * np, P + P_QR * np,
-                         P + P_S1 * np, P + P_S2 * np, P + P_S3 * np, p->zpoly};
-    const uint64_t len[15] = {n + 2, n + 2, n + 2, n + 2, n + 2, n + 2, n + 2,
-                              p->poly_len[P_QARITH], p->poly_len[P_QC], p->poly_len[P_QL], p->poly_len[P_QR],
-                              p->poly_len[P_S1], p->poly_len[P_S2], p->poly_len[P_S3], n + 3};
-    for (int k = 0; k < 15; ++k) {
-      ea.items[k].poly = pol[k];
-      ea.items[k].len = len[k];
-      ea.items[k].x = (k >= 4 && k <= 6) || k == 14 ? zw : z_ch;
-    }
+    const uint64_t max_len = eval_items(p, z_ch, zw, 0, np, &ea);   // n + 3: z(X) is the longest of the 15
     gap.launching();
-    PTRY(poly_eval(c, ea, 15, n + 3, p->evout));
+    PTRY(poly_eval(c, ea, 15, max_len, p->evout));
     HIP_TRY(hipMemcpyAsync(p->ev_host, p->evout, 15 * sizeof(Fr), hipMemcpyDeviceToHost, c->stream));
     const auto t_before = HostGap::clock::now();
     HIP_TRY(hipStreamSynchronize(c->stream));
     gap.synced(t_before);
-    const Fr* h = p->ev_host;
-    ev.a = h[0]; ev.b = h[1]; ev.c = h[2]; ev.d = h[3]; ev.a_w = h[4]; ev.b_w = h[5]; ev.d_w = h[6];
-    ev.q_arith = h[7]; ev.q_c = h[8]; ev.q_l = h[9]; ev.q_r = h[10]; ev.s1 = h[11]; ev.s2 = h[12]; ev.s3 = h[13]; ev.z = h[14];
+    ev = unpack_evals(p->ev_host);
   }
   append_evaluations(tr, ev);
 
   // ---- round 5 (prover.rs:678-739)
   const Fr v = tr.challenge_scalar("v_challenge");
-  const Fr one = Fr::one();
-  const Fr z_n = z_ch.pow_u64(n);
-  const Fr zh = z_n - one;                                           // evaluate_vanishing_polynomial
-  const Fr n_inv = p->n_inv;
-  // 1/z, 1/(z - 1) and 1/(z omega) from one shared inversion
-  const bool z_zero = z_ch.is_zero();
-  Fr inv_z, inv_zm1;
-  {
-    const Fr zm1 = z_ch - one;
-    const Fr a = z_zero ? one : z_ch, b = zm1.is_zero() ? one : zm1;
-    const Fr iab = fr_inv_gcd(a * b);
-    inv_z = iab * b;
-    inv_zm1 = iab * a;
-  }
-  if (z_zero || zw.is_zero()) return PLONK_ERR_STATE;   // probability 2^-255; (X - 0) division is a shift — not worth a code path
+  Opening op;
+  PTRY(opening_point(p, z_ch, zw, &op));
   // W_z's commitment is not absorbed before v_w is drawn (prover.rs:727-730): both opening witnesses are committed as one
   // group, and the second one — W_zw = (z + v_w a + v_w^2 b + v_w^3 d) / (X - z w), which needs nothing but z and v_w — is
   // built on the SIDE stream (round 6, second session) while the host is still computing the linearisation scalars of the
   // first and the main stream builds that: below 2^18 gates the two chains of ~6 latency-bound kernels ran back to back.
-  // Buffers: the transform scratch (no transform runs after round 3), the upper half of `scratch`, the upper half of `totals`.
+  // Buffers, none of them the main stream's: the transform scratch (no transform runs after round 3), the upper half of
+  // `scratch` (a division takes np - 1 elements) and the scan totals `totals2`.
   const Fr v_w = tr.challenge_scalar("v_w_challenge");
   {
     gap.launching();
     SideScope side(c, p->ev_ready);
     LinCombArgs la;
-    la.t[0].p = p->zpoly; la.t[0].len = n + 3; la.t[0].s = one;
-    la.t[1].p = p->wpoly; la.t[1].len = n + 2; la.t[1].s = v_w;
-    la.t[2].p = p->wpoly + np; la.t[2].len = n + 2; la.t[2].s = v_w.sqr();
-    la.t[3].p = p->wpoly + 3 * np; la.t[3].len = n + 2; la.t[3].s = v_w.sqr() * v_w;
-    la.count = 4;
+    wzw_terms(p, v_w, 0, np, &la);
     la.len = np - 1;
     la.constant = Fr::zero();
     la.out = p->tmp8;
     PTRY(poly_lincomb(c, la));
-    PTRY(poly_ruffini(c, p->tmp8, p->wit2, np - 1, zw, inv_z * p->omega_inv, p->scratch + np, p->totals + 8192));
+    PTRY(poly_ruffini(c, p->tmp8, p->wit2, np - 1, zw, op.inv_z * p->omega_inv, p->scratch + np, p->totals2));
     HIP_TRY(hipEventRecord(p->ev_side, c->side_stream));
   }
-  const Fr pi_eval = public_input_eval(p, pi_idx, pi_val, pi_count, z_ch, zh);
-  // permutation linearisation scalars (permutation/proverkey.rs:127-269)
-  const Fr bz = beta * z_ch;
-  const Fr lin_a = (ev.a + bz + gamma) * (ev.b + fr_small(7) * bz + gamma) * (ev.c + fr_small(13) * bz + gamma) *
-                   (ev.d + fr_small(17) * bz + gamma) * alpha;
-  const Fr lin_b = (ev.a + beta * ev.s1 + gamma) * (ev.b + beta * ev.s2 + gamma) * (ev.c + beta * ev.s3 + gamma) *
-                   (beta * ev.z) * alpha;
-  Fr l1_z;                                                            // evaluate_all_lagrange_coefficients(z)[0]
-  if (z_n == one) l1_z = (z_ch == one) ? one : Fr::zero();
-  else l1_z = zh * n_inv * inv_zm1;
-  const Fr c_range = range_identity(range_ch, ev) * range_ch;
-  const Fr c_logic = logic_identity(logic_ch, ev) * logic_ch;
-  const Fr c_fixed = fixed_identity(fixed_ch, ev, edwards_d) * fixed_ch;
-  const Fr c_var = var_identity(var_ch, ev, edwards_d) * var_ch;
-  const Fr nzh = zh.neg();                                            // z_h_eval = -(z^n - 1)
-  Fr vp[12];
-  vp[0] = one;
-  for (int k = 1; k < 12; ++k) vp[k] = vp[k - 1] * v;
-  // W_z numerator = r + v a + v^2 b + v^3 c + v^4 d + v^5 s1 + v^6 s2 + v^7 s3 + v^8 q_arith + v^9 q_c
-  //                 + v^10 q_l + v^11 q_r  (prover.rs:706-726) with r expanded into its terms
+  opening_scalars(p, ev, ch, z_ch, v, pi_idx, pi_val, pi_count, &op);
   {
     LinCombArgs la;
-    int k = 0;
-    const Fr* P = p->polys;
-    auto term = [&](const Fr* ptr, uint64_t len, const Fr& s) { la.t[k].p = ptr; la.t[k].len = len; la.t[k].s = s; ++k; };
-    term(P + P_QM * np, p->poly_len[P_QM], ev.q_arith * ev.a * ev.b);
-    term(P + P_QL * np, p->poly_len[P_QL], ev.q_arith * ev.a + vp[10]);
-    term(P + P_QR * np, p->poly_len[P_QR], ev.q_arith * ev.b + vp[11]);
-    term(P + P_QO * np, p->poly_len[P_QO], ev.q_arith * ev.c);
-    term(P + P_QF * np, p->poly_len[P_QF], ev.q_arith * ev.d);
-    term(P + P_QC * np, p->poly_len[P_QC], ev.q_arith + vp[9]);
-    term(P + P_QARITH * np, p->poly_len[P_QARITH], vp[8]);
-    term(P + P_QRANGE * np, p->poly_len[P_QRANGE], c_range);
-    term(P + P_QLOGIC * np, p->poly_len[P_QLOGIC], c_logic);
-    term(P + P_QFIXED * np, p->poly_len[P_QFIXED], c_fixed);
-    term(P + P_QVAR * np, p->poly_len[P_QVAR], c_var);
-    term(P + P_S1 * np, p->poly_len[P_S1], vp[5]);
-    term(P + P_S2 * np, p->poly_len[P_S2], vp[6]);
-    term(P + P_S3 * np, p->poly_len[P_S3], vp[7]);
-    term(P + P_S4 * np, p->poly_len[P_S4], lin_b.neg());
-    term(p->zpoly, n + 3, lin_a + l1_z * alpha.sqr());
-    term(p->wpoly, n + 2, vp[1]);
-    term(p->wpoly + np, n + 2, vp[2]);
-    term(p->wpoly + 2 * np, n + 2, vp[3]);
-    term(p->wpoly + 3 * np, n + 2, vp[4]);
-    term(p->tparts, n + 1, nzh);
-    term(p->tparts + np, n + 1, nzh * z_n);
-    term(p->tparts + 2 * np, n + 1, nzh * z_n.sqr());
-    term(t4, t4_len, nzh * z_n.sqr() * z_n);
-    la.count = k;
+    numerator_terms(p, ev, ch, op, t4, t4_len, 0, np, &la);
     la.len = np - 1;
-    la.constant = pi_eval;
+    la.constant = op.pi_eval;
     la.out = p->agg;
     gap.launching();
     PTRY(poly_lincomb(c, la));
   }
-  PTRY(poly_ruffini(c, p->agg, p->wit, np - 1, z_ch, inv_z, p->scratch, p->totals));
+  PTRY(poly_ruffini(c, p->agg, p->wit, np - 1, z_ch, op.inv_z, p->scratch, p->totals));
   // ruffini's suffix scan leaves sum_j c_j z^j = (W_z numerator)(z) in scratch[0]: keep it for the
   // quotient-identity check below
   HIP_TRY(hipMemcpyAsync(p->evout + 15, p->scratch, sizeof(Fr), hipMemcpyDeviceToDevice, c->stream));
@@ -1344,7 +1407,7 @@ static int prover_prove(Prover* p, const Fr* wires_dev, const uint64_t* pi_idx, 
     PTRY(msm_group(p, sc, ms, 2, 9));
   }
   PTRY(fetch_commitments(p, 9, 2, comm + 9));
-  if (!quotient_identity_holds(p->ev_host[15], ev, alpha, beta, gamma, l1_z, vp)) return PLONK_ERR_UNSAT;
+  if (!quotient_identity_holds(p->ev_host[15], ev, ch.alpha, ch.beta, ch.gamma, op.l1_z, op.vp)) return PLONK_ERR_UNSAT;
 
   // ---- Proof::to_bytes (proof.rs:137-162, linearization_poly.rs:98-124)
   write_proof(proof, comm, ev);
@@ -1366,11 +1429,7 @@ static int prover_prove_sharded(Prover* p, const Fr* wires_dev, const uint64_t* 
   const uint64_t lo = p->lo, hi = p->hi;                       // owned coefficient indices, hi <= n + 7
   NttTables* tbn;
   PTRY(ntt_tables(c, L, false, &tbn));
-  const Fr omega = p->omega, one = Fr::one();
-  auto own_len = [&](uint64_t len) -> uint64_t {               // coefficients of a length-`len` polynomial inside [lo, hi)
-    const uint64_t e = len < hi ? len : hi;
-    return e > lo ? e - lo : 0;
-  };
+  const Fr omega = p->omega;
 
   Transcript tr((const uint8_t*)p->label.data(), p->label.size());
   seed_transcript(tr, p, pi_val, pi_count);
@@ -1380,25 +1439,6 @@ static int prover_prove_sharded(Prover* p, const Fr* wires_dev, const uint64_t* 
   uint8_t comm[11][48];
   // ---- round 1 (replicated polynomials, sharded commitments)
   const bool lag = p->lag_on;
-  // iNTT + blinding of the four columns and their lowest coefficients (quotient_low), on the CURRENT stream
-  auto wire_polynomials = [&](Fr* ntt_tmp) -> int {
-    prof_begin(c, 4);   // slot 4: replicated polynomial work (rounds 1-2)
-    for (int k = 0; k < 4; ++k) {
-      Fr* wp = p->wpoly + k * np;
-      if (p->wires_pending) HIP_TRY(hipStreamWaitEvent(c->stream, p->ev_wire[k], 0));   // column k has arrived
-      PTRY(ntt_device(c, wires_dev + k * n, wp, ntt_tmp, L, true, false, n));
-      BlindArgs ba;
-      ba.count = 2;
-      ba.b[0] = bl[2 * k];
-      ba.b[1] = bl[2 * k + 1];
-      PTRY(poly_fill_zero(c, wp + n, np - n));
-      PTRY(poly_blind(c, wp, n, ba));
-    }
-    prof_end(c, 4);
-    for (int k = 0; k < 4; ++k)
-      HIP_TRY(hipMemcpyAsync(p->low_host + 7 * k, p->wpoly + k * np, 7 * sizeof(Fr), hipMemcpyDeviceToHost, c->stream));
-    return PLONK_OK;
-  };
   // Round 4 (r04): the schedule of the single-GPU path for a RANK.  With the Lagrange-basis slice the wire commitments read
   // the wire VALUES, so the replicated wire polynomials (needed from round 3 on) ride on the side stream under the
   // commitment pipeline — a rank's MSM over 1/W of the points leaves most of the chip idle in its latency-bound sort and
@@ -1409,25 +1449,19 @@ static int prover_prove_sharded(Prover* p, const Fr* wires_dev, const uint64_t* 
   const uint64_t rank_pts = hi - lo;
   const bool polys_on_side = lag && shard_side_env && rank_pts <= (1ull << 18) + 64;   // (2^19 points per rank: 19.2 -> 19.4 ms, the accumulation owns the VALU)
   const bool side_defer = shard_side_env && rank_pts <= (1ull << 18) + 64;
-  if (!polys_on_side) PTRY(wire_polynomials(p->tmp8));
+  if (!polys_on_side) PTRY(wire_polynomials(p, wires_dev, bl, p->tmp8, 0, 4));
   SideJoin side_join{c};
   uint64_t pi_len = 0;
   Fr* fold_side = p->fold + n;
   auto side_round1 = [&]() -> int {
     // class evaluations of a, b, c, d, PI on the side stream: fold mod (X^n - x^n|class), size-n coset transform
-    if (polys_on_side) PTRY(wire_polynomials(p->tmp8b));
+    if (polys_on_side) PTRY(wire_polynomials(p, wires_dev, bl, p->tmp8b, 0, 4));
     for (uint32_t k = 0; k < cpr; ++k)
       for (int w = 0; w < 4; ++w) {
         PTRY(poly_fold(c, p->wpoly + w * np, fold_side, n, 2, p->sigma_j[p->cls[k]]));
         PTRY(ntt_device(c, fold_side, p->cos + (1 + w) * qn + k * n, p->tmp8b, L, false, true, n, &p->cs_fwd[k]));
       }
-    PTRY(poly_fill_zero(c, p->pipoly, np));
-    if (pi_count) {
-      PTRY(public_input_polynomial(p, pi_idx, pi_val, pi_count, p->tmp8b));
-      pi_len = n;
-    }
-    HIP_TRY(hipMemcpyAsync(p->low_host + 35, p->pipoly, 7 * sizeof(Fr), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipEventRecord(p->ev_pi, c->stream));
+    PTRY(public_input_polynomial(p, pi_idx, pi_val, pi_count, p->tmp8b, &pi_len));
     if (pi_len)
       for (uint32_t k = 0; k < cpr; ++k)
         PTRY(ntt_device(c, p->pipoly, p->cos + 5 * qn + k * n, p->tmp8b, L, false, true, n, &p->cs_fwd[k]));
@@ -1487,25 +1521,16 @@ static int prover_prove_sharded(Prover* p, const Fr* wires_dev, const uint64_t* 
     SideScopeAfter side(c, p->ev_acc);
     PTRY(side_round1());
   }
-  PTRY(fetch_commitments(p, 0, 4, comm));
-  tr.append_commitment("a_comm", comm[0]);
-  tr.append_commitment("b_comm", comm[1]);
-  tr.append_commitment("c_comm", comm[2]);
-  tr.append_commitment("d_comm", comm[3]);
+  PTRY(absorb_commitments(p, tr, 0, 4, comm));
 
   // ---- round 2 (replicated grand product)
-  const Fr beta = tr.challenge_scalar("beta");
-  tr.append_scalar("beta", beta);
-  const Fr gamma = tr.challenge_scalar("gamma");
+  Challenges ch;
+  ch.beta = tr.challenge_scalar("beta");
+  tr.append_scalar("beta", ch.beta);
+  ch.gamma = tr.challenge_scalar("gamma");
   {
     prof_begin(c, 4);
-    PermArgs pa;
-    pa.n = n;
-    for (int k = 0; k < 4; ++k) { pa.wires[k] = wires_dev + k * n; pa.sigma[k] = p->sigma_n + k * n; }
-    pa.beta = beta; pa.gamma = gamma;
-    pa.ks[0] = Fr::one(); pa.ks[1] = fr_small(7); pa.ks[2] = fr_small(13); pa.ks[3] = fr_small(17);
-    pa.tw_lo29 = tbn->tw_lo29; pa.tw_hi29 = tbn->tw_hi29; pa.lobits = L < 13 ? L : 13; pa.use_hi = L > 13;
-    pa.num = p->scratch; pa.den = p->scratch + np;
+    PermArgs pa = perm_args(p, wires_dev, ch, tbn);
     gap.launching();
     HIP_TRY(hipMemsetAsync(p->flag_dev, 0, sizeof(int), c->stream));
     // Round 4: the grand product (permutation.rs:213-294) split over the ranks from 2^19 gates and four ranks on.  Rank r forms the n / W
@@ -1533,7 +1558,7 @@ static int prover_prove_sharded(Prover* p, const Fr* wires_dev, const uint64_t* 
       struct { Fr total; int flag; int pad[7]; } mine, *all;
       static_assert(sizeof(mine) == 64, "exchange record");
       memset(&mine, 0, sizeof mine);
-      HIP_TRY(hipMemcpyAsync(p->ev_host, p->totals + (scan_prefix_blocks(cnt) - 1), sizeof(Fr), hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(hipMemcpyAsync(p->ev_host, &p->totals[scan_prefix_blocks(cnt) - 1], sizeof(Fr), hipMemcpyDeviceToHost, c->stream));
       HIP_TRY(hipMemcpyAsync(p->flag_host, p->flag_dev, sizeof(int), hipMemcpyDeviceToHost, c->stream));
       const auto t_before = HostGap::clock::now();
       PTRY(comm_sync(c, c->stream));
@@ -1555,12 +1580,7 @@ static int prover_prove_sharded(Prover* p, const Fr* wires_dev, const uint64_t* 
       PTRY(scan_prefix_product_apply(c, pa.num + first, cnt, p->totals, carry));
       PTRY(comm_allgather_dev(c, p->link, pa.num, sizeof(Fr) * cnt));
     }
-    PTRY(ntt_device(c, pa.num, p->zpoly, p->tmp8, L, true, false, n));
-    BlindArgs ba;
-    ba.count = 3;
-    ba.b[0] = bl[8]; ba.b[1] = bl[9]; ba.b[2] = bl[10];
-    PTRY(poly_fill_zero(c, p->zpoly + n, np - n));
-    PTRY(poly_blind(c, p->zpoly, n, ba));
+    PTRY(blind_z(p, pa.num, bl, p->tmp8));
     prof_end(c, 4);
   }
   HIP_TRY(hipMemcpyAsync(p->low_host + 28, p->zpoly, 7 * sizeof(Fr), hipMemcpyDeviceToHost, c->stream));
@@ -1584,41 +1604,20 @@ static int prover_prove_sharded(Prover* p, const Fr* wires_dev, const uint64_t* 
     SideScopeAfter side(c, p->ev_acc);
     PTRY(side_round2());
   }
-  PTRY(fetch_commitments(p, 4, 1, comm + 4));
-  tr.append_commitment("z_comm", comm[4]);
+  PTRY(absorb_commitments(p, tr, 4, 1, comm));
 
   // ---- round 3: quotient on the owned classes
-  const Fr alpha = tr.challenge_scalar("alpha");
-  const Fr range_ch = tr.challenge_scalar("range separation challenge");
-  const Fr logic_ch = tr.challenge_scalar("logic separation challenge");
-  const Fr fixed_ch = tr.challenge_scalar("fixed base separation challenge");
-  const Fr var_ch = tr.challenge_scalar("variable base separation challenge");
-  const Fr edwards_d = p->edwards_d;
+  ch.alpha = tr.challenge_scalar("alpha");
+  ch.range_ch = tr.challenge_scalar("range separation challenge");
+  ch.logic_ch = tr.challenge_scalar("logic separation challenge");
+  ch.fixed_ch = tr.challenge_scalar("fixed base separation challenge");
+  ch.var_ch = tr.challenge_scalar("variable base separation challenge");
   gap.launching();
   HIP_TRY(hipStreamWaitEvent(c->main_stream, p->ev_side, 0));
   for (uint32_t k = 0; k < cpr; ++k) {
-    QuotientArgs q;
+    QuotientArgs q = quotient_args(p, ch, (uint64_t)k * n, pi_len);
     q.n8 = n;
     q.rot = 1;                                                 // X -> omega X is the next point of the class
-    const Fr* co = p->cos + k * n;
-    q.z = co; q.a = co + qn; q.b = co + 2 * qn; q.c = co + 3 * qn; q.d = co + 4 * qn; q.pi = pi_len ? co + 5 * qn : nullptr;
-    const Fr* e = p->evals8 + k * n;
-    q.q_m = e + P_QM * qn; q.q_l = e + P_QL * qn; q.q_r = e + P_QR * qn; q.q_o = e + P_QO * qn; q.q_f = e + P_QF * qn;
-    q.q_c = e + P_QC * qn; q.q_arith = e + P_QARITH * qn; q.q_range = e + P_QRANGE * qn; q.q_logic = e + P_QLOGIC * qn;
-    q.q_fixed = e + P_QFIXED * qn; q.q_var = e + P_QVAR * qn;
-    q.s1 = e + P_S1 * qn; q.s2 = e + P_S2 * qn; q.s3 = e + P_S3 * qn; q.s4 = e + P_S4 * qn;
-    q.linear = e + P_COUNT * qn; q.l1 = e + (P_COUNT + 1) * qn;
-    for (int s = 0; s < QS_COUNT; ++s) q.has[s] = p->has[s];
-    q.range_ch = range_ch; q.logic_ch = logic_ch; q.fixed_ch = fixed_ch; q.var_ch = var_ch;
-    q.edwards_d = edwards_d;
-    q.inv32 = p->inv32;
-    quotient_data(gamma, q.k.gamma);
-    quotient_data(Fr::one(), q.k.one);
-    const Fr ks[4] = {Fr::one(), fr_small(7), fr_small(13), fr_small(17)};
-    for (int i = 0; i < 4; ++i) quotient_const(beta * ks[i], 0, q.k.beta_k[i]);
-    quotient_const(alpha, 20, q.k.alpha_pos);
-    quotient_const(alpha.neg(), 20, q.k.alpha_neg);
-    quotient_const(alpha.sqr(), 0, q.k.alpha_sq);
     for (int i = 0; i < 8; ++i) quotient_const(p->vinv[p->cls[k]], 0, q.k.vinv[i]);   // 1 / (x^n - 1): constant on a class
     q.out = p->Fbuf + (uint64_t)k * n;
     PTRY(poly_quotient(c, q));
@@ -1639,12 +1638,7 @@ static int prover_prove_sharded(Prover* p, const Fr* wires_dev, const uint64_t* 
     for (int i1 = 0; i1 < 5; ++i1) for (int j = 0; j < 8; ++j) cb.coef[i1][j] = p->coef[i1][j];
     if (Q == 4) {   // de-alias with the host-computed low coefficients, as on one GPU (quotient_low)
       HIP_TRY(hipEventSynchronize(p->ev_pi));
-      QuotientLowIn qi;
-      qi.low = p->low_host;
-      qi.alpha = alpha; qi.beta = beta; qi.gamma = gamma;
-      qi.range_ch = range_ch; qi.logic_ch = logic_ch; qi.fixed_ch = fixed_ch; qi.var_ch = var_ch;
-      qi.edwards_d = edwards_d; qi.omega = omega; qi.n_inv = p->n_inv;
-      quotient_low(p->key_low, p->has, qi, cb.low);
+      quotient_low(p->key_low, p->has, quotient_low_in(p, ch), cb.low);
     }
     cb.g4n_inv = p->gq_inv;
     cb.parts[0] = p->tparts; cb.parts[1] = p->tparts + np; cb.parts[2] = p->tparts + 2 * np; cb.parts[3] = t4;
@@ -1662,12 +1656,8 @@ static int prover_prove_sharded(Prover* p, const Fr* wires_dev, const uint64_t* 
     const uint64_t ms[4] = {n + 1, n + 1, n + 1, t4_len};
     PTRY(msm_group(p, sc, ms, 4, 5));
   }
-  PTRY(fetch_commitments(p, 5, 4, comm + 5));
+  PTRY(absorb_commitments(p, tr, 5, 4, comm));
   if (*p->flag_host) return (plonk::set_last_error("invalid argument", __func__, __FILE__, __LINE__), PLONK_ERR_ARG);
-  tr.append_commitment("t_low_comm", comm[5]);
-  tr.append_commitment("t_mid_comm", comm[6]);
-  tr.append_commitment("t_high_comm", comm[7]);
-  tr.append_commitment("t_fourth_comm", comm[8]);
 
   // ---- round 4: every rank evaluates its coefficient range, partial sums are all-gathered
   const Fr z_ch = tr.challenge_scalar("z_challenge");
@@ -1675,23 +1665,7 @@ static int prover_prove_sharded(Prover* p, const Fr* wires_dev, const uint64_t* 
   Evals ev;
   {
     EvalArgs ea;
-    ea.partial = p->evpart;
-    ea.max_blocks = p->ev_max_blocks;
-    const Fr* P = p->polys;
-    const Fr* pol[15] = {p->wpoly, p->wpoly + np, p->wpoly + 2 * np, p->wpoly + 3 * np,
-                         p->wpoly, p->wpoly + np, p->wpoly + 3 * np,
-                         P + P_QARITH * np, P + P_QC * np, P + P_QL * np, P + P_QR * np,
-                         P + P_S1 * np, P + P_S2 * np, P + P_S3 * np, p->zpoly};
-    const uint64_t len[15] = {n + 2, n + 2, n + 2, n + 2, n + 2, n + 2, n + 2,
-                              p->poly_len[P_QARITH], p->poly_len[P_QC], p->poly_len[P_QL], p->poly_len[P_QR],
-                              p->poly_len[P_S1], p->poly_len[P_S2], p->poly_len[P_S3], n + 3};
-    uint64_t max_len = 1;
-    for (int k = 0; k < 15; ++k) {
-      ea.items[k].poly = pol[k] + lo;
-      ea.items[k].len = own_len(len[k]);
-      ea.items[k].x = (k >= 4 && k <= 6) || k == 14 ? zw : z_ch;
-      if (ea.items[k].len > max_len) max_len = ea.items[k].len;
-    }
+    const uint64_t max_len = eval_items(p, z_ch, zw, lo, hi, &ea);
     gap.launching();
     PTRY(poly_eval(c, ea, 15, max_len, p->evout));
     HIP_TRY(hipMemcpyAsync(p->ev_host, p->evout, 15 * sizeof(Fr), hipMemcpyDeviceToHost, c->stream));
@@ -1714,83 +1688,30 @@ static int prover_prove_sharded(Prover* p, const Fr* wires_dev, const uint64_t* 
       pz = pz * step_z;
       pzw = pzw * step_zw;
     }
-    ev.a = h[0]; ev.b = h[1]; ev.c = h[2]; ev.d = h[3]; ev.a_w = h[4]; ev.b_w = h[5]; ev.d_w = h[6];
-    ev.q_arith = h[7]; ev.q_c = h[8]; ev.q_l = h[9]; ev.q_r = h[10]; ev.s1 = h[11]; ev.s2 = h[12]; ev.s3 = h[13]; ev.z = h[14];
+    ev = unpack_evals(h);
   }
   append_evaluations(tr, ev);
 
   // ---- round 5: linearisation + both opening quotients on the owned coefficient range
   const Fr v = tr.challenge_scalar("v_challenge");
   const Fr v_w = tr.challenge_scalar("v_w_challenge");        // W_z's commitment is not absorbed before it (prover.rs:727-730)
-  const Fr z_n = z_ch.pow_u64(n);
-  const Fr zh = z_n - one;
-  const Fr n_inv = p->n_inv;
-  if (z_ch.is_zero() || zw.is_zero()) return PLONK_ERR_STATE;   // probability 2^-255
-  const Fr zm1 = z_ch - one;
-  const Fr iab = fr_inv_gcd(z_ch * (zm1.is_zero() ? one : zm1));
-  const Fr inv_z = iab * (zm1.is_zero() ? one : zm1), inv_zm1 = iab * z_ch;
-  const Fr pi_eval = public_input_eval(p, pi_idx, pi_val, pi_count, z_ch, zh);
-  const Fr bz = beta * z_ch;
-  const Fr lin_a = (ev.a + bz + gamma) * (ev.b + fr_small(7) * bz + gamma) * (ev.c + fr_small(13) * bz + gamma) *
-                   (ev.d + fr_small(17) * bz + gamma) * alpha;
-  const Fr lin_b = (ev.a + beta * ev.s1 + gamma) * (ev.b + beta * ev.s2 + gamma) * (ev.c + beta * ev.s3 + gamma) *
-                   (beta * ev.z) * alpha;
-  Fr l1_z;
-  if (z_n == one) l1_z = (z_ch == one) ? one : Fr::zero();
-  else l1_z = zh * n_inv * inv_zm1;
-  const Fr c_range = range_identity(range_ch, ev) * range_ch;
-  const Fr c_logic = logic_identity(logic_ch, ev) * logic_ch;
-  const Fr c_fixed = fixed_identity(fixed_ch, ev, edwards_d) * fixed_ch;
-  const Fr c_var = var_identity(var_ch, ev, edwards_d) * var_ch;
-  const Fr nzh = zh.neg();
-  Fr vp[12];
-  vp[0] = one;
-  for (int k = 1; k < 12; ++k) vp[k] = vp[k - 1] * v;
+  Opening op;
+  PTRY(opening_point(p, z_ch, zw, &op));
+  opening_scalars(p, ev, ch, z_ch, v, pi_idx, pi_val, pi_count, &op);
   const uint64_t rlen = hi - lo;                               // owned part of the n + 7 numerator coefficients
   gap.launching();
   {
     LinCombArgs la;
-    int k = 0;
-    const Fr* P = p->polys;
-    auto term = [&](const Fr* ptr, uint64_t len, const Fr& s) { la.t[k].p = ptr + lo; la.t[k].len = own_len(len); la.t[k].s = s; ++k; };
-    term(P + P_QM * np, p->poly_len[P_QM], ev.q_arith * ev.a * ev.b);
-    term(P + P_QL * np, p->poly_len[P_QL], ev.q_arith * ev.a + vp[10]);
-    term(P + P_QR * np, p->poly_len[P_QR], ev.q_arith * ev.b + vp[11]);
-    term(P + P_QO * np, p->poly_len[P_QO], ev.q_arith * ev.c);
-    term(P + P_QF * np, p->poly_len[P_QF], ev.q_arith * ev.d);
-    term(P + P_QC * np, p->poly_len[P_QC], ev.q_arith + vp[9]);
-    term(P + P_QARITH * np, p->poly_len[P_QARITH], vp[8]);
-    term(P + P_QRANGE * np, p->poly_len[P_QRANGE], c_range);
-    term(P + P_QLOGIC * np, p->poly_len[P_QLOGIC], c_logic);
-    term(P + P_QFIXED * np, p->poly_len[P_QFIXED], c_fixed);
-    term(P + P_QVAR * np, p->poly_len[P_QVAR], c_var);
-    term(P + P_S1 * np, p->poly_len[P_S1], vp[5]);
-    term(P + P_S2 * np, p->poly_len[P_S2], vp[6]);
-    term(P + P_S3 * np, p->poly_len[P_S3], vp[7]);
-    term(P + P_S4 * np, p->poly_len[P_S4], lin_b.neg());
-    term(p->zpoly, n + 3, lin_a + l1_z * alpha.sqr());
-    term(p->wpoly, n + 2, vp[1]);
-    term(p->wpoly + np, n + 2, vp[2]);
-    term(p->wpoly + 2 * np, n + 2, vp[3]);
-    term(p->wpoly + 3 * np, n + 2, vp[4]);
-    term(p->tparts, n + 1, nzh);
-    term(p->tparts + np, n + 1, nzh * z_n);
-    term(p->tparts + 2 * np, n + 1, nzh * z_n.sqr());
-    term(t4, t4_len, nzh * z_n.sqr() * z_n);
-    la.count = k;
+    numerator_terms(p, ev, ch, op, t4, t4_len, lo, hi, &la);
     la.len = rlen;
-    la.constant = lo == 0 ? pi_eval : Fr::zero();
+    la.constant = lo == 0 ? op.pi_eval : Fr::zero();
     la.out = p->agg + lo;
     if (rlen) PTRY(poly_lincomb(c, la));
   }
   PTRY(poly_ruffini_local(c, p->agg + lo, lo, rlen, z_ch, p->scratch, p->totals));
   {
     LinCombArgs la;
-    la.t[0].p = p->zpoly + lo; la.t[0].len = own_len(n + 3); la.t[0].s = one;
-    la.t[1].p = p->wpoly + lo; la.t[1].len = own_len(n + 2); la.t[1].s = v_w;
-    la.t[2].p = p->wpoly + np + lo; la.t[2].len = own_len(n + 2); la.t[2].s = v_w.sqr();
-    la.t[3].p = p->wpoly + 3 * np + lo; la.t[3].len = own_len(n + 2); la.t[3].s = v_w.sqr() * v_w;
-    la.count = 4;
+    wzw_terms(p, v_w, lo, hi, &la);
     la.len = rlen;
     la.constant = Fr::zero();
     la.out = p->agg2 + lo;
@@ -1811,15 +1732,15 @@ static int prover_prove_sharded(Prover* p, const Fr* wires_dev, const uint64_t* 
     if (r > (uint32_t)p->rank) { carry_z = carry_z + tot[2 * r]; carry_zw = carry_zw + tot[2 * r + 1]; }
   }
   gap.launching();
-  PTRY(poly_ruffini_finish(c, p->scratch, p->wit, lo, rlen, inv_z, carry_z, n + 6));
-  PTRY(poly_ruffini_finish(c, p->scratch2, p->wit2, lo, rlen, inv_z * p->omega_inv, carry_zw, n + 6));
+  PTRY(poly_ruffini_finish(c, p->scratch, p->wit, lo, rlen, op.inv_z, carry_z, n + 6));
+  PTRY(poly_ruffini_finish(c, p->scratch2, p->wit2, lo, rlen, op.inv_z * p->omega_inv, carry_zw, n + 6));
   {
     const Fr* sc[2] = {p->wit, p->wit2};
     const uint64_t ms[2] = {np - 2, np - 2};
     PTRY(msm_group(p, sc, ms, 2, 9));
   }
   PTRY(fetch_commitments(p, 9, 2, comm + 9));
-  if (!quotient_identity_holds(num_at_z, ev, alpha, beta, gamma, l1_z, vp)) return PLONK_ERR_UNSAT;
+  if (!quotient_identity_holds(num_at_z, ev, ch.alpha, ch.beta, ch.gamma, op.l1_z, op.vp)) return PLONK_ERR_UNSAT;
   write_proof(proof, comm, ev);
   return PLONK_OK;
 }

@@ -138,9 +138,11 @@ def test_sharded_grand_product_matches_single_gpu(ranks, log_gates, profile):
     assert m["n_gpus"] == ranks and m["proof_blake2b"] == s["proof_blake2b"]
 
 
-@pytest.mark.parametrize("ranks,log_gates,env", [(3, 13, {}), (2, 12, {"PLONK_SHARD_QUOTIENT": "0"})])
+@pytest.mark.parametrize("ranks,log_gates,env", [(3, 13, {}), (2, 12, {"PLONK_SHARD_QUOTIENT": "0"}), (2, 12, {"PLONK_SHARD_SIDE": "0"})])
 def test_msm_only_sharding_matches_single_gpu(ranks, log_gates, env):
-    """other world sizes / PLONK_SHARD_QUOTIENT=0: only the MSMs are sharded (round-1 path)."""
+    """other world sizes / PLONK_SHARD_QUOTIENT=0: only the MSMs are sharded (round-1 path).  PLONK_SHARD_SIDE=0 is the
+    sharded quotient again, with a rank's side work started beside its commitments instead of after their accumulation —
+    an order no other multi-rank case runs."""
     s = single(log_gates, "dense")
     e = {"PLONK_BENCH_BACKEND": "gloo", "PLONK_BENCH_SHARE_GPU": "1"}
     e.update(env)
