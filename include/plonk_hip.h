@@ -776,6 +776,56 @@ int plonk_kzg_open_domain_dev(plonk_kzg_domain* domain, const void* const* polys
                               void* evaluations_dev, void* witnesses48_dev, void* commitments48_dev /* or NULL */);
 int plonk_kzg_domain_last(plonk_kzg_domain* domain, plonk_kzg_domain_info* out);
 
+/* ---- KZG10 in evaluation form ---------------------------------------------------------------------------
+ * Commitments and openings of polynomials given by their VALUES on the handle's domain — witness columns, a table, a blob,
+ * the `evaluations` of plonk_kzg_open_domain — without the inverse transform and the second copy in coefficient form that
+ * plonk_kzg_open needs.  n = 2^log_n, w the generator plonk_ntt uses for size n, e_j[i] = p_j(w^i), every vector exactly n
+ * Montgomery Fr:
+ *     commit_j = sum_i e_j[i] [L_i(tau)] G                          the 48 bytes of plonk_msm of plonk_ntt(inverse) of e_j
+ *     y_j = (z^n - 1) / n * sum_i e_j[i] w^i / (z - w^i)            z outside the domain;   y_j = e_j[m]  for z = w^m
+ *     F[i] = sum_j v^j e_j[i],  Y = sum_j v^j y_j                   (weight 1 for a single vector)
+ *     q[i] = (F[i] - Y) / (w^i - z)  (w^i != z),   q[m] = -w^(-m) sum_(i != m) q[i] w^i    (the derivative, for z = w^m)
+ *     witness = sum_i q[i] [L_i(tau)] G                             the 48 bytes plonk_kzg_open returns for the same z and v
+ *   The point may be ANY canonical field element, a point of the domain included.  The denominators are shared by the vectors
+ *   of a call and inverted once; every value crosses HBM once per call (fold contribution and evaluation partial in one
+ *   pass).  Commitments and the witness are bucket MSMs over the n Lagrange points [L_i(tau)] G (96 bytes each), which the
+ *   first call that commits builds from the commit key by one group transform and the handle keeps until it is destroyed: no
+ *   tables, nothing of the context's table budget (plonk_ctx_table_bytes is unchanged), and neither plonk_kzg_domain_info
+ *   nor plonk_kzg_domain_last counts them — plonk_kzg_evals_last does.  A key of exactly n points is enough.
+ * plonk_kzg_commit_evals: commitments48[j] = commit_j, j < count (count x 48 bytes).  count == 0 is PLONK_OK and writes nothing.
+ * plonk_kzg_open_evals: evaluations[j] = y_j (count x 4 limbs, Montgomery); commitments48[j] = commit_j (NULL skips them);
+ *   witness48 as above.  witness48 == NULL evaluates only: no quotient and no MSM run (with commitments48 == NULL the
+ *   Lagrange points are not even built).  count == 0 writes the compressed identity as the witness, as plonk_kzg_open does.
+ *   The host form stages the vectors through the two upload buffers of plonk_kzg_open (max(n, 2^16) values each), group
+ *   after group, so count x n is never resident.
+ * The _dev forms: evals_dev is a HOST array of `count` device pointers on the context's GPU; the outputs stay host memory, as
+ *   for plonk_kzg_open_dev.
+ * PLONK_ERR_ARG for a NULL argument (domain, the array, one of its entries, point, evaluations; commitments48 of
+ *   plonk_kzg_commit_evals), count > 65536, or v_challenge == NULL with count > 1; PLONK_ERR_DATA for a point, a challenge or
+ *   a value that is not a canonical residue; PLONK_ERR_STATE once the context's key was reloaded, and on a context with a
+ *   communicator.  Every check is made before anything is queued or written: an error leaves nothing queued and no output
+ *   touched.  The calls leave the context, its tables and its provers as they found them; plonk_ctx_last_msm_points keeps
+ *   describing the caller's own last call.
+ * plonk_kzg_evals_last: what the last evaluation-form call on the handle ran as (count == 0 before the first): the tests
+ *   assert it against the plan computed on the host (plonk_amd/csrc/kzg_evals_core.hpp). */
+typedef struct plonk_kzg_evals_info {
+  uint32_t log_n;
+  uint32_t built_points;           /* 1: this call built the Lagrange points */
+  uint64_t count;                  /* vectors of the last call */
+  uint64_t in_domain_index;        /* m with point == w^m, all ones when the point is outside the domain (or the call had no point) */
+  uint64_t msm_launches;           /* bucket MSMs the call ran: one per commitment, one for the witness */
+  uint64_t msm_terms;              /* terms of each: n */
+  uint64_t lagrange_bytes;         /* bytes of the Lagrange points the handle holds: 96 n once built */
+} plonk_kzg_evals_info;
+int plonk_kzg_commit_evals(plonk_kzg_domain* domain, const uint64_t* const* evals, uint64_t count, uint8_t* commitments48 /* count x 48 */);
+int plonk_kzg_commit_evals_dev(plonk_kzg_domain* domain, const void* const* evals_dev, uint64_t count, uint8_t* commitments48);
+int plonk_kzg_open_evals(plonk_kzg_domain* domain, const uint64_t* const* evals, uint64_t count, const uint64_t point[4],
+                         const uint64_t* v_challenge /* 4 limbs; may be NULL when count <= 1 */, uint64_t* evaluations /* count x 4 */,
+                         uint8_t* commitments48 /* count x 48, or NULL */, uint8_t* witness48 /* 48, or NULL */);
+int plonk_kzg_open_evals_dev(plonk_kzg_domain* domain, const void* const* evals_dev, uint64_t count, const uint64_t point[4],
+                             const uint64_t* v_challenge, uint64_t* evaluations, uint8_t* commitments48, uint8_t* witness48);
+int plonk_kzg_evals_last(plonk_kzg_domain* domain, plonk_kzg_evals_info* out);
+
 /* ---- variable-base MSM over caller-supplied points ------------------------------------------------
  * sum_i scalars[i] * P_i for points the CALLER brings — the reference's msm_variable_base (the primitive under Proof::verify
  * and OpeningKey::batch_check) — where plonk_msm / _batch / _dev run over the loaded commit key and its precomputed tables.

@@ -75,6 +75,8 @@ EXPORTS = [
     "plonk_kzg_pairing_check_each", "plonk_kzg_check_each", "plonk_verify_each",
     "plonk_kzg_domain_create", "plonk_kzg_domain_destroy", "plonk_kzg_domain_points", "plonk_kzg_open_domain",
     "plonk_kzg_open_domain_dev", "plonk_kzg_domain_last",
+    "plonk_kzg_commit_evals", "plonk_kzg_commit_evals_dev", "plonk_kzg_open_evals", "plonk_kzg_open_evals_dev",
+    "plonk_kzg_evals_last",
 ]
 
 # what bit f of plonk_unsat_row.families / slot f of plonk_unsat_info.family_rows stands for (include/plonk_hip.h); the
@@ -148,6 +150,13 @@ class _KzgDomainInfo(ctypes.Structure):
     _fields_ = [("log_n", ctypes.c_uint32), ("chunks", ctypes.c_uint32), ("count", ctypes.c_uint64),
                 ("device_bytes", ctypes.c_uint64), ("workspace_cap_bytes", ctypes.c_uint64), ("chunk_polys", ctypes.c_uint64),
                 ("stage_launches", ctypes.c_uint64), ("scalar_muls", ctypes.c_uint64)]
+
+
+class _KzgEvalsInfo(ctypes.Structure):
+    """plonk_kzg_evals_info (include/plonk_hip.h)"""
+    _fields_ = [("log_n", ctypes.c_uint32), ("built_points", ctypes.c_uint32), ("count", ctypes.c_uint64),
+                ("in_domain_index", ctypes.c_uint64), ("msm_launches", ctypes.c_uint64), ("msm_terms", ctypes.c_uint64),
+                ("lagrange_bytes", ctypes.c_uint64)]
 
 
 class _ProverInfo(ctypes.Structure):
@@ -418,6 +427,11 @@ def load_library() -> ctypes.CDLL:
     lib.plonk_kzg_open_domain_dev.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(u64), u64, vp, vp, vp]
     lib.plonk_kzg_domain_last.argtypes = [vp, ctypes.POINTER(_KzgDomainInfo)]
     lib.plonk_test_kzg_domain_set_cap.argtypes = [vp, u64]   # test hook of kzg_domain.hip, not in the header
+    lib.plonk_kzg_commit_evals.argtypes = [vp, ctypes.POINTER(vp), u64, vp]
+    lib.plonk_kzg_commit_evals_dev.argtypes = [vp, ctypes.POINTER(vp), u64, vp]
+    lib.plonk_kzg_open_evals.argtypes = [vp, ctypes.POINTER(vp), u64, vp, vp, vp, vp, vp]
+    lib.plonk_kzg_open_evals_dev.argtypes = [vp, ctypes.POINTER(vp), u64, vp, vp, vp, vp, vp]
+    lib.plonk_kzg_evals_last.argtypes = [vp, ctypes.POINTER(_KzgEvalsInfo)]
     _lib = lib
     return lib
 
@@ -1632,6 +1646,57 @@ class KzgDomain:
     def last(self) -> dict:
         info = _KzgDomainInfo()
         self.ctx._check(self.ctx.lib.plonk_kzg_domain_last(self.handle, ctypes.byref(info)))
+        return {k: getattr(info, k) for k, _ in info._fields_}
+
+    # ---- evaluation form: vectors of exactly n values on the domain ----
+    def _host_vectors(self, vectors):
+        bufs = [bytes(p) if isinstance(p, (bytes, bytearray)) else fr_to_bytes_mont(p) for p in vectors]
+        for b in bufs:
+            if len(b) != 32 * self.n:
+                raise ValueError("a vector of values must hold exactly n field elements")
+        keep = [ctypes.create_string_buffer(b, len(b)) for b in bufs]
+        return keep, [ctypes.cast(k, ctypes.c_void_p).value for k in keep]
+
+    def _commit_evals(self, fn, ptrs):
+        count = len(ptrs)
+        parr = (ctypes.c_void_p * max(count, 1))(*ptrs)
+        cm = ctypes.create_string_buffer(48 * max(count, 1))
+        self.ctx._check(fn(self.handle, parr, count, cm))
+        return [cm.raw[48 * j:48 * j + 48] for j in range(count)]
+
+    def commit_evals(self, vectors) -> list:
+        """plonk_kzg_commit_evals: vectors of n values (lists of ints, or Montgomery bytes) -> 48-byte commitments"""
+        keep, ptrs = self._host_vectors(vectors)
+        return self._commit_evals(self.ctx.lib.plonk_kzg_commit_evals, ptrs)
+
+    def commit_evals_dev(self, ptrs) -> list:
+        """plonk_kzg_commit_evals_dev: the same for vectors resident in HBM (device pointers, n values each)"""
+        return self._commit_evals(self.ctx.lib.plonk_kzg_commit_evals_dev, list(ptrs))
+
+    def _open_evals(self, fn, ptrs, point, v, commitments, witness):
+        count = len(ptrs)
+        parr = (ctypes.c_void_p * max(count, 1))(*ptrs)
+        ev = ctypes.create_string_buffer(32 * max(count, 1))
+        cm = ctypes.create_string_buffer(48 * max(count, 1)) if commitments else None
+        wit = ctypes.create_string_buffer(48) if witness else None
+        vb = fr_to_bytes_mont([v]) if v is not None else None
+        self.ctx._check(fn(self.handle, parr, count, fr_to_bytes_mont([point]), vb, ev, cm, wit))
+        return (fr_from_bytes_mont(ev.raw[:32 * count]),
+                [cm.raw[48 * j:48 * j + 48] for j in range(count)] if commitments else None, wit.raw if witness else None)
+
+    def open_evals(self, vectors, point: int, v: "int | None" = None, commitments: bool = True, witness: bool = True):
+        """plonk_kzg_open_evals: vectors of n values opened at `point` (any field element, a domain point included) ->
+        (evaluations, commitments or None, witness or None), the tuple Context.kzg_open returns for the coefficient forms"""
+        keep, ptrs = self._host_vectors(vectors)
+        return self._open_evals(self.ctx.lib.plonk_kzg_open_evals, ptrs, point, v, commitments, witness)
+
+    def open_evals_dev(self, ptrs, point: int, v: "int | None" = None, commitments: bool = True, witness: bool = True):
+        """plonk_kzg_open_evals_dev: the same for vectors resident in HBM (device pointers, n values each)"""
+        return self._open_evals(self.ctx.lib.plonk_kzg_open_evals_dev, list(ptrs), point, v, commitments, witness)
+
+    def evals_last(self) -> dict:
+        info = _KzgEvalsInfo()
+        self.ctx._check(self.ctx.lib.plonk_kzg_evals_last(self.handle, ctypes.byref(info)))
         return {k: getattr(info, k) for k, _ in info._fields_}
 
     def _set_workspace_cap(self, nbytes: int):

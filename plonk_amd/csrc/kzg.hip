@@ -86,6 +86,22 @@ void kzg_ws_release(Ctx* c) {
   c->kzg_ws = nullptr;
 }
 
+// the two upload buffers of the host forms (each at least `values` Fr) with their events and the copy stream: kzg_evals.hip
+// stages vectors of values through the buffers plonk_kzg_open stages coefficients through
+int kzg_stage_reserve(Ctx* c, uint64_t values, Fr* stage[2], hipEvent_t up[2], hipEvent_t done[2]) {
+  KzgWork& w = kzg_work(c);
+  PTRY_K(w.need(KzgWork::STAGE0, sizeof(Fr) * values));
+  PTRY_K(w.need(KzgWork::STAGE1, sizeof(Fr) * values));
+  PTRY_K(w.events());
+  if (!c->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
+  for (int b = 0; b < 2; ++b) {
+    stage[b] = w.at<Fr>(b ? KzgWork::STAGE1 : KzgWork::STAGE0);
+    up[b] = w.up[b];
+    done[b] = w.done[b];
+  }
+  return PLONK_OK;
+}
+
 static void identity48(uint8_t out[48]) {
   memset(out, 0, 48);
   out[0] = 0xC0;

@@ -30,6 +30,7 @@
 #include "hostg1.hpp"
 #include "kzg_core.hpp"
 #include "kzg_domain.hpp"
+#include "kzg_evals.hpp"
 
 #define PTRY_D(expr) do { int _rc = (expr); if (_rc) return _rc; } while (0)
 #define KZD_FAIL(code, msg) return (plonk::set_last_error(api_fn, msg, __FILE__, __LINE__), code)
@@ -340,7 +341,9 @@ struct KzgDomain {
   uint64_t cap[NBUF] = {};
   uint64_t ws_cap = KZD_WS_CAP_DEFAULT;
   plonk_kzg_domain_info last = {};
+  void* evals = nullptr;         // the Lagrange points and workspace of the evaluation-form calls (kzg_evals.hip); not in device_bytes()
   ~KzgDomain() {
+    kze_release(evals);
     (void)hipFree(A);
     (void)hipFree(tw);
     for (int i = 0; i < NBUF; ++i) (void)hipFree(p[i]);
@@ -362,6 +365,11 @@ struct KzgDomain {
     return s;
   }
 };
+
+KzdView kzd_view(plonk_kzg_domain* dom) {
+  KzgDomain* d = dom->d;
+  return KzdView{d->c, d->log_n, d->srs_gen == d->c->srs_gen, d->tw, &d->evals};
+}
 
 static void identity48(uint8_t out[48]) {
   memset(out, 0, 48);

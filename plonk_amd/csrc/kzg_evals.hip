@@ -1,0 +1,665 @@
+// KZG10 in evaluation form: commitments and openings of polynomials given by their values on a plonk_kzg_domain.  The
+// formulas, the argument checks and the plan are in kzg_evals_core.hpp; DESIGN.md section 15 has the resources and the
+// measurements.
+//
+//   kze_load_kernel       once per handle: the first n points of the commit key (row 0 of its tables) as XYZZ slots
+//   kze_points_kernel     once per handle: slot rev((n - i) mod n) of the forward group transform (kzd_transform) times 1/n,
+//                         normalised: [L_i(tau)] G as 96 affine bytes, the layout msm_points_run reads
+//   kze_scan_kernel       resident vectors: the canonical-form check
+//   kze_denoms_kernel     w^i - z per lane and the lane m where it vanishes; poly_batch_inverse inverts in place and
+//                         leaves that zero alone, so lane m cannot poison its block
+//   kze_fold_kernel       one pass over the values: F[i] += v^j e_j[i] and the partial of y_j with the weight
+//                         1 + z / (w^i - z) = w^i / (w^i - z) (inside the domain: 1 at lane m, 0 elsewhere); a wave's partials
+//                         are summed by shuffles, kze_final_kernel adds them per vector and applies -(z^n - 1) / n
+//   kze_quotient_kernel   q[i] = (F[i] - Y) / (w^i - z); inside the domain also the block partials of sum q[i] w^i, from
+//   kze_qfix_kernel       which one lane writes q[m] = -w^(-m) sum
+// Commitments and the witness go through msm_points_run over the resident Lagrange points: no tables, nothing of the
+// context's table budget.
+#include <hip/hip_runtime.h>
+
+#include <mutex>
+#include <new>
+#include <vector>
+
+#include "../../include/plonk_hip.h"
+#include "plonk_internal.hpp"
+#include "api_guard.hpp"
+#include "poly.hpp"
+#include "fr29.cuh"
+#include "hostg1.hpp"
+#include "kzg_core.hpp"
+#include "kzg_domain.hpp"
+#include "kzg_evals.hpp"
+
+#define PTRY_E(expr) do { int _rc = (expr); if (_rc) return _rc; } while (0)
+#define KZE_FAIL(code, msg) return (plonk::set_last_error(api_fn, msg, __FILE__, __LINE__), code)
+
+namespace plonk {
+
+namespace {
+
+// Fp28 / G1R in memory: each coordinate padded to 16 words (64 B), as the slots of kzg_domain.hip
+struct alignas(16) G1RSlot {
+  Fp28Slot X, Y, ZZ, ZZZ;
+};
+static_assert(sizeof(G1RSlot) == KZD_SLOT_BYTES, "slot size");
+static_assert(sizeof(G1Affine) == KZE_POINT_BYTES, "point size");
+__device__ __forceinline__ Fp28 ld_f28(const Fp28Slot* p) {
+  const uint4* q = reinterpret_cast<const uint4*>(p);
+  const uint4 a = q[0], b = q[1], c = q[2], d = q[3];
+  Fp28 r;
+  r.l[0] = a.x; r.l[1] = a.y; r.l[2] = a.z; r.l[3] = a.w;
+  r.l[4] = b.x; r.l[5] = b.y; r.l[6] = b.z; r.l[7] = b.w;
+  r.l[8] = c.x; r.l[9] = c.y; r.l[10] = c.z; r.l[11] = c.w;
+  r.l[12] = d.x; r.l[13] = d.y;
+  return r;
+}
+__device__ __forceinline__ void st_f28(Fp28Slot* p, const Fp28& v) {
+  uint4* q = reinterpret_cast<uint4*>(p);
+  q[0] = make_uint4(v.l[0], v.l[1], v.l[2], v.l[3]);
+  q[1] = make_uint4(v.l[4], v.l[5], v.l[6], v.l[7]);
+  q[2] = make_uint4(v.l[8], v.l[9], v.l[10], v.l[11]);
+  q[3] = make_uint4(v.l[12], v.l[13], 0u, 0u);
+}
+__device__ __forceinline__ G1R ld_g1r(const G1RSlot* p) {
+  G1R r;
+  r.X = ld_f28(&p->X); r.Y = ld_f28(&p->Y); r.ZZ = ld_f28(&p->ZZ); r.ZZZ = ld_f28(&p->ZZZ);
+  return r;
+}
+__device__ __forceinline__ void st_g1r(G1RSlot* p, const G1R& v) {
+  st_f28(&p->X, v.X); st_f28(&p->Y, v.Y); st_f28(&p->ZZ, v.ZZ); st_f28(&p->ZZZ, v.ZZZ);
+}
+__device__ __forceinline__ Fr ldf(const Fr* p) {
+  const uint4* q = reinterpret_cast<const uint4*>(p);
+  const uint4 a = q[0], b = q[1];
+  Fr r;
+  r.l[0] = a.x; r.l[1] = a.y; r.l[2] = a.z; r.l[3] = a.w;
+  r.l[4] = b.x; r.l[5] = b.y; r.l[6] = b.z; r.l[7] = b.w;
+  return r;
+}
+__device__ __forceinline__ void stf(Fr* p, const Fr& v) {
+  uint4* q = reinterpret_cast<uint4*>(p);
+  q[0] = make_uint4(v.l[0], v.l[1], v.l[2], v.l[3]);
+  q[1] = make_uint4(v.l[4], v.l[5], v.l[6], v.l[7]);
+}
+
+// reduced-radix operands as kernel arguments, as poly.hip passes them: x * R'' ("twiddle form") or the re-sliced R form
+struct Tw {
+  uint32_t w[9];
+};
+__device__ __forceinline__ Fr29 tw29(const Tw& t) {
+  Fr29 r;
+#pragma unroll
+  for (int i = 0; i < 9; ++i) r.l[i] = t.w[i];
+  return r;
+}
+Tw tw_of(const Fr& x) {   // host: x (R form) -> x * R''
+  const Fr29 t = Fr29::twiddle_from_fr(x);
+  Tw r;
+  for (int i = 0; i < 9; ++i) r.w[i] = t.l[i];
+  return r;
+}
+Tw tw_plain(const Fr& x) {   // host: the re-sliced R-form value
+  const Fr29 t = Fr29::from_fr(x);
+  Tw r;
+  for (int i = 0; i < 9; ++i) r.w[i] = t.l[i];
+  return r;
+}
+__device__ __forceinline__ Fr29 ld_slot(const void* base, uint64_t idx) {
+  const uint4* q = reinterpret_cast<const uint4*>(reinterpret_cast<const Fr29Slot*>(base) + idx);
+  const uint4 a = q[0], b = q[1];
+  const uint32_t c = reinterpret_cast<const Fr29Slot*>(base)[idx].w[8];
+  Fr29 r;
+  r.l[0] = a.x; r.l[1] = a.y; r.l[2] = a.z; r.l[3] = a.w;
+  r.l[4] = b.x; r.l[5] = b.y; r.l[6] = b.z; r.l[7] = b.w;
+  r.l[8] = c;
+  return r;
+}
+
+constexpr uint32_t KZE_POINT_LANES = 64;   // one wave per workgroup in the point kernels, as kzg_domain.hip
+
+Fr kze_root(uint32_t log_size) {   // the generator of the size-2^log_size domain, as ntt.hip derives it
+  Fr w = fr_root_of_unity();
+  for (uint32_t i = log_size; i < 32; ++i) w = w.sqr();
+  return w;
+}
+
+}  // namespace
+
+// ---- the Lagrange points ---------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(KZE_POINT_LANES) kze_load_kernel(const G1AffineR* __restrict__ row0, uint64_t n,
+                                                                   G1RSlot* __restrict__ v) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  st_g1r(v + i, G1R::from_affine(ld_f28(&row0[i].x), ld_f28(&row0[i].y)));
+}
+
+// the forward transform leaves sum_j w^(jk) s_j = n [L_(-k)(tau)] G in slot rev(k)
+__global__ void __launch_bounds__(KZE_POINT_LANES) kze_points_kernel(const G1RSlot* __restrict__ v, uint32_t log_n, Fr n_inv_canonical,
+                                                                     G1Affine* __restrict__ out) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint64_t n = 1ull << log_n;
+  if (i >= n) return;
+  const G1R s = ld_g1r(v + kzd_rev((n - i) & (n - 1), log_n));
+  uint32_t w[24];
+#pragma unroll
+  for (int k = 0; k < 24; ++k) w[k] = 0;
+  if (!s.is_identity()) {   // (tau a point of the domain makes all but one of them the identity)
+    const G1R p = g1r_mul_glv(s, n_inv_canonical.l);
+    Fp28 x, y;
+    g1r_to_affine(p, &x, &y);
+    const Fp xf = x.to_fp(), yf = y.to_fp();
+#pragma unroll
+    for (int k = 0; k < 12; ++k) { w[k] = xf.l[k]; w[12 + k] = yf.l[k]; }
+  }
+  uint4* q = reinterpret_cast<uint4*>(out + i);
+#pragma unroll
+  for (int k = 0; k < 6; ++k) q[k] = make_uint4(w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]);
+}
+
+// ---- the scalar stage --------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) kze_scan_kernel(const Fr* const* __restrict__ vecs, uint64_t n, KzeMeta* __restrict__ meta) {
+  const Fr* p = vecs[blockIdx.y];
+  unsigned long long bad = 0;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+    const Fr x = ldf(p + i);
+    bool lt = false;
+    for (int k = 7; k >= 0; --k)
+      if (x.l[k] != FrP::MOD[k]) { lt = x.l[k] < FrP::MOD[k]; break; }
+    if (!lt) bad = 1;
+  }
+  if (bad) atomicOr(&meta->bad, bad);
+}
+
+__global__ void __launch_bounds__(256) kze_denoms_kernel(Fr w, Fr z, uint64_t n, Fr* __restrict__ den, KzeMeta* __restrict__ meta) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const Fr d = w.pow_u64(i) - z;
+  stf(den + i, d);
+  if (d.is_zero()) meta->m = i;   // at most one lane: the w^i are distinct
+}
+
+// A lane owns the KZE_FOLD_E values base + k * KZE_FOLD_T (coalesced).  Per vector it loads each value ONCE and uses it
+// twice: f[k] += v^j e (the fold) and h += e u_k (the partial of y_j).  Values stay in data form: data x twiddle -> data.
+__global__ void __launch_bounds__(KZE_FOLD_T) kze_fold_kernel(KzeFoldArgs a, Tw zt_, Tw conv_, Tw one_plain, Tw one_t, uint32_t nwaves) {
+  const uint64_t base = (uint64_t)blockIdx.x * (KZE_FOLD_T * KZE_FOLD_E) + threadIdx.x;
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t wave = ((uint64_t)blockIdx.x * KZE_FOLD_T + threadIdx.x) >> 6;
+  static_assert(KZE_FOLD_E == 4, "the fold kernel is written out for four values per lane");
+  // written out per value so that the accumulators have constant names and stay in registers
+  const uint64_t i0 = base, i1 = base + KZE_FOLD_T, i2 = base + 2 * KZE_FOLD_T, i3 = base + 3 * KZE_FOLD_T;
+  Fr29 f0 = Fr29::zero(), f1 = f0, f2 = f0, f3 = f0, u0 = f0, u1 = f0, u2 = f0, u3 = f0;
+  if (a.m != KZE_NONE) {
+    const Fr29 one = tw29(one_t);
+    if (i0 == a.m) u0 = one;
+    if (i1 == a.m) u1 = one;
+    if (i2 == a.m) u2 = one;
+    if (i3 == a.m) u3 = one;
+  } else {   // (1 + z d_i) in data form, then into twiddle form
+    const Fr29 zt = tw29(zt_), conv = tw29(conv_), one = tw29(one_plain);
+#define KZE_WEIGHT(k) \
+  if (i##k < a.n) u##k = Fr29::mul(Fr29::add_csub(Fr29::mul(Fr29::from_fr(ldf(a.inv + i##k)), zt), one), conv);
+    KZE_WEIGHT(0) KZE_WEIGHT(1) KZE_WEIGHT(2) KZE_WEIGHT(3)
+#undef KZE_WEIGHT
+  }
+  for (uint32_t j = 0; j < a.count; ++j) {
+    const Fr* p = a.vecs[a.first + j];
+    const Fr29 vt = ld_slot(a.vpow, a.first + j);
+    Fr29 h = Fr29::zero();
+#define KZE_STEP(k)                                   \
+  if (i##k < a.n) {                                   \
+    const Fr29 e = Fr29::from_fr(ldf(p + i##k));      \
+    f##k = Fr29::add_csub(f##k, Fr29::mul(e, vt));    \
+    h = Fr29::add_csub(h, Fr29::mul(e, u##k));        \
+  }
+    KZE_STEP(0) KZE_STEP(1) KZE_STEP(2) KZE_STEP(3)
+#undef KZE_STEP
+#pragma unroll
+    for (int off = 32; off; off >>= 1) {
+      Fr29 o;
+#pragma unroll
+      for (int w = 0; w < 9; ++w) o.l[w] = __shfl_down(h.l[w], off, 64);
+      h = Fr29::add_csub(h, o);
+    }
+    if (!lane) stf(a.partial + (uint64_t)j * nwaves + wave, h.to_fr());
+  }
+#define KZE_STORE(k)                                                                  \
+  if (i##k < a.n) {                                                                   \
+    Fr29 r = f##k;                                                                    \
+    if (a.accumulate) r = Fr29::add_csub(r, Fr29::from_fr(ldf(a.fold + i##k)));       \
+    stf(a.fold + i##k, r.to_fr());                                                    \
+  }
+  KZE_STORE(0) KZE_STORE(1) KZE_STORE(2) KZE_STORE(3)
+#undef KZE_STORE
+}
+// one workgroup per vector of the launch: evals[j] = scale * the sum of its nwaves partials
+__global__ void __launch_bounds__(256) kze_final_kernel(const Fr* __restrict__ partial, uint32_t nwaves, Fr scale, Fr* __restrict__ evals) {
+  __shared__ Fr sh[256];
+  const uint32_t t = threadIdx.x;
+  Fr acc = Fr::zero();
+  for (uint32_t w = t; w < nwaves; w += 256) acc = acc + ldf(partial + (uint64_t)blockIdx.x * nwaves + w);
+  sh[t] = acc;
+  __syncthreads();
+  for (uint32_t h = 128; h; h >>= 1) {
+    if (t < h) sh[t] = sh[t] + sh[t + h];
+    __syncthreads();
+  }
+  if (!t) stf(evals + blockIdx.x, sh[0] * scale);
+}
+
+// in_domain: lane m has inv == 0, so its q is 0 for now and contributes nothing to the sum
+__global__ void __launch_bounds__(KZE_Q_T) kze_quotient_kernel(const Fr* __restrict__ fold, const Fr* __restrict__ inv, Fr Y, uint64_t n,
+                                                               Fr w, int in_domain, Fr* __restrict__ q, Fr* __restrict__ qpart) {
+  __shared__ Fr sh[KZE_Q_T];
+  const uint32_t t = threadIdx.x;
+  const uint64_t i = (uint64_t)blockIdx.x * KZE_Q_T + t;
+  Fr v = Fr::zero();
+  if (i < n) {
+    v = (ldf(fold + i) - Y) * ldf(inv + i);
+    stf(q + i, v);
+  }
+  if (!in_domain) return;   // (uniform over the grid)
+  sh[t] = i < n ? v * w.pow_u64(i) : Fr::zero();
+  __syncthreads();
+  for (uint32_t h = KZE_Q_T / 2; h; h >>= 1) {
+    if (t < h) sh[t] = sh[t] + sh[t + h];
+    __syncthreads();
+  }
+  if (!t) stf(qpart + blockIdx.x, sh[0]);
+}
+__global__ void __launch_bounds__(256) kze_qfix_kernel(const Fr* __restrict__ qpart, uint32_t nblocks, Fr neg_w_inv_m, uint64_t m,
+                                                       Fr* __restrict__ q) {
+  __shared__ Fr sh[256];
+  const uint32_t t = threadIdx.x;
+  Fr acc = Fr::zero();
+  for (uint32_t b = t; b < nblocks; b += 256) acc = acc + ldf(qpart + b);
+  sh[t] = acc;
+  __syncthreads();
+  for (uint32_t h = 128; h; h >>= 1) {
+    if (t < h) sh[t] = sh[t] + sh[t + h];
+    __syncthreads();
+  }
+  if (!t) stf(q + m, sh[0] * neg_w_inv_m);
+}
+
+// ---- launchers (kzg_evals.hpp) -----------------------------------------------------------------------------------------------
+int kze_lagrange_points(Ctx* c, uint32_t log_n, const GlvScalar* tw, uint32_t tw_log, G1Affine* out) {
+  const uint64_t n = 1ull << log_n;
+  if (!c->srs_table || c->srs_n < n || log_n < 1 || log_n > tw_log) return PLONK_ERR_ARG;
+  G1RSlot* v = nullptr;
+  HIP_TRY(hipMalloc((void**)&v, sizeof(G1RSlot) * n));
+  const dim3 grid((uint32_t)((n + KZE_POINT_LANES - 1) / KZE_POINT_LANES));
+  hipLaunchKernelGGL(kze_load_kernel, grid, dim3(KZE_POINT_LANES), 0, c->stream, (const G1AffineR*)c->srs_table, n, v);
+  int rc = hipGetLastError() == hipSuccess ? PLONK_OK : PLONK_ERR_HIP;
+  if (rc == PLONK_OK) rc = kzd_transform(c, v, n, log_n, 1, false, tw, tw_log, nullptr, nullptr);
+  if (rc == PLONK_OK) {
+    hipLaunchKernelGGL(kze_points_kernel, grid, dim3(KZE_POINT_LANES), 0, c->stream, (const G1RSlot*)v, log_n,
+                       Fr::from_u64(n).inv().from_mont(), out);
+    if (hipGetLastError() != hipSuccess) rc = PLONK_ERR_HIP;
+  }
+  if (hipStreamSynchronize(c->stream) != hipSuccess && rc == PLONK_OK) rc = PLONK_ERR_HIP;
+  (void)hipFree(v);
+  if (rc == PLONK_ERR_HIP) set_last_error("kze_lagrange_points", "a launch of the Lagrange-point build failed", __FILE__, __LINE__);
+  return rc;
+}
+
+int kze_scan(Ctx* c, const Fr* const* vecs, uint32_t first, uint32_t cnt, uint64_t n, KzeMeta* meta) {
+  if (!cnt) return PLONK_OK;
+  const uint32_t blocks = (uint32_t)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024);
+  hipLaunchKernelGGL(kze_scan_kernel, dim3(blocks, cnt), dim3(256), 0, c->stream, vecs + first, n, meta);
+  HIP_TRY(hipGetLastError());
+  return PLONK_OK;
+}
+
+int kze_denominators(Ctx* c, uint32_t log_n, const Fr& z, Fr* den, KzeMeta* meta) {
+  const uint64_t n = 1ull << log_n;
+  hipLaunchKernelGGL(kze_denoms_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, c->stream, kze_root(log_n), z, n, den, meta);
+  HIP_TRY(hipGetLastError());
+  return PLONK_OK;
+}
+
+int kze_fold_eval(Ctx* c, const KzeFoldArgs& a, Fr* evals) {
+  if (!a.count || a.count > KZE_GROUP || !a.n) return (set_last_error("invalid argument", __func__, __FILE__, __LINE__), PLONK_ERR_ARG);
+  const uint32_t nwaves = kze_fold_waves(a.n);
+  // R''^2 / R = (R'' / R) in twiddle form; R'' / R = 2^5 (poly_batch_inverse's constant)
+  hipLaunchKernelGGL(kze_fold_kernel, dim3(kze_fold_blocks(a.n)), dim3(KZE_FOLD_T), 0, c->stream, a, tw_of(a.z), tw_of(Fr::from_u64(32)),
+                     tw_plain(Fr::one()), tw_of(Fr::one()), nwaves);
+  hipLaunchKernelGGL(kze_final_kernel, dim3(a.count), dim3(256), 0, c->stream, (const Fr*)a.partial, nwaves, a.scale, evals);
+  HIP_TRY(hipGetLastError());
+  return PLONK_OK;
+}
+
+int kze_quotient(Ctx* c, uint32_t log_n, const Fr* fold, const Fr* inv, const Fr& Y, uint64_t m, Fr* q, Fr* qpart) {
+  const uint64_t n = 1ull << log_n;
+  if (m != KZE_NONE && m >= n) return (set_last_error("invalid argument", __func__, __FILE__, __LINE__), PLONK_ERR_ARG);
+  const Fr w = kze_root(log_n);
+  const uint32_t blocks = kze_quotient_blocks(n);
+  hipLaunchKernelGGL(kze_quotient_kernel, dim3(blocks), dim3(KZE_Q_T), 0, c->stream, fold, inv, Y, n, w, m != KZE_NONE ? 1 : 0, q, qpart);
+  if (m != KZE_NONE)
+    hipLaunchKernelGGL(kze_qfix_kernel, dim3(1), dim3(256), 0, c->stream, (const Fr*)qpart, blocks, w.pow_u64(m).inv().neg(), m, q);
+  HIP_TRY(hipGetLastError());
+  return PLONK_OK;
+}
+
+// ---- the state a handle holds for these calls ------------------------------------------------------------------------------
+namespace {
+
+struct KzgEvals {
+  enum { DEN, FOLD, Q, PARTIAL, EVALS, VPOW, VECS, META, QPART, NBUF };   // grow-only
+  void* p[NBUF] = {};
+  uint64_t cap[NBUF] = {};
+  G1Affine* lag = nullptr;      // [L_i(tau)] G, i < n
+  uint64_t lag_bytes = 0;
+  plonk_kzg_evals_info last = {};
+  ~KzgEvals() {
+    (void)hipFree(lag);
+    for (int i = 0; i < NBUF; ++i) (void)hipFree(p[i]);
+  }
+  int need(int i, uint64_t bytes) {
+    if (bytes <= cap[i]) return PLONK_OK;
+    (void)hipFree(p[i]);
+    p[i] = nullptr;
+    cap[i] = 0;
+    HIP_TRY(hipMalloc(&p[i], bytes));
+    cap[i] = bytes;
+    return PLONK_OK;
+  }
+  template <class T>
+  T* at(int i) const { return (T*)p[i]; }
+};
+
+KzgEvals* kze_state(const KzdView& v) {
+  if (!*v.evals) *v.evals = new KzgEvals();
+  return (KzgEvals*)*v.evals;
+}
+
+void identity48(uint8_t out[48]) {
+  memset(out, 0, 48);
+  out[0] = 0xC0;
+}
+
+// the points, built by the first call that commits
+int lagrange_ready(const KzdView& v, KzgEvals* e, uint32_t* built) {
+  if (e->lag) return PLONK_OK;
+  const uint64_t bytes = KZE_POINT_BYTES << v.log_n;
+  G1Affine* pts = nullptr;
+  HIP_TRY(hipMalloc((void**)&pts, bytes));
+  const int rc = kze_lagrange_points(v.c, v.log_n, v.tw, v.log_n + 1, pts);
+  if (rc != PLONK_OK) {
+    (void)hipFree(pts);
+    return rc;
+  }
+  e->lag = pts;
+  e->lag_bytes = bytes;
+  *built = 1;
+  return PLONK_OK;
+}
+
+// sum_i s[i] [L_i(tau)] G as 48 compressed bytes (returns with the stream synchronised); plonk_ctx_last_msm_points keeps
+// reporting the caller's own last call
+int commit_values(Ctx* c, const KzgEvals* e, const Fr* s, uint64_t n, uint8_t out48[48]) {
+  const plonk_msm_points_info keep = c->last_points;
+  const bool keep_valid = c->last_points_valid;
+  MpInput in;
+  in.points = reinterpret_cast<const uint8_t*>(e->lag);
+  in.scalars = s;
+  G1 sum;
+  const int rc = msm_points_run(c, in, n, nullptr, &sum);
+  c->last_points = keep;
+  c->last_points_valid = keep_valid;
+  PTRY_E(rc);
+  uint8_t aff[1][97];
+  batch_xyzz_to_affine97(&sum, 1, aff);
+  g1_compress97(aff[0], out48);
+  return PLONK_OK;
+}
+
+// The call's vectors made resident group after group, `per` at most at a time: fn(first, cnt, ptrs) runs with ptrs[k] the
+// device address of vector first + k.  The resident form passes the caller's pointers through; the host form packs a group
+// into one of the context's two upload buffers, the upload of group g + 1 (copy stream) queued under what fn queued for group
+// g (main stream); a buffer is reused once the work that read it has finished.
+template <class F>
+int for_groups(Ctx* c, const void* const* vecs, uint64_t count, uint64_t n, bool resident, const KzePlan& plan, F fn) {
+  const uint32_t per = (uint32_t)plan.group_vectors;
+  std::vector<const Fr*> ptrs(per);
+  if (resident) {
+    for (uint64_t first = 0; first < count; first += per) {
+      const uint32_t cnt = (uint32_t)(count - first < per ? count - first : per);
+      for (uint32_t k = 0; k < cnt; ++k) ptrs[k] = (const Fr*)vecs[first + k];
+      PTRY_E(fn((uint32_t)first, cnt, ptrs.data()));
+    }
+    return PLONK_OK;
+  }
+  Fr* stage[2];
+  hipEvent_t up[2], done[2];
+  PTRY_E(kzg_stage_reserve(c, plan.stage_values, stage, up, done));
+  HIP_TRY(hipStreamSynchronize(c->stream));   // the copy stream is not ordered behind what the main stream still runs
+  uint64_t g = 0;
+  for (uint64_t first = 0; first < count; first += per, ++g) {
+    const int b = (int)(g & 1);
+    const uint32_t cnt = (uint32_t)(count - first < per ? count - first : per);
+    if (g >= 2) HIP_TRY(hipStreamWaitEvent(c->copy_stream, done[b], 0));
+    for (uint32_t k = 0; k < cnt; ++k) {
+      ptrs[k] = stage[b] + (uint64_t)k * n;
+      HIP_TRY(hipMemcpyAsync((void*)ptrs[k], vecs[first + k], sizeof(Fr) * n, hipMemcpyHostToDevice, c->copy_stream));
+    }
+    HIP_TRY(hipEventRecord(up[b], c->copy_stream));
+    HIP_TRY(hipStreamWaitEvent(c->stream, up[b], 0));
+    PTRY_E(fn((uint32_t)first, cnt, ptrs.data()));
+    HIP_TRY(hipEventRecord(done[b], c->stream));
+  }
+  return PLONK_OK;
+}
+
+struct EvalsCall {
+  const void* const* vecs;
+  uint64_t count;
+  bool resident;
+  bool open;                 // plonk_kzg_open_evals (false: plonk_kzg_commit_evals)
+  Fr z, v;
+  uint64_t* evaluations;
+  uint8_t* commitments48;
+  uint8_t* witness48;
+};
+
+int evals_body(const char* api_fn, const KzdView& dv, KzgEvals* e, const EvalsCall& a) {
+  Ctx& c = *dv.c;
+  const uint32_t L = dv.log_n;
+  const uint64_t n = 1ull << L, count = a.count;
+  const bool in_domain = a.open && kze_in_domain(a.z, L);
+  const KzePlan plan = kze_plan(L, count, a.commitments48 != nullptr, a.witness48 != nullptr, !a.resident);
+  plonk_kzg_evals_info info = {};
+  info.log_n = L;
+  info.count = count;
+  info.in_domain_index = KZE_NONE;
+  info.msm_launches = plan.msm_launches;
+  info.msm_terms = plan.msm_terms;
+  // ---- checks that need the device: canonical values of the resident form, the lane m ----
+  PTRY_E(e->need(KzgEvals::META, sizeof(KzeMeta)));
+  PTRY_E(e->need(KzgEvals::VECS, sizeof(Fr*) * count));
+  if (a.open) PTRY_E(e->need(KzgEvals::DEN, sizeof(Fr) * n));
+  KzeMeta mh = {KZE_NONE, 0};
+  if (a.resident || in_domain) {
+    HIP_TRY(hipMemcpyAsync(e->p[KzgEvals::META], &mh, sizeof mh, hipMemcpyHostToDevice, c.stream));
+    if (a.resident) {
+      HIP_TRY(hipMemcpyAsync(e->p[KzgEvals::VECS], a.vecs, sizeof(Fr*) * count, hipMemcpyHostToDevice, c.stream));
+      for (uint64_t first = 0; first < count; first += 32768)   // grid.y
+        PTRY_E(kze_scan(&c, e->at<const Fr*>(KzgEvals::VECS), (uint32_t)first, (uint32_t)(count - first < 32768 ? count - first : 32768), n,
+                        e->at<KzeMeta>(KzgEvals::META)));
+    }
+    if (a.open) PTRY_E(kze_denominators(&c, L, a.z, e->at<Fr>(KzgEvals::DEN), e->at<KzeMeta>(KzgEvals::META)));
+    HIP_TRY(hipMemcpyAsync(&mh, e->p[KzgEvals::META], sizeof mh, hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    if (mh.bad) KZE_FAIL(PLONK_ERR_DATA, "a value is not a canonical residue");
+    if (in_domain != (mh.m != KZE_NONE) || (in_domain && mh.m >= n)) KZE_FAIL(PLONK_ERR_STATE, "the device and the host disagree on whether the point lies in the domain");
+  } else if (a.open) {
+    PTRY_E(kze_denominators(&c, L, a.z, e->at<Fr>(KzgEvals::DEN), e->at<KzeMeta>(KzgEvals::META)));
+  }
+  info.in_domain_index = mh.m;
+  // ---- from here on the call writes ----
+  if (plan.msm_launches) PTRY_E(lagrange_ready(dv, e, &info.built_points));
+  if (!a.open) {
+    PTRY_E(for_groups(&c, a.vecs, count, n, a.resident, plan, [&](uint32_t first, uint32_t cnt, const Fr* const* ptrs) -> int {
+      for (uint32_t k = 0; k < cnt; ++k) PTRY_E(commit_values(&c, e, ptrs[k], n, a.commitments48 + 48ull * (first + k)));
+      return PLONK_OK;
+    }));
+    info.lagrange_bytes = e->lag_bytes;
+    e->last = info;
+    return PLONK_OK;
+  }
+  const uint32_t nwaves = kze_fold_waves(n);
+  PTRY_E(e->need(KzgEvals::FOLD, sizeof(Fr) * n));
+  PTRY_E(e->need(KzgEvals::PARTIAL, sizeof(Fr) * KZE_GROUP * nwaves));
+  PTRY_E(e->need(KzgEvals::EVALS, sizeof(Fr) * count));
+  PTRY_E(e->need(KzgEvals::VPOW, sizeof(Fr29Slot) * count));
+  PTRY_E(poly_batch_inverse(&c, e->at<Fr>(KzgEvals::DEN), n));
+  PTRY_E(poly_kzg_powers(&c, e->p[KzgEvals::VPOW], (uint32_t)count, a.v));
+  KzeFoldArgs fa;
+  fa.vecs = e->at<const Fr*>(KzgEvals::VECS);
+  fa.vpow = e->p[KzgEvals::VPOW];
+  fa.n = n;
+  fa.inv = e->at<Fr>(KzgEvals::DEN);
+  fa.m = mh.m;
+  fa.fold = e->at<Fr>(KzgEvals::FOLD);
+  fa.partial = e->at<Fr>(KzgEvals::PARTIAL);
+  fa.z = a.z;
+  fa.scale = kze_eval_scale(a.z, L);
+  std::vector<const Fr*> staged(a.resident ? 0 : count);   // the host form's device addresses, alive until the call's last copy has run
+  PTRY_E(for_groups(&c, a.vecs, count, n, a.resident, plan, [&](uint32_t first, uint32_t cnt, const Fr* const* ptrs) -> int {
+    if (!a.resident) {
+      for (uint32_t k = 0; k < cnt; ++k) staged[first + k] = ptrs[k];
+      HIP_TRY(hipMemcpyAsync(e->at<const Fr*>(KzgEvals::VECS) + first, staged.data() + first, sizeof(Fr*) * cnt, hipMemcpyHostToDevice, c.stream));
+    }
+    fa.first = first;
+    fa.count = cnt;
+    fa.accumulate = first ? 1 : 0;
+    PTRY_E(kze_fold_eval(&c, fa, e->at<Fr>(KzgEvals::EVALS) + first));
+    if (a.commitments48)
+      for (uint32_t k = 0; k < cnt; ++k) PTRY_E(commit_values(&c, e, ptrs[k], n, a.commitments48 + 48ull * (first + k)));
+    return PLONK_OK;
+  }));
+  std::vector<Fr> y(count);
+  HIP_TRY(hipMemcpyAsync(y.data(), e->p[KzgEvals::EVALS], sizeof(Fr) * count, hipMemcpyDeviceToHost, c.stream));
+  HIP_TRY(hipStreamSynchronize(c.stream));
+  if (a.witness48) {
+    Fr Y = Fr::zero(), vp = Fr::one();
+    for (uint64_t j = 0; j < count; ++j) {
+      Y = Y + vp * y[j];
+      vp = vp * a.v;
+    }
+    PTRY_E(e->need(KzgEvals::Q, sizeof(Fr) * n));
+    PTRY_E(e->need(KzgEvals::QPART, sizeof(Fr) * kze_quotient_blocks(n)));
+    PTRY_E(kze_quotient(&c, L, e->at<Fr>(KzgEvals::FOLD), e->at<Fr>(KzgEvals::DEN), Y, mh.m, e->at<Fr>(KzgEvals::Q), e->at<Fr>(KzgEvals::QPART)));
+    PTRY_E(commit_values(&c, e, e->at<Fr>(KzgEvals::Q), n, a.witness48));
+  }
+  memcpy(a.evaluations, y.data(), sizeof(Fr) * count);
+  info.lagrange_bytes = e->lag_bytes;
+  e->last = info;
+  return PLONK_OK;
+}
+
+int evals_impl(const char* api_fn, plonk_kzg_domain* dom, const void* const* vecs, uint64_t count, bool resident, bool open,
+               const uint64_t* point, const uint64_t* v_challenge, uint64_t* evaluations, uint8_t* commitments48, uint8_t* witness48) {
+  const int arg = open ? kze_check_open(dom != nullptr, vecs != nullptr, point != nullptr, v_challenge != nullptr, evaluations != nullptr, count)
+                       : kze_check_commit(dom != nullptr, vecs != nullptr, commitments48 != nullptr, count);
+  if (arg != PLONK_OK) KZE_FAIL(PLONK_ERR_ARG, count > KZE_MAX_COUNT ? "invalid argument: at most 65536 vectors per call"
+                                                                      : "invalid argument: a required pointer is NULL");
+  for (uint64_t i = 0; i < count; ++i)
+    if (!vecs[i]) KZE_FAIL(PLONK_ERR_ARG, "invalid argument: evals[i] is NULL");
+  EvalsCall a = {vecs, count, resident, open, Fr::zero(), Fr::one(), evaluations, commitments48, witness48};
+  if (open && (!kzg_fr_load(point, &a.z) || (v_challenge && !kzg_fr_load(v_challenge, &a.v)))) KZE_FAIL(PLONK_ERR_DATA, "non-canonical scalar");
+  const KzdView dv = kzd_view(dom);
+  Ctx& c = *dv.c;
+  CTX_ENTER(c, api_fn);
+  HIP_TRY(hipSetDevice(c.device));
+  if (!dv.key_current) KZE_FAIL(PLONK_ERR_STATE, "the domain is bound to a commit key that was replaced on its context");
+  if (c.nccl_comm) KZE_FAIL(PLONK_ERR_STATE, "a context with a communicator holds only a range of the commit key");
+  if (!resident) {   // before anything is queued or written
+    Fr t;
+    for (uint64_t i = 0; i < count; ++i)
+      for (uint64_t k = 0; k < (1ull << dv.log_n); ++k)
+        if (!kzg_fr_load((const uint64_t*)vecs[i] + 4 * k, &t)) KZE_FAIL(PLONK_ERR_DATA, "a value is not a canonical residue");
+  }
+  KzgEvals* e = kze_state(dv);
+  if (!count) {
+    if (witness48) identity48(witness48);
+    plonk_kzg_evals_info info = {};
+    info.log_n = dv.log_n;
+    info.in_domain_index = KZE_NONE;
+    info.msm_terms = 1ull << dv.log_n;
+    info.lagrange_bytes = e->lag_bytes;
+    e->last = info;
+    return PLONK_OK;
+  }
+  const int rc = evals_body(api_fn, dv, e, a);
+  if (rc != PLONK_OK) {   // an error leaves nothing of the call queued
+    if (c.copy_stream) (void)hipStreamSynchronize(c.copy_stream);
+    (void)hipStreamSynchronize(c.stream);
+  }
+  return rc;
+}
+
+}  // namespace
+
+void kze_release(void* evals) { delete (KzgEvals*)evals; }
+
+}  // namespace plonk
+
+using namespace plonk;
+
+extern "C" {
+
+int plonk_kzg_commit_evals(plonk_kzg_domain* dom, const uint64_t* const* evals, uint64_t count, uint8_t* commitments48) {
+  const char* const api_fn = __func__;
+  return plonk::api_guard(api_fn, [&]() -> int {
+    return plonk::evals_impl(api_fn, dom, (const void* const*)evals, count, false, false, nullptr, nullptr, nullptr, commitments48, nullptr);
+  });
+}
+
+int plonk_kzg_commit_evals_dev(plonk_kzg_domain* dom, const void* const* evals_dev, uint64_t count, uint8_t* commitments48) {
+  const char* const api_fn = __func__;
+  return plonk::api_guard(api_fn, [&]() -> int {
+    return plonk::evals_impl(api_fn, dom, evals_dev, count, true, false, nullptr, nullptr, nullptr, commitments48, nullptr);
+  });
+}
+
+int plonk_kzg_open_evals(plonk_kzg_domain* dom, const uint64_t* const* evals, uint64_t count, const uint64_t point[4],
+                         const uint64_t* v_challenge, uint64_t* evaluations, uint8_t* commitments48, uint8_t* witness48) {
+  const char* const api_fn = __func__;
+  return plonk::api_guard(api_fn, [&]() -> int {
+    return plonk::evals_impl(api_fn, dom, (const void* const*)evals, count, false, true, point, v_challenge, evaluations, commitments48,
+                             witness48);
+  });
+}
+
+int plonk_kzg_open_evals_dev(plonk_kzg_domain* dom, const void* const* evals_dev, uint64_t count, const uint64_t point[4],
+                             const uint64_t* v_challenge, uint64_t* evaluations, uint8_t* commitments48, uint8_t* witness48) {
+  const char* const api_fn = __func__;
+  return plonk::api_guard(api_fn, [&]() -> int {
+    return plonk::evals_impl(api_fn, dom, evals_dev, count, true, true, point, v_challenge, evaluations, commitments48, witness48);
+  });
+}
+
+int plonk_kzg_evals_last(plonk_kzg_domain* dom, plonk_kzg_evals_info* out) {
+  const char* const api_fn = __func__;
+  return plonk::api_guard(api_fn, [&]() -> int {
+  if (!dom || !out) KZE_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
+  const KzdView dv = kzd_view(dom);
+  Ctx& c = *dv.c;
+  CTX_ENTER(c, api_fn);
+  if (!dv.key_current) KZE_FAIL(PLONK_ERR_STATE, "the domain is bound to a commit key that was replaced on its context");
+  const KzgEvals* e = (const KzgEvals*)*dv.evals;
+  plonk_kzg_evals_info info = {};
+  info.log_n = dv.log_n;
+  info.in_domain_index = KZE_NONE;
+  info.msm_terms = 1ull << dv.log_n;
+  if (e) {
+    info = e->last.log_n ? e->last : info;
+    info.lagrange_bytes = e->lag_bytes;
+  }
+  *out = info;
+  return PLONK_OK;
+  });
+}
+
+}  // extern "C"

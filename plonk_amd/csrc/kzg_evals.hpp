@@ -1,0 +1,53 @@
+// Launchers of kzg_evals.hip: the scalar stage of KZG10 in evaluation form and the Lagrange points it commits over.  Shared
+// with the doors of the per-kernel tests (tests/csrc/dev_kzg_evals.hip).  Every pointer is device memory unless said
+// otherwise, everything is queued on the context's stream, nothing synchronises (kze_lagrange_points does: it frees its
+// workspace).
+#pragma once
+#include "plonk_internal.hpp"
+#include "curve28.cuh"
+#include "kzg_evals_core.hpp"
+
+namespace plonk {
+
+struct KzeMeta {              // what the host reads back before anything else of a call is queued
+  unsigned long long m;       // the lane with w^m == z (KZE_NONE: none)
+  unsigned long long bad;     // != 0: a resident value is not a canonical residue
+};
+
+// den[i] = w^i - z, i < n = 2^log_n; meta->m = the lane where that is zero (the caller presets KZE_NONE)
+int kze_denominators(Ctx* c, uint32_t log_n, const Fr& z, Fr* den, KzeMeta* meta);
+// meta->bad |= 1 when one of the n values of vecs[first .. first + cnt) is >= q
+int kze_scan(Ctx* c, const Fr* const* vecs, uint32_t first, uint32_t cnt, uint64_t n, KzeMeta* meta);
+
+struct KzeFoldArgs {
+  const Fr* const* vecs;   // device table of the call's vectors; the launch covers vecs[first, first + count), count <= KZE_GROUP
+  const void* vpow;        // v^j, j < (all vectors of the call), twiddle form (Fr29Slot, poly_kzg_powers)
+  uint32_t first, count;
+  uint64_t n;
+  int accumulate;          // 0: fold[i] = sum; 1: fold[i] += sum
+  const Fr* inv;           // 1 / (w^i - z), 0 at lane m
+  uint64_t m;              // KZE_NONE: z outside the domain
+  Fr* fold;                // n
+  Fr* partial;             // [count][kze_fold_waves(n)]
+  Fr z, scale;             // scale: kze_eval_scale
+};
+// fold += sum_j v^j e_j and evals[j] = y_(first + j), j < count: one pass over the values
+int kze_fold_eval(Ctx* c, const KzeFoldArgs& a, Fr* evals);
+// q[i] = (fold[i] - Y) inv[i]; with m != KZE_NONE also q[m] = -w^(-m) sum_(i != m) q[i] w^i (qpart: kze_quotient_blocks(n) values)
+int kze_quotient(Ctx* c, uint32_t log_n, const Fr* fold, const Fr* inv, const Fr& Y, uint64_t m, Fr* q, Fr* qpart);
+// out[i] = [L_i(tau)] G, i < n, as affine x || y (96 zero bytes: the identity) from row 0 of the context's commit-key tables
+// (n points are enough); tw: kzd_twiddles_create's table for tw_log > log_n.  Returns with the stream synchronised.
+int kze_lagrange_points(Ctx* c, uint32_t log_n, const GlvScalar* tw, uint32_t tw_log, G1Affine* out);
+
+// kzg_domain.hip: what the evaluation-form calls need of a handle
+struct KzdView {
+  Ctx* c;
+  uint32_t log_n;
+  bool key_current;        // the context still holds the commit key the handle was built on
+  const GlvScalar* tw;     // w_(2n)^e, e < n
+  void** evals;            // the handle's slot for the state of kzg_evals.hip, released through kze_release
+};
+KzdView kzd_view(plonk_kzg_domain* dom);
+void kze_release(void* evals);
+
+}  // namespace plonk

@@ -376,6 +376,8 @@ int pairing_each_launch(Ctx* c, const void* tables, const G1* pairs, const int32
 int each_finish(Ctx* c, const int32_t* verdict_dev, const int32_t* pre_dev, uint64_t count, int32_t* verdicts, uint32_t* checked,
                 uint32_t* rejected);
 void kzg_ws_release(Ctx* c);                          // kzg.hip: frees the opening workspace of the context
+// kzg.hip: the two upload buffers of the host forms grown to `values` Fr each, their events, and the copy stream created
+int kzg_stage_reserve(Ctx* c, uint64_t values, Fr* stage[2], hipEvent_t up[2], hipEvent_t done[2]);
 // msm_points.hip: sum_i s_i P_i over points that are not the commit key, by the bucket method (or, below
 // opts.min_bucket_terms terms, by verify.hip's per-term kernel).  The terms come in one of two layouts:
 //   caller layout   points (m x 96 raw bytes, or m x 48 compressed) + Montgomery scalars: plonk_msm_points / _dev
