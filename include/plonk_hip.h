@@ -826,6 +826,63 @@ int plonk_kzg_open_evals_dev(plonk_kzg_domain* domain, const void* const* evals_
                              const uint64_t* v_challenge, uint64_t* evaluations, uint8_t* commitments48, uint8_t* witness48);
 int plonk_kzg_evals_last(plonk_kzg_domain* domain, plonk_kzg_evals_info* out);
 
+/* ---- KZG10 cell proofs: a polynomial opened on every coset of its domain --------------------------------
+ * The n = 2^log_n evaluations of a polynomial cut into r = n / l cells of l = 2^log_cell values, each cell with ONE 48-byte
+ * proof that opens all l of its values at once (Feist-Khovratovich section 3; data-availability sampling).  w is the generator
+ * plonk_ntt uses for size n, phi = w^l, s_i = [tau^i] g the commit key, f_0 .. f_(n-1) the zero-padded coefficients:
+ *     cell k (k < r) = the coset { w^(k + r j) : j < l }, with vanishing polynomial X^l - x_k,  x_k = phi^k = w^(l k)
+ *     cells[k l + j] = f(w^(k + r j))        cell-major: the forward NTT of f read as an l x r matrix and transposed
+ *     proofs[k] = commit(q_k),  f = q_k (X^l - x_k) + r_k,  deg r_k < l
+ *     r_k has the coefficients c_j = sum_t f_(j + t l) x_k^t = w^(-k j) * (the size-l inverse NTT of cell k's values)_j
+ *   computed as proofs = DFT_r(H), H_m = sum_j f_(j + (m+1) l) s_j, the sum over u < l of the Toeplitz products of
+ *   plonk_kzg_open_domain at size r:  A^(u) = DFT_2r(s_u, s_(u+l) .. s_(u+l(r-2)), O ...) (per handle and cell size);
+ *   G^(u) = NTT_2r(f_(u+l(r-1)) .. f_(u+l), 0 ...);  P_i = sum_u [G^(u)_i / 2r] A^(u)_i;  c = DFT_2r^-1(P);
+ *   H_m = c_(r-2-m) (m <= r-2), H_(r-1) = O                                                          
+ *   A VERIFIER checks cell k with  e(proofs[k], [tau^l] h) == e(C - commit(r_k) + x_k proofs[k], h):  with an opening key whose
+ *   third element is [tau^l] h instead of [tau] h that is plonk_kzg_pairing_check_each(key_l, A = proofs[k],
+ *   B = C - commit(r_k) + x_k proofs[k]), C the commitment and r_k from the cell's values by the formula above.  The library
+ *   has no device-side cell verifier.
+ * plonk_kzg_open_cells: `count` polynomials in coefficient form (host pointers; lengths may differ).  cells: count x n x 4
+ *   limbs, Montgomery, cell-major; proofs48: count x r x 48 bytes, compressed G1, encoded on the device; commitments48:
+ *   count x 48 through the ordinary commitment path, NULL skips them.  A polynomial of fewer than l + 1 coefficients has r
+ *   compressed identities as proofs (and c_j = f_j).  Checks, in this order: PLONK_ERR_ARG for a NULL domain, log_cell
+ *   outside [1, log_n - 1] (so a handle of log_n = 1 has no cell size), count > 65536, a NULL polys / lens / cells / proofs48
+ *   with count > 0, polys[i] NULL with lens[i] > 0; PLONK_ERR_STATE once the context's key was reloaded, and on a context
+ *   with a communicator; count == 0 is PLONK_OK and writes nothing; lengths are judged WITHOUT trailing zeros: a coefficient
+ *   that is not a canonical residue is PLONK_ERR_DATA, then more than n coefficients is PLONK_ERR_DEGREE.  Every check is
+ *   made before anything is queued or written: an error leaves nothing queued and none of the three outputs touched.
+ *   The first call with a cell size builds its A^(u) (2n slots of 256 bytes) and the handle keeps them until it is destroyed;
+ *   the point workspace (S x 2r slots per polynomial of a chunk, S the slice count of the accumulate) stays under the
+ *   handle's workspace cap, chunked as plonk_kzg_open_domain chunks.  Neither plonk_kzg_domain_info nor
+ *   plonk_kzg_domain_last counts any of this memory; plonk_kzg_cells_last does.  The calls leave the context, its tables,
+ *   its provers and the handle's other entry points as they found them.
+ * plonk_kzg_open_cells_dev: polys_dev is a HOST array of `count` device pointers; the three outputs are device pointers on
+ *   the context's GPU.
+ * plonk_kzg_cell_points: x[k] = x_k = w^(l k) and shift[k] = w^k (NULL skips it), k < r, Montgomery: cell k is shift[k] times
+ *   the size-l subgroup.  PLONK_ERR_ARG / PLONK_ERR_STATE as above.
+ * plonk_kzg_cells_last: what the last plonk_kzg_open_cells call on the handle ran as (count == 0 before the first): the
+ *   tests assert it against the plan computed on the host (plonk_amd/csrc/kzg_cells_core.hpp). */
+typedef struct plonk_kzg_cells_info {
+  uint32_t log_n;
+  uint32_t log_cell;               /* cell size of the last call */
+  uint32_t chunks;                 /* chunks the polynomials of the last call were processed in */
+  uint32_t built_table;            /* 1: this call built the A^(u) of its cell size */
+  uint64_t count;                  /* polynomials of the last call */
+  uint64_t slices;                 /* S: lanes per position of the accumulate, each with l / S terms */
+  uint64_t chunk_polys;            /* polynomials per chunk (the last chunk may be shorter) */
+  uint64_t workspace_bytes;        /* point workspace of the call: S x 2r slots per polynomial of a chunk */
+  uint64_t table_bytes;            /* bytes of all A^(u) tables the handle holds: 2n x 256 per cell size used */
+  uint64_t stage_launches;         /* group-FFT stage launches: (2 log r + 1) per chunk */
+  uint64_t scalar_muls;            /* full-width scalar multiplications issued: 2n in the accumulate + the butterflies whose twiddle is not 1 */
+} plonk_kzg_cells_info;
+int plonk_kzg_open_cells(plonk_kzg_domain* domain, uint32_t log_cell, const uint64_t* const* polys, const uint64_t* lens, uint64_t count,
+                         uint64_t* cells /* count x n x 4, cell-major, Montgomery */, uint8_t* proofs48 /* count x r x 48 */,
+                         uint8_t* commitments48 /* count x 48, or NULL */);
+int plonk_kzg_open_cells_dev(plonk_kzg_domain* domain, uint32_t log_cell, const void* const* polys_dev, const uint64_t* lens, uint64_t count,
+                             void* cells_dev, void* proofs48_dev, void* commitments48_dev /* or NULL */);
+int plonk_kzg_cell_points(plonk_kzg_domain* domain, uint32_t log_cell, uint64_t* x /* r x 4: w^(l k) */, uint64_t* shift /* r x 4: w^k, or NULL */);
+int plonk_kzg_cells_last(plonk_kzg_domain* domain, plonk_kzg_cells_info* out);
+
 /* ---- variable-base MSM over caller-supplied points ------------------------------------------------
  * sum_i scalars[i] * P_i for points the CALLER brings — the reference's msm_variable_base (the primitive under Proof::verify
  * and OpeningKey::batch_check) — where plonk_msm / _batch / _dev run over the loaded commit key and its precomputed tables.

@@ -77,6 +77,7 @@ EXPORTS = [
     "plonk_kzg_open_domain_dev", "plonk_kzg_domain_last",
     "plonk_kzg_commit_evals", "plonk_kzg_commit_evals_dev", "plonk_kzg_open_evals", "plonk_kzg_open_evals_dev",
     "plonk_kzg_evals_last",
+    "plonk_kzg_open_cells", "plonk_kzg_open_cells_dev", "plonk_kzg_cell_points", "plonk_kzg_cells_last",
 ]
 
 # what bit f of plonk_unsat_row.families / slot f of plonk_unsat_info.family_rows stands for (include/plonk_hip.h); the
@@ -157,6 +158,14 @@ class _KzgEvalsInfo(ctypes.Structure):
     _fields_ = [("log_n", ctypes.c_uint32), ("built_points", ctypes.c_uint32), ("count", ctypes.c_uint64),
                 ("in_domain_index", ctypes.c_uint64), ("msm_launches", ctypes.c_uint64), ("msm_terms", ctypes.c_uint64),
                 ("lagrange_bytes", ctypes.c_uint64)]
+
+
+class _KzgCellsInfo(ctypes.Structure):
+    """plonk_kzg_cells_info (include/plonk_hip.h)"""
+    _fields_ = [("log_n", ctypes.c_uint32), ("log_cell", ctypes.c_uint32), ("chunks", ctypes.c_uint32), ("built_table", ctypes.c_uint32),
+                ("count", ctypes.c_uint64), ("slices", ctypes.c_uint64), ("chunk_polys", ctypes.c_uint64),
+                ("workspace_bytes", ctypes.c_uint64), ("table_bytes", ctypes.c_uint64), ("stage_launches", ctypes.c_uint64),
+                ("scalar_muls", ctypes.c_uint64)]
 
 
 class _ProverInfo(ctypes.Structure):
@@ -432,6 +441,10 @@ def load_library() -> ctypes.CDLL:
     lib.plonk_kzg_open_evals.argtypes = [vp, ctypes.POINTER(vp), u64, vp, vp, vp, vp, vp]
     lib.plonk_kzg_open_evals_dev.argtypes = [vp, ctypes.POINTER(vp), u64, vp, vp, vp, vp, vp]
     lib.plonk_kzg_evals_last.argtypes = [vp, ctypes.POINTER(_KzgEvalsInfo)]
+    lib.plonk_kzg_open_cells.argtypes = [vp, u32, ctypes.POINTER(vp), ctypes.POINTER(u64), u64, vp, vp, vp]
+    lib.plonk_kzg_open_cells_dev.argtypes = [vp, u32, ctypes.POINTER(vp), ctypes.POINTER(u64), u64, vp, vp, vp]
+    lib.plonk_kzg_cell_points.argtypes = [vp, u32, vp, vp]
+    lib.plonk_kzg_cells_last.argtypes = [vp, ctypes.POINTER(_KzgCellsInfo)]
     _lib = lib
     return lib
 
@@ -1697,6 +1710,56 @@ class KzgDomain:
     def evals_last(self) -> dict:
         info = _KzgEvalsInfo()
         self.ctx._check(self.ctx.lib.plonk_kzg_evals_last(self.handle, ctypes.byref(info)))
+        return {k: getattr(info, k) for k, _ in info._fields_}
+
+    # ---- cell proofs: one proof per coset of l = 2^log_cell values ----
+    def open_cells_bytes(self, polys_bytes, log_cell: int, commitments: bool = True):
+        """plonk_kzg_open_cells on Montgomery bytes (32 per coefficient) -> (cell-value bytes, proof bytes, commitment bytes or
+        None), each the concatenation over the polynomials"""
+        bufs = [bytes(b) for b in polys_bytes]
+        count = len(bufs)
+        r = self.n >> log_cell if 0 <= log_cell < 64 else 0
+        keep = [ctypes.create_string_buffer(b, len(b)) if b else None for b in bufs]
+        parr = (ctypes.c_void_p * max(count, 1))(*[ctypes.cast(k, ctypes.c_void_p).value if k is not None else None for k in keep])
+        larr = (ctypes.c_uint64 * max(count, 1))(*[len(b) // 32 for b in bufs])
+        cells = ctypes.create_string_buffer(max(32 * self.n * count, 1))
+        proofs = ctypes.create_string_buffer(max(48 * r * count, 1))
+        cm = ctypes.create_string_buffer(max(48 * count, 1)) if commitments else None
+        self.ctx._check(self.ctx.lib.plonk_kzg_open_cells(self.handle, log_cell, parr, larr, count, cells, proofs, cm))
+        return cells.raw[:32 * self.n * count], proofs.raw[:48 * r * count], cm.raw[:48 * count] if commitments else None
+
+    def open_cells(self, polys, log_cell: int, commitments: bool = True):
+        """polys: coefficient lists of ints, or Montgomery bytes -> (cells[j][k] (the l values of cell k: f(w^(k + r i)), i < l),
+        proofs[j][k] (48 bytes each), commitments[j] or None); cell k and proof k belong to cell_points(log_cell)[0][k]"""
+        bufs = [p if isinstance(p, (bytes, bytearray)) else fr_to_bytes_mont(p) for p in polys]
+        cells, proofs, cm = self.open_cells_bytes(bufs, log_cell, commitments)
+        n, count, l = self.n, len(bufs), 1 << log_cell
+        r = n >> log_cell
+        vals = fr_from_bytes_mont(cells)
+        return ([[vals[j * n + k * l:j * n + (k + 1) * l] for k in range(r)] for j in range(count)],
+                [[proofs[48 * (j * r + k):48 * (j * r + k + 1)] for k in range(r)] for j in range(count)],
+                [cm[48 * j:48 * j + 48] for j in range(count)] if commitments else None)
+
+    def open_cells_dev(self, ptrs, lens, log_cell: int, cells: int, proofs: int, commitments: "int | None" = None):
+        """plonk_kzg_open_cells_dev: polynomials resident in HBM (device pointers, coefficients each); the outputs are device
+        pointers (count x n x 32, count x r x 48, count x 48 bytes or None)"""
+        ptrs, lens = list(ptrs), list(lens)
+        count = len(lens)
+        parr = (ctypes.c_void_p * max(count, 1))(*ptrs)
+        larr = (ctypes.c_uint64 * max(count, 1))(*lens)
+        self.ctx._check(self.ctx.lib.plonk_kzg_open_cells_dev(self.handle, log_cell, parr, larr, count, cells, proofs, commitments))
+
+    def cell_points(self, log_cell: int):
+        """plonk_kzg_cell_points -> (x, shift): x[k] = w^(l k), the constant of cell k's vanishing polynomial X^l - x[k], and
+        shift[k] = w^k, the coset's representative"""
+        r = max(self.n >> log_cell, 1) if 0 <= log_cell < 64 else 1
+        x, sh = ctypes.create_string_buffer(32 * r), ctypes.create_string_buffer(32 * r)
+        self.ctx._check(self.ctx.lib.plonk_kzg_cell_points(self.handle, log_cell, x, sh))
+        return fr_from_bytes_mont(x.raw), fr_from_bytes_mont(sh.raw)
+
+    def cells_last(self) -> dict:
+        info = _KzgCellsInfo()
+        self.ctx._check(self.ctx.lib.plonk_kzg_cells_last(self.handle, ctypes.byref(info)))
         return {k: getattr(info, k) for k, _ in info._fields_}
 
     def _set_workspace_cap(self, nbytes: int):

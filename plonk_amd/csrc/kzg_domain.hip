@@ -31,6 +31,8 @@
 #include "kzg_core.hpp"
 #include "kzg_domain.hpp"
 #include "kzg_evals.hpp"
+#include "kzg_cells.hpp"
+#include "kzg_slot.cuh"
 
 #define PTRY_D(expr) do { int _rc = (expr); if (_rc) return _rc; } while (0)
 #define KZD_FAIL(code, msg) return (plonk::set_last_error(api_fn, msg, __FILE__, __LINE__), code)
@@ -42,87 +44,6 @@ struct plonk_kzg_domain {
 };
 
 namespace plonk {
-
-namespace {
-
-// Fp28 / G1R in memory: each coordinate padded to 16 words (64 B), as the commit-key tables of msm.hip
-struct alignas(16) G1RSlot {
-  Fp28Slot X, Y, ZZ, ZZZ;
-};
-static_assert(sizeof(G1RSlot) == KZD_SLOT_BYTES, "slot size");
-__device__ __forceinline__ Fp28 ld_f28(const Fp28Slot* p) {
-  const uint4* q = reinterpret_cast<const uint4*>(p);
-  const uint4 a = q[0], b = q[1], c = q[2], d = q[3];
-  Fp28 r;
-  r.l[0] = a.x; r.l[1] = a.y; r.l[2] = a.z; r.l[3] = a.w;
-  r.l[4] = b.x; r.l[5] = b.y; r.l[6] = b.z; r.l[7] = b.w;
-  r.l[8] = c.x; r.l[9] = c.y; r.l[10] = c.z; r.l[11] = c.w;
-  r.l[12] = d.x; r.l[13] = d.y;
-  return r;
-}
-__device__ __forceinline__ void st_f28(Fp28Slot* p, const Fp28& v) {
-  uint4* q = reinterpret_cast<uint4*>(p);
-  q[0] = make_uint4(v.l[0], v.l[1], v.l[2], v.l[3]);
-  q[1] = make_uint4(v.l[4], v.l[5], v.l[6], v.l[7]);
-  q[2] = make_uint4(v.l[8], v.l[9], v.l[10], v.l[11]);
-  q[3] = make_uint4(v.l[12], v.l[13], 0u, 0u);
-}
-__device__ __forceinline__ G1R ld_g1r(const G1RSlot* p) {
-  G1R r;
-  r.X = ld_f28(&p->X); r.Y = ld_f28(&p->Y); r.ZZ = ld_f28(&p->ZZ); r.ZZZ = ld_f28(&p->ZZZ);
-  return r;
-}
-__device__ __forceinline__ void st_g1r(G1RSlot* p, const G1R& v) {
-  st_f28(&p->X, v.X); st_f28(&p->Y, v.Y); st_f28(&p->ZZ, v.ZZ); st_f28(&p->ZZZ, v.ZZZ);
-}
-__device__ __forceinline__ G1R g1r_neg(const G1R& p) {   // -P: Y -> 16p - Y (Y < 8p), canonicalised
-  G1R r = p;
-  if (!p.is_identity()) r.Y = Fp28::sub<16>(Fp28::zero(), p.Y).canon();
-  return r;
-}
-__device__ __forceinline__ Fr ld_fr(const Fr* p) {
-  const uint4* q = reinterpret_cast<const uint4*>(p);
-  const uint4 a = q[0], b = q[1];
-  Fr r;
-  r.l[0] = a.x; r.l[1] = a.y; r.l[2] = a.z; r.l[3] = a.w;
-  r.l[4] = b.x; r.l[5] = b.y; r.l[6] = b.z; r.l[7] = b.w;
-  return r;
-}
-__device__ __forceinline__ void st_fr(Fr* p, const Fr& v) {
-  uint4* q = reinterpret_cast<uint4*>(p);
-  q[0] = make_uint4(v.l[0], v.l[1], v.l[2], v.l[3]);
-  q[1] = make_uint4(v.l[4], v.l[5], v.l[6], v.l[7]);
-}
-__device__ __forceinline__ GlvScalar ld_glv(const GlvScalar* p) {
-  const uint4* q = reinterpret_cast<const uint4*>(p);
-  const uint4 a = q[0], b = q[1];
-  GlvScalar g;
-  g.k1[0] = (uint64_t)a.x | ((uint64_t)a.y << 32); g.k1[1] = (uint64_t)a.z | ((uint64_t)a.w << 32);
-  g.k2[0] = (uint64_t)b.x | ((uint64_t)b.y << 32); g.k2[1] = (uint64_t)b.z | ((uint64_t)b.w << 32);
-  return g;
-}
-
-// [k1 + k2 LAMBDA] p for halves that are already split: g1r_mul_glv (curve28.cuh) from its double-and-add on
-__device__ __forceinline__ G1R kzd_mul_split(const G1R& p, const GlvScalar& g) {
-  if (p.is_identity()) return p;
-  G1R p2 = p;
-  p2.X = Fp28::mul(p.X, glv_beta());                          // 16 * 1 -> < 2p
-  const G1R p3 = p.add(p2);
-  G1R acc = G1R::identity();
-  for (int b = 127; b >= 0; --b) {
-    acc = acc.dbl();
-    const uint32_t s = (uint32_t)((g.k1[b >> 6] >> (b & 63)) & 1u) | ((uint32_t)((g.k2[b >> 6] >> (b & 63)) & 1u) << 1);
-    if (s) acc = acc.add(s == 1 ? p : (s == 2 ? p2 : p3));
-  }
-  return acc;
-}
-
-struct KzdDesc {   // a resident polynomial as the scan kernel takes it
-  const Fr* p;
-  uint64_t len;
-};
-
-}  // namespace
 
 __global__ void __launch_bounds__(KZD_LANES) kzd_twiddle_kernel(Fr w, uint64_t count, GlvScalar* __restrict__ out) {
   const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -342,7 +263,9 @@ struct KzgDomain {
   uint64_t ws_cap = KZD_WS_CAP_DEFAULT;
   plonk_kzg_domain_info last = {};
   void* evals = nullptr;         // the Lagrange points and workspace of the evaluation-form calls (kzg_evals.hip); not in device_bytes()
+  void* cells = nullptr;         // the A^(u) tables and workspace of the cell proofs (kzg_cells.hip); not in device_bytes()
   ~KzgDomain() {
+    kzc_release(cells);
     kze_release(evals);
     (void)hipFree(A);
     (void)hipFree(tw);
@@ -368,7 +291,7 @@ struct KzgDomain {
 
 KzdView kzd_view(plonk_kzg_domain* dom) {
   KzgDomain* d = dom->d;
-  return KzdView{d->c, d->log_n, d->srs_gen == d->c->srs_gen, d->tw, &d->evals};
+  return KzdView{d->c, d->log_n, d->srs_gen == d->c->srs_gen, d->tw, &d->evals, &d->cells, d->ws_cap};
 }
 
 static void identity48(uint8_t out[48]) {
@@ -400,7 +323,7 @@ static int domain_create_body(Ctx& c, uint32_t log_n, KzgDomain* d) {
 }
 
 // commitments of the chunk's polynomials (zero-padded rows of f, trimmed lengths m) through the ordinary commitment path
-static int domain_commit(Ctx* c, const Fr* f, uint64_t n, const uint64_t* m, uint32_t cnt, uint8_t* out48) {
+int kzd_commit(Ctx* c, const Fr* f, uint64_t n, const uint64_t* m, uint32_t cnt, uint8_t* out48) {
   const Fr* sc[MSM_MAX_BATCH];
   uint64_t mm[MSM_MAX_BATCH];
   uint32_t which[MSM_MAX_BATCH];
@@ -473,7 +396,7 @@ static int domain_open_body(KzgDomain* d, const void* const* polys, const uint64
     HIP_TRY(hipMemcpyAsync((uint8_t*)witnesses48 + 48 * n * first, out48, 48 * n * cnt, hipMemcpyDefault, c.stream));
     if (commitments48) {
       comm.resize(48ull * cnt);
-      PTRY_D(domain_commit(&c, f, n, trimmed + first, cnt, comm.data()));
+      PTRY_D(kzd_commit(&c, f, n, trimmed + first, cnt, comm.data()));
       HIP_TRY(hipMemcpyAsync((uint8_t*)commitments48 + 48 * first, comm.data(), 48ull * cnt, hipMemcpyDefault, c.stream));
     }
     HIP_TRY(hipStreamSynchronize(c.stream));   // the chunk's buffers are reused by the next one
@@ -481,6 +404,50 @@ static int domain_open_body(KzgDomain* d, const void* const* polys, const uint64
   }
   info.device_bytes = d->device_bytes();
   d->last = info;
+  return PLONK_OK;
+}
+
+// The trimmed lengths of a call's polynomials and the checks that go with them (canonical coefficients: PLONK_ERR_DATA,
+// then more than n coefficients: PLONK_ERR_DEGREE), before anything is written.  The resident form scans on the device
+// (desc_dev: count descriptors, meta_dev: 2 x count words, the caller's) and returns with the stream drained.
+int kzd_lengths(const char* api_fn, Ctx* c, uint32_t log_n, const void* const* polys, const uint64_t* lens, uint64_t count, bool resident,
+                KzdDesc* desc_dev, unsigned long long* meta_dev, uint64_t* trimmed) {
+  // lengths without trailing zeros and the canonical-form check, before anything is queued or written
+  if (resident) {
+    std::vector<KzdDesc> desc(count);
+    for (uint64_t i = 0; i < count; ++i) desc[i] = KzdDesc{(const Fr*)polys[i], lens[i]};
+    std::vector<unsigned long long> meta(2 * count);
+    uint64_t longest = 1;
+    for (uint64_t i = 0; i < count; ++i) longest = lens[i] > longest ? lens[i] : longest;
+    const uint32_t blocks = (uint32_t)((longest + 255) / 256 < 1024 ? (longest + 255) / 256 : 1024);
+    // whatever fails, the stream is drained before the call returns: nothing stays queued
+    hipError_t e = hipMemcpyAsync(desc_dev, desc.data(), sizeof(KzdDesc) * count, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(meta_dev, 0, 16 * count, c->stream);
+    for (uint64_t first = 0; first < count && e == hipSuccess; first += 32768) {   // grid.y
+      const uint32_t cnt = (uint32_t)(count - first < 32768 ? count - first : 32768);
+      hipLaunchKernelGGL(kzd_scan_kernel, dim3(blocks, cnt), dim3(256), 0, c->stream, (const KzdDesc*)desc_dev + first,
+                         meta_dev + 2 * first);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(meta.data(), meta_dev, 16 * count, hipMemcpyDeviceToHost, c->stream);
+    const hipError_t es = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) KZD_FAIL(PLONK_ERR_HIP, hipGetErrorString(e));
+    for (uint64_t i = 0; i < count; ++i) {
+      if (meta[2 * i + 1]) KZD_FAIL(PLONK_ERR_DATA, "non-canonical coefficient");
+      trimmed[i] = meta[2 * i];
+    }
+  } else {
+    for (uint64_t i = 0; i < count; ++i) {
+      const uint64_t* p = (const uint64_t*)polys[i];
+      trimmed[i] = host_trimmed(p, lens[i]);
+      Fr t;
+      for (uint64_t k = 0; k < trimmed[i]; ++k)
+        if (!kzg_fr_load(p + 4 * k, &t)) KZD_FAIL(PLONK_ERR_DATA, "non-canonical coefficient");
+    }
+  }
+  for (uint64_t i = 0; i < count; ++i)
+    if (kzd_check_len(log_n, trimmed[i])) return PLONK_ERR_DEGREE;
   return PLONK_OK;
 }
 
@@ -501,42 +468,11 @@ static int domain_open_impl(const char* api_fn, plonk_kzg_domain* dom, const voi
   // lengths without trailing zeros and the canonical-form check, before anything is queued or written
   std::vector<uint64_t> trimmed(count);
   if (resident) {
-    std::vector<KzdDesc> desc(count);
-    for (uint64_t i = 0; i < count; ++i) desc[i] = KzdDesc{(const Fr*)polys[i], lens[i]};
     PTRY_D(d->need(KzgDomain::DESC, sizeof(KzdDesc) * count));
     PTRY_D(d->need(KzgDomain::META, 16 * count));
-    std::vector<unsigned long long> meta(2 * count);
-    uint64_t longest = 1;
-    for (uint64_t i = 0; i < count; ++i) longest = lens[i] > longest ? lens[i] : longest;
-    const uint32_t blocks = (uint32_t)((longest + 255) / 256 < 1024 ? (longest + 255) / 256 : 1024);
-    // whatever fails, the stream is drained before the call returns: nothing stays queued
-    hipError_t e = hipMemcpyAsync(d->p[KzgDomain::DESC], desc.data(), sizeof(KzdDesc) * count, hipMemcpyHostToDevice, c.stream);
-    if (e == hipSuccess) e = hipMemsetAsync(d->p[KzgDomain::META], 0, 16 * count, c.stream);
-    for (uint64_t first = 0; first < count && e == hipSuccess; first += 32768) {   // grid.y
-      const uint32_t cnt = (uint32_t)(count - first < 32768 ? count - first : 32768);
-      hipLaunchKernelGGL(kzd_scan_kernel, dim3(blocks, cnt), dim3(256), 0, c.stream, d->at<const KzdDesc>(KzgDomain::DESC) + first,
-                         d->at<unsigned long long>(KzgDomain::META) + 2 * first);
-      e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(meta.data(), d->p[KzgDomain::META], 16 * count, hipMemcpyDeviceToHost, c.stream);
-    const hipError_t es = hipStreamSynchronize(c.stream);
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) KZD_FAIL(PLONK_ERR_HIP, hipGetErrorString(e));
-    for (uint64_t i = 0; i < count; ++i) {
-      if (meta[2 * i + 1]) KZD_FAIL(PLONK_ERR_DATA, "non-canonical coefficient");
-      trimmed[i] = meta[2 * i];
-    }
-  } else {
-    for (uint64_t i = 0; i < count; ++i) {
-      const uint64_t* p = (const uint64_t*)polys[i];
-      trimmed[i] = host_trimmed(p, lens[i]);
-      Fr t;
-      for (uint64_t k = 0; k < trimmed[i]; ++k)
-        if (!kzg_fr_load(p + 4 * k, &t)) KZD_FAIL(PLONK_ERR_DATA, "non-canonical coefficient");
-    }
   }
-  for (uint64_t i = 0; i < count; ++i)
-    if (kzd_check_len(d->log_n, trimmed[i])) return PLONK_ERR_DEGREE;
+  PTRY_D(kzd_lengths(api_fn, &c, d->log_n, polys, lens, count, resident, d->at<KzdDesc>(KzgDomain::DESC),
+                     d->at<unsigned long long>(KzgDomain::META), trimmed.data()));
   const int rc = domain_open_body(d, polys, trimmed.data(), count, evaluations, witnesses48, commitments48);
   if (rc != PLONK_OK) (void)hipStreamSynchronize(c.stream);   // an error leaves nothing of the call queued
   return rc;

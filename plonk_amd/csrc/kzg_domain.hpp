@@ -27,4 +27,19 @@ int kzd_finish(Ctx* c, const void* slots, uint64_t stride, uint64_t offset, uint
 // slots[i] = the affine point xy96[i] (Montgomery x || y, 96 zero bytes = the identity), i < count
 int kzd_load_raw(Ctx* c, const G1Affine* xy96, uint64_t count, void* slots);
 
+// What the other openings on a handle (kzg_cells.hip) share with plonk_kzg_open_domain.
+struct KzdDesc {   // a resident polynomial as the scan kernel takes it
+  const Fr* p;
+  uint64_t len;
+};
+// trimmed[i] = the length of polynomial i without trailing zeros; PLONK_ERR_DATA for a coefficient that is not a canonical
+// residue, then PLONK_ERR_DEGREE for more than 2^log_n coefficients.  Host form: polys are host pointers, nothing is queued.
+// Resident form: a scan on the device (desc_dev: count descriptors, meta_dev: 2 x count words, both the caller's); returns
+// with the stream drained.
+int kzd_lengths(const char* api_fn, Ctx* c, uint32_t log_n, const void* const* polys, const uint64_t* lens, uint64_t count, bool resident,
+                KzdDesc* desc_dev, unsigned long long* meta_dev, uint64_t* trimmed);
+// out48[i] (HOST memory) = the commitment of row i of f (n coefficients per row, trimmed length m[i]) through the ordinary
+// commitment path; the caller has reserved the MSM scratch (msm_reserve); returns with the stream synchronised
+int kzd_commit(Ctx* c, const Fr* f, uint64_t n, const uint64_t* m, uint32_t cnt, uint8_t* out48);
+
 }  // namespace plonk

@@ -46,6 +46,8 @@ struct KzdView {
   bool key_current;        // the context still holds the commit key the handle was built on
   const GlvScalar* tw;     // w_(2n)^e, e < n
   void** evals;            // the handle's slot for the state of kzg_evals.hip, released through kze_release
+  void** cells;            // the handle's slot for the state of kzg_cells.hip, released through kzc_release
+  uint64_t ws_cap;         // the cap on the point workspace of a call
 };
 KzdView kzd_view(plonk_kzg_domain* dom);
 void kze_release(void* evals);
