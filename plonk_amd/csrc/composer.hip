@@ -13,39 +13,26 @@
 // inversion per gadget; their intermediates are parked in the gadget's own output slots (no per-lane arrays, no scratch).
 // The only atomic is a vector atomicMin on the error word (lowest record id that met a malformed JubJub scalar).
 #include "composer.hpp"
+#include "devmem.cuh"
 
 namespace plonk {
 
 namespace {
 
-__device__ __forceinline__ Fr ldf(const Fr* p) {
-  const uint4* q = reinterpret_cast<const uint4*>(p);
-  uint4 a = q[0], b = q[1];
-  Fr r;
-  r.l[0] = a.x; r.l[1] = a.y; r.l[2] = a.z; r.l[3] = a.w;
-  r.l[4] = b.x; r.l[5] = b.y; r.l[6] = b.z; r.l[7] = b.w;
-  return r;
-}
-__device__ __forceinline__ void stf(Fr* p, const Fr& v) {
-  uint4* q = reinterpret_cast<uint4*>(p);
-  q[0] = make_uint4(v.l[0], v.l[1], v.l[2], v.l[3]);
-  q[1] = make_uint4(v.l[4], v.l[5], v.l[6], v.l[7]);
-}
-
 struct DevExec {   // executor backend of composer_core.hpp over the witness table in HBM
   static constexpr bool EXEC = true;
   Fr* tab;
   uint32_t next;
-  __device__ __forceinline__ Fr get(uint32_t i) const { return ldf(tab + i); }
-  __device__ __forceinline__ void put(uint32_t i, const Fr& v) { stf(tab + i, v); }
-  __device__ __forceinline__ uint32_t alloc(const Fr& v) { stf(tab + next, v); return next++; }
+  __device__ __forceinline__ Fr get(uint32_t i) const { return ld_fr(tab + i); }
+  __device__ __forceinline__ void put(uint32_t i, const Fr& v) { st_fr(tab + i, v); }
+  __device__ __forceinline__ uint32_t alloc(const Fr& v) { st_fr(tab + next, v); return next++; }
   __device__ __forceinline__ uint32_t mark() const { return next; }
   __device__ __forceinline__ void skip(uint32_t n) { next += n; }
   __device__ __forceinline__ void emit(const ComposerRow&) {}
 };
 struct DevPool {
   const Fr* pool;
-  __device__ __forceinline__ Fr operator()(uint32_t i) const { return ldf(pool + i); }
+  __device__ __forceinline__ Fr operator()(uint32_t i) const { return ld_fr(pool + i); }
 };
 
 __device__ __forceinline__ void run_record(const ComposerOp* ops, uint32_t i, Fr* tab, const Fr* pool, uint32_t* err) {
@@ -70,14 +57,14 @@ __global__ void __launch_bounds__(COMPOSER_NARROW) composer_levels_kernel(const 
 
 __global__ void __launch_bounds__(256) composer_scatter_kernel(const Fr* inputs, const uint32_t* slots, uint64_t n, Fr* tab) {
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) stf(tab + slots[i], ldf(inputs + i));
+  if (i < n) st_fr(tab + slots[i], ld_fr(inputs + i));
 }
 
 __global__ void __launch_bounds__(256) composer_pi_kernel(const ComposerPiRow* rows, uint64_t n, const Fr* tab, const Fr* pool, Fr* out) {
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const DevExec b{const_cast<Fr*>(tab), 0};
-  stf(out + i, composer_pi_value(b, rows[i], DevPool{pool}));
+  st_fr(out + i, composer_pi_value(b, rows[i], DevPool{pool}));
 }
 
 template <class T> int upload(Ctx* c, T** dst, const T* src, size_t count) {

@@ -10,20 +10,11 @@
 //   sigma_decode_kernel  one lane per (wire, row): K_col * omega^row -> packed position, once per prover
 // Only vector stores and ordinary atomics (integer adds of exact counts).
 #include "diagnose.hpp"
-#include "fr29.cuh"
+#include "devmem.cuh"
 
 namespace plonk {
 
 namespace {
-
-__device__ __forceinline__ Fr ldf(const Fr* p) {
-  const uint4* q = reinterpret_cast<const uint4*>(p);
-  uint4 a = q[0], b = q[1];
-  Fr r;
-  r.l[0] = a.x; r.l[1] = a.y; r.l[2] = a.z; r.l[3] = a.w;
-  r.l[4] = b.x; r.l[5] = b.y; r.l[6] = b.z; r.l[7] = b.w;
-  return r;
-}
 
 // A value in twiddle form.  Range discipline (fr29.cuh; the lazy ranges poly.hip's widget path describes): every sum is
 // add_csub'd and every difference sub_reduce'd to [0, 2q + eps), normalised, so both operands of every product are inside
@@ -36,7 +27,7 @@ __device__ __forceinline__ T29 operator+(const T29& a, const T29& b) { return T2
 __device__ __forceinline__ T29 operator-(const T29& a, const T29& b) { return T29{Fr29::sub_reduce(a.v, b.v)}; }
 __device__ __forceinline__ T29 operator*(const T29& a, const T29& b) { return T29{Fr29::mul(a.v, b.v)}; }
 __device__ __forceinline__ bool diag_nonzero(const T29& x) { return !x.v.to_fr().is_zero(); }
-__device__ __forceinline__ T29 t29_load(const Fr* p) { return T29{Fr29::twiddle_from_fr(ldf(p))}; }
+__device__ __forceinline__ T29 t29_load(const Fr* p) { return T29{Fr29::twiddle_from_fr(ld_fr(p))}; }
 __device__ __forceinline__ T29 t29_zero() { return T29{Fr29::zero()}; }
 
 T29 t29_of(const Fr& x) { return T29{Fr29::twiddle_from_fr(x)}; }   // host
@@ -46,7 +37,7 @@ struct RowLoader {
   uint64_t i, iw;
   __device__ __forceinline__ T29 wire(int col) const { return t29_load(a.wires + (uint64_t)col * a.n + i); }
   __device__ __forceinline__ T29 wire_next(int col) const { return t29_load(a.wires + (uint64_t)col * a.n + iw); }
-  __device__ __forceinline__ bool sel_nonzero(int id) const { return a.sel[id] && !ldf(a.sel[id] + i).is_zero(); }
+  __device__ __forceinline__ bool sel_nonzero(int id) const { return a.sel[id] && !ld_fr(a.sel[id] + i).is_zero(); }
   __device__ __forceinline__ T29 sel(int id) const { return a.sel[id] ? t29_load(a.sel[id] + i) : t29_zero(); }
   __device__ __forceinline__ T29 pi() const { return a.pi ? t29_load(a.pi + i) : t29_zero(); }
 };
@@ -66,7 +57,7 @@ __global__ void __launch_bounds__(DIAG_T) diag_row_kernel(DiagArgs a, DiagConsts
       bool bad = to == DIAG_POS_NONE;
       if (!bad) {
         const uint64_t at = (uint64_t)(to >> SIGMA_ROW_BITS) * a.n + (to & ((1u << SIGMA_ROW_BITS) - 1));
-        if (at != (uint64_t)col * a.n + i) bad = !(ldf(a.wires + (uint64_t)col * a.n + i) == ldf(a.wires + at));
+        if (at != (uint64_t)col * a.n + i) bad = !(ld_fr(a.wires + (uint64_t)col * a.n + i) == ld_fr(a.wires + at));
       }
       if (bad) mask |= 1u << (DIAG_COPY_SHIFT + col);
     }

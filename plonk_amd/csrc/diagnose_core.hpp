@@ -155,9 +155,7 @@ inline SigmaDecodeConsts<Fr> sigma_decode_consts_fr(uint32_t logn) {
     k.kn[cc] = kc.pow_u64(1ull << logn);
     k.kinv[cc] = kc.inv();
   }
-  Fr w = fr_root_of_unity();
-  for (uint32_t i = logn; i < 32; ++i) w = w.sqr();
-  Fr wi = w.inv();
+  Fr wi = fr_domain_root(logn).inv();
   for (int j = 0; j < DIAG_MAX_LOG; ++j) { k.winv[j] = wi; wi = wi.sqr(); }
   return k;
 }

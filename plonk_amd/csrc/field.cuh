@@ -242,5 +242,10 @@ HD Fr fr_root_of_unity() {   // 7^((q-1)/2^32), order 2^32 (TWO_ADACITY = 32)
   for (int i = 0; i < 8; ++i) r.l[i] = v[i];
   return r;
 }
+HD Fr fr_domain_root(uint32_t log_size) {   // the generator of the size-2^log_size domain, log_size <= 32
+  Fr w = fr_root_of_unity();
+  for (uint32_t i = log_size; i < 32; ++i) w = w.sqr();
+  return w;
+}
 
 }  // namespace plonk

@@ -9,11 +9,14 @@
 
 namespace plonk {
 
+static void identity48(uint8_t out[48]) {   // the compressed point at infinity
+  memset(out, 0, 48);
+  out[0] = 0xC0;
+}
 // G1Affine::to_bytes: 48-byte BE x, flags 0x80 | 0x40 inf | 0x20 y > -y  (commitment.rs:46-57)
 static void g1_compress97(const uint8_t in[97], uint8_t out[48]) {
   if (in[96]) {
-    memset(out, 0, 48);
-    out[0] = 0xC0;
+    identity48(out);
     return;
   }
   Fp x, y;

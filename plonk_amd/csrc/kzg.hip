@@ -31,9 +31,6 @@
 #include "verify_core.hpp"
 #include "kzg_core.hpp"
 
-#define PTRY_K(expr) do { int _rc = (expr); if (_rc) return _rc; } while (0)
-#define KZG_FAIL(code, msg) return (plonk::set_last_error(api_fn, msg, __FILE__, __LINE__), code)
-
 namespace plonk { struct KzgKey; }
 struct plonk_kzg_key {
   plonk::KzgKey* k;
@@ -44,27 +41,17 @@ namespace plonk {
 
 static constexpr uint64_t KZG_STAGE_MIN = 1ull << 16;   // coefficients a staging buffer holds at least
 
-struct KzgWork {
+struct KzgBufs {
   enum { DESC, VPOW, EVALS, PARTIAL, FOLD, SCRATCH, TOTALS, STAGE0, STAGE1, PTS, KIND, COMP, SC, IDS, PART, POWERS,
          E_POINTS, E_PROOFS, E_PAIRS, E_PRE, E_VERDICT, E_VALUES, NBUF };   // E_*: the per-item checks (pairing.hip)
-  void* p[NBUF] = {};
-  uint64_t cap[NBUF] = {};
+};
+struct KzgWork : KzgBufs, DevBufs<KzgBufs::NBUF> {
   hipEvent_t up[2] = {nullptr, nullptr}, done[2] = {nullptr, nullptr};
-  ~KzgWork() {
-    for (int i = 0; i < NBUF; ++i) (void)hipFree(p[i]);
+  ~KzgWork() {   // the events go before the buffers, which the base frees
     for (int b = 0; b < 2; ++b) {
       if (up[b]) (void)hipEventDestroy(up[b]);
       if (done[b]) (void)hipEventDestroy(done[b]);
     }
-  }
-  int need(int i, uint64_t bytes) {
-    if (bytes <= cap[i]) return PLONK_OK;
-    (void)hipFree(p[i]);
-    p[i] = nullptr;
-    cap[i] = 0;
-    HIP_TRY(hipMalloc(&p[i], bytes));
-    cap[i] = bytes;
-    return PLONK_OK;
   }
   int events() {
     for (int b = 0; b < 2; ++b) {
@@ -73,8 +60,6 @@ struct KzgWork {
     }
     return PLONK_OK;
   }
-  template <class T>
-  T* at(int i) const { return (T*)p[i]; }
 };
 
 static KzgWork& kzg_work(Ctx* c) {
@@ -90,9 +75,9 @@ void kzg_ws_release(Ctx* c) {
 // stages vectors of values through the buffers plonk_kzg_open stages coefficients through
 int kzg_stage_reserve(Ctx* c, uint64_t values, Fr* stage[2], hipEvent_t up[2], hipEvent_t done[2]) {
   KzgWork& w = kzg_work(c);
-  PTRY_K(w.need(KzgWork::STAGE0, sizeof(Fr) * values));
-  PTRY_K(w.need(KzgWork::STAGE1, sizeof(Fr) * values));
-  PTRY_K(w.events());
+  PTRY(w.need(KzgWork::STAGE0, sizeof(Fr) * values));
+  PTRY(w.need(KzgWork::STAGE1, sizeof(Fr) * values));
+  PTRY(w.events());
   if (!c->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
   for (int b = 0; b < 2; ++b) {
     stage[b] = w.at<Fr>(b ? KzgWork::STAGE1 : KzgWork::STAGE0);
@@ -102,17 +87,12 @@ int kzg_stage_reserve(Ctx* c, uint64_t values, Fr* stage[2], hipEvent_t up[2], h
   return PLONK_OK;
 }
 
-static void identity48(uint8_t out[48]) {
-  memset(out, 0, 48);
-  out[0] = 0xC0;
-}
-
 // commitments of up to MSM_MAX_BATCH resident scalar sets (every m > 0) as one grouped launch, finished on the host like
 // plonk_msm_batch's: 48-byte compressed each
 static int commit_group(Ctx* c, const Fr* const* sc, const uint64_t* m, int cnt, uint8_t* out48) {
   G1 sums[MSM_MAX_BATCH];
   uint8_t aff[MSM_MAX_BATCH][97];
-  PTRY_K(msm_group_sums(c, sc, m, cnt, sums));
+  PTRY(msm_group_sums(c, sc, m, cnt, sums));
   batch_xyzz_to_affine97(sums, cnt, aff);
   for (int k = 0; k < cnt; ++k) g1_compress97(aff[k], out48 + 48 * k);
   return PLONK_OK;
@@ -131,17 +111,12 @@ static int commit_polys(Ctx* c, const KzgDesc* desc, uint32_t cnt, uint8_t* out4
       sc[g] = desc[i].p; m[g] = desc[i].len; which[g] = i; ++g;
     }
     if (g == MSM_MAX_BATCH || (i == cnt && g)) {
-      PTRY_K(commit_group(c, sc, m, g, tmp));
+      PTRY(commit_group(c, sc, m, g, tmp));
       for (int k = 0; k < g; ++k) memcpy(out48 + 48ull * which[k], tmp + 48 * k, 48);
       g = 0;
     }
   }
   return PLONK_OK;
-}
-
-static uint64_t host_trimmed(const uint64_t* p, uint64_t len) {
-  while (len && !(p[4 * len - 4] | p[4 * len - 3] | p[4 * len - 2] | p[4 * len - 1])) --len;
-  return len;
 }
 
 // One fold launch over desc_dev[first, first + cnt): the first launch of a call covers the whole fold and overwrites it
@@ -167,16 +142,16 @@ static int kzg_open_impl(const char* api_fn, plonk_ctx* ctx, const void* const* 
                          const uint64_t* point, const uint64_t* v_challenge, uint64_t* evaluations, uint8_t* commitments,
                          uint8_t* witness48, bool resident) {
   if (!ctx || !point || !witness48 || (count && (!polys || !lens || !evaluations)) || (count > 1 && !v_challenge))
-    KZG_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
-  if (count > KZG_MAX_OPEN) KZG_FAIL(PLONK_ERR_ARG, "invalid argument: at most 65536 polynomials per call");
+    API_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
+  if (count > KZG_MAX_OPEN) API_FAIL(PLONK_ERR_ARG, "invalid argument: at most 65536 polynomials per call");
   Fr z, v = Fr::one();
-  if (!kzg_fr_load(point, &z) || (v_challenge && !kzg_fr_load(v_challenge, &v))) KZG_FAIL(PLONK_ERR_DATA, "non-canonical scalar");
+  if (!kzg_fr_load(point, &z) || (v_challenge && !kzg_fr_load(v_challenge, &v))) API_FAIL(PLONK_ERR_DATA, "non-canonical scalar");
   for (uint64_t i = 0; i < count; ++i)
-    if (lens[i] && !polys[i]) KZG_FAIL(PLONK_ERR_ARG, "invalid argument: polys[i] is NULL with lens[i] > 0");
+    if (lens[i] && !polys[i]) API_FAIL(PLONK_ERR_ARG, "invalid argument: polys[i] is NULL with lens[i] > 0");
   Ctx& c = ctx->c;
   CTX_ENTER(c, api_fn);
   HIP_TRY(hipSetDevice(c.device));
-  if (c.nccl_comm) KZG_FAIL(PLONK_ERR_STATE, "a context with a communicator holds only a range of the commit key");
+  if (c.nccl_comm) API_FAIL(PLONK_ERR_STATE, "a context with a communicator holds only a range of the commit key");
   if (count && !c.srs_table) return PLONK_ERR_NO_SRS;
   const int rc = kzg_open_body(api_fn, c, polys, lens, count, z, v, evaluations, commitments, witness48, resident);
   if (rc != PLONK_OK) {   // an error leaves nothing of the call queued (the evaluations' copy, a staged upload) and no profile slot open
@@ -196,10 +171,10 @@ static int kzg_open_body(const char* api_fn, Ctx& c, const void* const* polys, c
   if (resident) {
     for (uint32_t i = 0; i < n; ++i) desc[i] = KzgDesc{(const Fr*)polys[i], lens[i]};
     if (n) {
-      PTRY_K(w.need(KzgWork::DESC, sizeof(KzgDesc) * n));
+      PTRY(w.need(KzgWork::DESC, sizeof(KzgDesc) * n));
       prof_begin(&c, 12);
       HIP_TRY(hipMemcpyAsync(w.p[KzgWork::DESC], desc.data(), sizeof(KzgDesc) * n, hipMemcpyHostToDevice, c.stream));
-      PTRY_K(poly_kzg_trim(&c, w.at<KzgDesc>(KzgWork::DESC), n));
+      PTRY(poly_kzg_trim(&c, w.at<KzgDesc>(KzgWork::DESC), n));
       HIP_TRY(hipMemcpyAsync(desc.data(), w.p[KzgWork::DESC], sizeof(KzgDesc) * n, hipMemcpyDeviceToHost, c.stream));
       prof_end(&c, 12);
       HIP_TRY(hipStreamSynchronize(c.stream));
@@ -216,16 +191,16 @@ static int kzg_open_body(const char* api_fn, Ctx& c, const void* const* polys, c
     if (commitments) for (uint32_t i = 0; i < n; ++i) identity48(commitments + 48ull * i);
     return PLONK_OK;
   }
-  PTRY_K(msm_reserve(&c, L));
-  PTRY_K(w.need(KzgWork::DESC, sizeof(KzgDesc) * n));
-  PTRY_K(w.need(KzgWork::VPOW, sizeof(Fr29Slot) * n));
-  PTRY_K(w.need(KzgWork::EVALS, sizeof(Fr) * n));
-  PTRY_K(w.need(KzgWork::PARTIAL, sizeof(Fr) * KZG_GROUP * kzg_fold_waves(L)));
-  PTRY_K(w.need(KzgWork::FOLD, sizeof(Fr) * (L + 1)));
-  PTRY_K(w.need(KzgWork::SCRATCH, sizeof(Fr) * (L + 1)));
-  PTRY_K(w.need(KzgWork::TOTALS, sizeof(Fr) * (L / 2048 + 2)));
+  PTRY(msm_reserve(&c, L));
+  PTRY(w.need(KzgWork::DESC, sizeof(KzgDesc) * n));
+  PTRY(w.need(KzgWork::VPOW, sizeof(Fr29Slot) * n));
+  PTRY(w.need(KzgWork::EVALS, sizeof(Fr) * n));
+  PTRY(w.need(KzgWork::PARTIAL, sizeof(Fr) * KZG_GROUP * kzg_fold_waves(L)));
+  PTRY(w.need(KzgWork::FOLD, sizeof(Fr) * (L + 1)));
+  PTRY(w.need(KzgWork::SCRATCH, sizeof(Fr) * (L + 1)));
+  PTRY(w.need(KzgWork::TOTALS, sizeof(Fr) * (L / 2048 + 2)));
   prof_begin(&c, 12);
-  PTRY_K(poly_kzg_powers(&c, w.p[KzgWork::VPOW], n, v));
+  PTRY(poly_kzg_powers(&c, w.p[KzgWork::VPOW], n, v));
   HIP_TRY(hipMemsetAsync(w.p[KzgWork::EVALS], 0, sizeof(Fr) * n, c.stream));
   bool started = false;
   if (resident) {
@@ -233,17 +208,17 @@ static int kzg_open_body(const char* api_fn, Ctx& c, const void* const* polys, c
       const uint32_t cnt = n - first < KZG_GROUP ? n - first : KZG_GROUP;
       uint64_t glen = 0;
       for (uint32_t i = 0; i < cnt; ++i) glen = desc[first + i].len > glen ? desc[first + i].len : glen;
-      if (glen) PTRY_K(fold_group(&c, w, first, cnt, glen, L, &started, z));
+      if (glen) PTRY(fold_group(&c, w, first, cnt, glen, L, &started, z));
     }
     prof_end(&c, 12);
-    if (commitments) PTRY_K(commit_polys(&c, desc.data(), n, commitments));
+    if (commitments) PTRY(commit_polys(&c, desc.data(), n, commitments));
   } else {
     // groups of polynomials packed into one of two staging buffers: the upload of group g + 1 (copy stream) runs under the
     // fold kernel of group g (main stream); a buffer is reused once the work that read it has finished
     const uint64_t S = L > KZG_STAGE_MIN ? L : KZG_STAGE_MIN;
-    PTRY_K(w.need(KzgWork::STAGE0, sizeof(Fr) * S));
-    PTRY_K(w.need(KzgWork::STAGE1, sizeof(Fr) * S));
-    PTRY_K(w.events());
+    PTRY(w.need(KzgWork::STAGE0, sizeof(Fr) * S));
+    PTRY(w.need(KzgWork::STAGE1, sizeof(Fr) * S));
+    PTRY(w.events());
     if (!c.copy_stream) HIP_TRY(hipStreamCreateWithFlags(&c.copy_stream, hipStreamNonBlocking));
     prof_end(&c, 12);
     HIP_TRY(hipStreamSynchronize(c.stream));   // the copy stream is not ordered behind what the main stream still runs
@@ -288,10 +263,10 @@ static int kzg_open_body(const char* api_fn, Ctx& c, const void* const* polys, c
   if (L > 1) {
     prof_begin(&c, 13);
     if (z.is_zero()) {
-      PTRY_K(poly_shift_down(&c, w.at<Fr>(KzgWork::FOLD), w.at<Fr>(KzgWork::SCRATCH), L));
+      PTRY(poly_shift_down(&c, w.at<Fr>(KzgWork::FOLD), w.at<Fr>(KzgWork::SCRATCH), L));
       wit = w.at<Fr>(KzgWork::SCRATCH);
     } else {
-      PTRY_K(poly_ruffini(&c, w.at<Fr>(KzgWork::FOLD), w.at<Fr>(KzgWork::FOLD), L, z, z.inv(), w.at<Fr>(KzgWork::SCRATCH),
+      PTRY(poly_ruffini(&c, w.at<Fr>(KzgWork::FOLD), w.at<Fr>(KzgWork::FOLD), L, z, z.inv(), w.at<Fr>(KzgWork::SCRATCH),
                           w.at<Fr>(KzgWork::TOTALS)));
       wit = w.at<Fr>(KzgWork::FOLD);
     }
@@ -300,7 +275,7 @@ static int kzg_open_body(const char* api_fn, Ctx& c, const void* const* polys, c
     prof_begin(&c, 14);
     const int rc = commit_group(&c, &wit, &m, 1, witness48);
     prof_end(&c, 14);
-    PTRY_K(rc);
+    PTRY(rc);
   }
   HIP_TRY(hipStreamSynchronize(c.stream));
   return PLONK_OK;
@@ -318,12 +293,12 @@ struct KzgKey {
 };
 
 static int check_reserve(KzgWork& w, uint64_t npts, uint64_t nterms) {
-  PTRY_K(w.need(KzgWork::PTS, sizeof(G1Affine) * npts));
-  PTRY_K(w.need(KzgWork::KIND, 4 * npts));
-  PTRY_K(w.need(KzgWork::COMP, 48 * npts));
-  PTRY_K(w.need(KzgWork::SC, 32 * nterms));
-  PTRY_K(w.need(KzgWork::IDS, 4 * nterms));
-  PTRY_K(w.need(KzgWork::PART, sizeof(G1) * 2 * VERIFY_MSM_MAX_BLOCKS));
+  PTRY(w.need(KzgWork::PTS, sizeof(G1Affine) * npts));
+  PTRY(w.need(KzgWork::KIND, 4 * npts));
+  PTRY(w.need(KzgWork::COMP, 48 * npts));
+  PTRY(w.need(KzgWork::SC, 32 * nterms));
+  PTRY(w.need(KzgWork::IDS, 4 * nterms));
+  PTRY(w.need(KzgWork::PART, sizeof(G1) * 2 * VERIFY_MSM_MAX_BLOCKS));
   return PLONK_OK;
 }
 
@@ -360,13 +335,13 @@ static int pairing_each_body(plonk_kzg_key* key, const uint8_t* a48, const uint8
   KzgKey* kk = key->k;
   Ctx& c = *kk->c;
   KzgWork& w = kzg_work(&c);
-  PTRY_K(pairing_tables_create(&c, kk->x_h, kk->h, &kk->pair_tables));
+  PTRY(pairing_tables_create(&c, kk->x_h, kk->h, &kk->pair_tables));
   const uint64_t npts = 2 * count;
-  PTRY_K(check_reserve(w, npts, 1));
-  PTRY_K(w.need(KzgWork::E_PAIRS, sizeof(G1) * npts));
-  PTRY_K(w.need(KzgWork::E_PRE, 4 * count));
-  PTRY_K(w.need(KzgWork::E_VERDICT, 4 * count));
-  if (values) PTRY_K(w.need(KzgWork::E_VALUES, 8 * 72 * count));
+  PTRY(check_reserve(w, npts, 1));
+  PTRY(w.need(KzgWork::E_PAIRS, sizeof(G1) * npts));
+  PTRY(w.need(KzgWork::E_PRE, 4 * count));
+  PTRY(w.need(KzgWork::E_VERDICT, 4 * count));
+  if (values) PTRY(w.need(KzgWork::E_VALUES, 8 * 72 * count));
   const auto t0 = std::chrono::steady_clock::now();
   std::vector<uint8_t> comp(48 * npts);
   for (uint64_t k = 0; k < count; ++k) {
@@ -374,16 +349,16 @@ static int pairing_each_body(plonk_kzg_key* key, const uint8_t* a48, const uint8
     memcpy(comp.data() + 96 * k + 48, b48 + 48 * k, 48);
   }
   std::vector<int32_t> st;
-  PTRY_K(decode_points(&c, comp.data(), (uint32_t)npts, w.at<uint8_t>(KzgWork::COMP), w.at<G1Affine>(KzgWork::PTS),
+  PTRY(decode_points(&c, comp.data(), (uint32_t)npts, w.at<uint8_t>(KzgWork::COMP), w.at<G1Affine>(KzgWork::PTS),
                        w.at<int32_t>(KzgWork::KIND), &st));
   const auto t1 = std::chrono::steady_clock::now();
-  PTRY_K(each_pairs_launch(&c, w.at<const G1Affine>(KzgWork::PTS), w.at<const int32_t>(KzgWork::KIND), count,
+  PTRY(each_pairs_launch(&c, w.at<const G1Affine>(KzgWork::PTS), w.at<const int32_t>(KzgWork::KIND), count,
                            w.at<G1>(KzgWork::E_PAIRS), w.at<int32_t>(KzgWork::E_PRE)));
-  PTRY_K(pairing_each_launch(&c, kk->pair_tables, w.at<const G1>(KzgWork::E_PAIRS), w.at<const int32_t>(KzgWork::E_PRE), count,
+  PTRY(pairing_each_launch(&c, kk->pair_tables, w.at<const G1>(KzgWork::E_PAIRS), w.at<const int32_t>(KzgWork::E_PRE), count,
                              w.at<int32_t>(KzgWork::E_VERDICT), values ? w.at<uint64_t>(KzgWork::E_VALUES) : nullptr));
   if (values) HIP_TRY(hipMemcpyAsync(values, w.p[KzgWork::E_VALUES], 8 * 72 * count, hipMemcpyDeviceToHost, c.stream));
   uint32_t checked = 0, rejected = 0;
-  PTRY_K(each_finish(&c, w.at<const int32_t>(KzgWork::E_VERDICT), w.at<const int32_t>(KzgWork::E_PRE), count, verdicts, &checked,
+  PTRY(each_finish(&c, w.at<const int32_t>(KzgWork::E_VERDICT), w.at<const int32_t>(KzgWork::E_PRE), count, verdicts, &checked,
                      &rejected));
   const auto t2 = std::chrono::steady_clock::now();
   each_info(info, count, 0, checked, rejected, ms_between(t0, t1), 0, 0, ms_between(t1, t2));
@@ -395,14 +370,14 @@ static int kzg_check_each_body(plonk_kzg_key* key, const uint64_t* points, const
   KzgKey* kk = key->k;
   Ctx& c = *kk->c;
   KzgWork& w = kzg_work(&c);
-  PTRY_K(pairing_tables_create(&c, kk->x_h, kk->h, &kk->pair_tables));
+  PTRY(pairing_tables_create(&c, kk->x_h, kk->h, &kk->pair_tables));
   const uint64_t npts = 1 + 2 * count, nterms = KZG_EACH_TERMS * count;
-  PTRY_K(check_reserve(w, npts, nterms));
-  PTRY_K(w.need(KzgWork::E_POINTS, 32 * count));
-  PTRY_K(w.need(KzgWork::E_PROOFS, sizeof(plonk_kzg_proof) * count));
-  PTRY_K(w.need(KzgWork::E_PAIRS, sizeof(G1) * 2 * count));
-  PTRY_K(w.need(KzgWork::E_PRE, 4 * count));
-  PTRY_K(w.need(KzgWork::E_VERDICT, 4 * count));
+  PTRY(check_reserve(w, npts, nterms));
+  PTRY(w.need(KzgWork::E_POINTS, 32 * count));
+  PTRY(w.need(KzgWork::E_PROOFS, sizeof(plonk_kzg_proof) * count));
+  PTRY(w.need(KzgWork::E_PAIRS, sizeof(G1) * 2 * count));
+  PTRY(w.need(KzgWork::E_PRE, 4 * count));
+  PTRY(w.need(KzgWork::E_VERDICT, 4 * count));
   const auto t0 = std::chrono::steady_clock::now();
   // the point table [g | C_0 W_0 | C_1 W_1 ...], as plonk_kzg_batch_check's
   std::vector<uint8_t> comp(48 * npts);
@@ -412,25 +387,25 @@ static int kzg_check_each_body(plonk_kzg_key* key, const uint64_t* points, const
     memcpy(comp.data() + 48 * (2 + 2 * k), proofs[k].witness, 48);
   }
   std::vector<int32_t> st;
-  PTRY_K(decode_points(&c, comp.data(), (uint32_t)npts, w.at<uint8_t>(KzgWork::COMP), w.at<G1Affine>(KzgWork::PTS),
+  PTRY(decode_points(&c, comp.data(), (uint32_t)npts, w.at<uint8_t>(KzgWork::COMP), w.at<G1Affine>(KzgWork::PTS),
                        w.at<int32_t>(KzgWork::KIND), &st));
   const auto t1 = std::chrono::steady_clock::now();
   HIP_TRY(hipMemcpyAsync(w.p[KzgWork::E_POINTS], points, 32 * count, hipMemcpyHostToDevice, c.stream));
   HIP_TRY(hipMemcpyAsync(w.p[KzgWork::E_PROOFS], proofs, sizeof(plonk_kzg_proof) * count, hipMemcpyHostToDevice, c.stream));
-  PTRY_K(kzg_each_pack_launch(&c, w.at<const uint64_t>(KzgWork::E_POINTS), w.at<const plonk_kzg_proof>(KzgWork::E_PROOFS),
+  PTRY(kzg_each_pack_launch(&c, w.at<const uint64_t>(KzgWork::E_POINTS), w.at<const plonk_kzg_proof>(KzgWork::E_PROOFS),
                               w.at<const int32_t>(KzgWork::KIND), count, w.at<uint32_t>(KzgWork::SC), w.at<uint32_t>(KzgWork::IDS),
                               w.at<int32_t>(KzgWork::E_PRE)));
   HIP_TRY(hipStreamSynchronize(c.stream));
   const auto t2 = std::chrono::steady_clock::now();
-  PTRY_K(each_sums_launch(&c, w.at<const uint32_t>(KzgWork::SC), w.at<const uint32_t>(KzgWork::IDS), 1, 3, count,
+  PTRY(each_sums_launch(&c, w.at<const uint32_t>(KzgWork::SC), w.at<const uint32_t>(KzgWork::IDS), 1, 3, count,
                           w.at<const G1Affine>(KzgWork::PTS), w.at<const int32_t>(KzgWork::KIND), w.at<const int32_t>(KzgWork::E_PRE),
                           w.at<G1>(KzgWork::E_PAIRS)));
   HIP_TRY(hipStreamSynchronize(c.stream));
   const auto t3 = std::chrono::steady_clock::now();
-  PTRY_K(pairing_each_launch(&c, kk->pair_tables, w.at<const G1>(KzgWork::E_PAIRS), w.at<const int32_t>(KzgWork::E_PRE), count,
+  PTRY(pairing_each_launch(&c, kk->pair_tables, w.at<const G1>(KzgWork::E_PAIRS), w.at<const int32_t>(KzgWork::E_PRE), count,
                              w.at<int32_t>(KzgWork::E_VERDICT), nullptr));
   uint32_t checked = 0, rejected = 0;
-  PTRY_K(each_finish(&c, w.at<const int32_t>(KzgWork::E_VERDICT), w.at<const int32_t>(KzgWork::E_PRE), count, verdicts, &checked,
+  PTRY(each_finish(&c, w.at<const int32_t>(KzgWork::E_VERDICT), w.at<const int32_t>(KzgWork::E_PRE), count, verdicts, &checked,
                      &rejected));
   const auto t4 = std::chrono::steady_clock::now();
   each_info(info, count, KZG_EACH_TERMS, checked, rejected, ms_between(t0, t1), ms_between(t1, t2), ms_between(t2, t3),
@@ -448,8 +423,8 @@ int plonk_kzg_pairing_check_each(plonk_kzg_key* key, const uint8_t* a48, const u
                                  plonk_verify_info* info) {
   const char* const api_fn = __func__;
   return plonk::api_guard(api_fn, [&]() -> int {
-  if (!key || !a48 || !b48 || !verdicts) KZG_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
-  if (count == 0 || count > KZG_MAX_BATCH) KZG_FAIL(PLONK_ERR_ARG, "invalid argument: count must be in [1, 2^24]");
+  if (!key || !a48 || !b48 || !verdicts) API_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
+  if (count == 0 || count > KZG_MAX_BATCH) API_FAIL(PLONK_ERR_ARG, "invalid argument: count must be in [1, 2^24]");
   if (info) memset(info, 0, sizeof *info);
   Ctx& c = *key->k->c;
   CTX_ENTER(c, api_fn);
@@ -465,8 +440,8 @@ int plonk_kzg_check_each(plonk_kzg_key* key, const uint64_t* points, const plonk
                          int32_t* verdicts, plonk_verify_info* info) {
   const char* const api_fn = __func__;
   return plonk::api_guard(api_fn, [&]() -> int {
-  if (!key || !points || !proofs || !verdicts) KZG_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
-  if (count == 0 || count > KZG_MAX_BATCH) KZG_FAIL(PLONK_ERR_ARG, "invalid argument: count must be in [1, 2^24]");
+  if (!key || !points || !proofs || !verdicts) API_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
+  if (count == 0 || count > KZG_MAX_BATCH) API_FAIL(PLONK_ERR_ARG, "invalid argument: count must be in [1, 2^24]");
   if (info) memset(info, 0, sizeof *info);
   Ctx& c = *key->k->c;
   CTX_ENTER(c, api_fn);
@@ -485,8 +460,8 @@ int plonk_kzg_check_each(plonk_kzg_key* key, const uint64_t* points, const plonk
 int plonk_test_pairing_each(plonk_kzg_key* key, const uint8_t* a48, const uint8_t* b48, uint64_t count, uint64_t* out) {
   const char* const api_fn = __func__;
   return plonk::api_guard(api_fn, [&]() -> int {
-  if (!key || !a48 || !b48 || !out) KZG_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
-  if (count == 0 || count > (1ull << 16)) KZG_FAIL(PLONK_ERR_ARG, "invalid argument: count must be in [1, 2^16]");
+  if (!key || !a48 || !b48 || !out) API_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
+  if (count == 0 || count > (1ull << 16)) API_FAIL(PLONK_ERR_ARG, "invalid argument: count must be in [1, 2^16]");
   Ctx& c = *key->k->c;
   CTX_ENTER(c, api_fn);
   HIP_TRY(hipSetDevice(c.device));
@@ -518,13 +493,13 @@ int plonk_kzg_flatten(plonk_ctx* ctx, const uint8_t* commitments, const uint64_t
                       const uint8_t witness48[48], plonk_kzg_proof* out) {
   const char* const api_fn = __func__;
   return plonk::api_guard(api_fn, [&]() -> int {
-  if (!ctx || !commitments || !evaluations || !v || !witness48 || !out) KZG_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
-  if (count == 0 || count > KZG_MAX_OPEN) KZG_FAIL(PLONK_ERR_ARG, "invalid argument: count must be in [1, 65536]");
+  if (!ctx || !commitments || !evaluations || !v || !witness48 || !out) API_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
+  if (count == 0 || count > KZG_MAX_OPEN) API_FAIL(PLONK_ERR_ARG, "invalid argument: count must be in [1, 65536]");
   Fr vv;
   std::vector<Fr> ev(count);
   bool canon = kzg_fr_load(v, &vv);
   for (uint64_t i = 0; i < count; ++i) canon &= kzg_fr_load(evaluations + 4 * i, &ev[i]);
-  if (!canon) KZG_FAIL(PLONK_ERR_DATA, "non-canonical scalar");
+  if (!canon) API_FAIL(PLONK_ERR_DATA, "non-canonical scalar");
   std::vector<uint32_t> sc(8 * count), ids(count);
   const Fr e = kzg_flatten_scalars(vv, ev.data(), count, sc.data());
   for (uint64_t i = 0; i < count; ++i) ids[i] = (uint32_t)i;
@@ -532,16 +507,16 @@ int plonk_kzg_flatten(plonk_ctx* ctx, const uint8_t* commitments, const uint64_t
   CTX_ENTER(c, api_fn);
   HIP_TRY(hipSetDevice(c.device));
   KzgWork& w = kzg_work(&c);
-  PTRY_K(check_reserve(w, count, count));
+  PTRY(check_reserve(w, count, count));
   std::vector<int32_t> st;
-  PTRY_K(decode_points(&c, commitments, (uint32_t)count, w.at<uint8_t>(KzgWork::COMP), w.at<G1Affine>(KzgWork::PTS),
+  PTRY(decode_points(&c, commitments, (uint32_t)count, w.at<uint8_t>(KzgWork::COMP), w.at<G1Affine>(KzgWork::PTS),
                        w.at<int32_t>(KzgWork::KIND), &st));
   for (uint64_t i = 0; i < count; ++i)
-    if (st[i] == VDEC_BAD) KZG_FAIL(PLONK_ERR_POINT, "a commitment is not a valid compressed point of G1");
+    if (st[i] == VDEC_BAD) API_FAIL(PLONK_ERR_POINT, "a commitment is not a valid compressed point of G1");
   HIP_TRY(hipMemcpyAsync(w.p[KzgWork::SC], sc.data(), 32 * count, hipMemcpyHostToDevice, c.stream));
   HIP_TRY(hipMemcpyAsync(w.p[KzgWork::IDS], ids.data(), 4 * count, hipMemcpyHostToDevice, c.stream));
   H1 sums[2];
-  PTRY_K(msm_run(&c, w.at<const uint32_t>(KzgWork::SC), w.at<const uint32_t>(KzgWork::IDS), count, 0, w.at<const G1Affine>(KzgWork::PTS),
+  PTRY(msm_run(&c, w.at<const uint32_t>(KzgWork::SC), w.at<const uint32_t>(KzgWork::IDS), count, 0, w.at<const G1Affine>(KzgWork::PTS),
                  w.at<const int32_t>(KzgWork::KIND), w.at<G1>(KzgWork::PART), sums));
   compress_h1(sums[0], out->commitment);
   memcpy(out->evaluation, e.l, 32);
@@ -553,9 +528,9 @@ int plonk_kzg_flatten(plonk_ctx* ctx, const uint8_t* commitments, const uint64_t
 int plonk_kzg_key_create(plonk_ctx* ctx, const uint8_t opening_key240[240], plonk_kzg_key** out) {
   const char* const api_fn = __func__;
   return plonk::api_guard(api_fn, [&]() -> int {
-  if (!ctx || !opening_key240 || !out) KZG_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
+  if (!ctx || !opening_key240 || !out) API_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
   *out = nullptr;
-  if (const char* why = opening_key_invalid(opening_key240)) KZG_FAIL(PLONK_ERR_DATA, why);
+  if (const char* why = opening_key_invalid(opening_key240)) API_FAIL(PLONK_ERR_DATA, why);
   std::unique_ptr<KzgKey> k(new KzgKey());
   memcpy(k->opening_key, opening_key240, OPENING_KEY_LEN);
   k->h = g2_prepare(g2_decode_valid(opening_key240 + 48));
@@ -567,10 +542,10 @@ int plonk_kzg_key_create(plonk_ctx* ctx, const uint8_t opening_key240[240], plon
   HIP_TRY(hipSetDevice(c.device));
   k->c = &c;
   KzgWork& w = kzg_work(&c);
-  PTRY_K(check_reserve(w, 1, 1));
+  PTRY(check_reserve(w, 1, 1));
   std::vector<int32_t> st;
-  PTRY_K(decode_points(&c, opening_key240, 1, w.at<uint8_t>(KzgWork::COMP), w.at<G1Affine>(KzgWork::PTS), w.at<int32_t>(KzgWork::KIND), &st));
-  if (st[0] != VDEC_OK) KZG_FAIL(PLONK_ERR_STATE, "device decoding of the opening key's g disagrees with the host");
+  PTRY(decode_points(&c, opening_key240, 1, w.at<uint8_t>(KzgWork::COMP), w.at<G1Affine>(KzgWork::PTS), w.at<int32_t>(KzgWork::KIND), &st));
+  if (st[0] != VDEC_OK) API_FAIL(PLONK_ERR_STATE, "device decoding of the opening key's g disagrees with the host");
   HIP_TRY(hipMemcpy(&k->g_aff, w.p[KzgWork::PTS], sizeof(G1Affine), hipMemcpyDeviceToHost));
   *out = new plonk_kzg_key{k.release(), ctx};
   return PLONK_OK;
@@ -591,23 +566,23 @@ int plonk_kzg_batch_check(plonk_kzg_key* key, const uint64_t* points, const plon
                           const uint8_t* label, uint64_t label_len, const uint64_t* u_override, plonk_verify_info* info) {
   const char* const api_fn = __func__;
   return plonk::api_guard(api_fn, [&]() -> int {
-  if (!key || (count && (!points || !proofs)) || (label_len && !label)) KZG_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
-  if (count > KZG_MAX_BATCH) KZG_FAIL(PLONK_ERR_ARG, "invalid argument: at most 2^24 openings per call");
+  if (!key || (count && (!points || !proofs)) || (label_len && !label)) API_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
+  if (count > KZG_MAX_BATCH) API_FAIL(PLONK_ERR_ARG, "invalid argument: at most 2^24 openings per call");
   if (info) memset(info, 0, sizeof *info);
-  if (count == 0) KZG_FAIL(PLONK_ERR_VERIFY, "empty batch (Error::ProofVerificationError, key.rs:667)");
+  if (count == 0) API_FAIL(PLONK_ERR_VERIFY, "empty batch (Error::ProofVerificationError, key.rs:667)");
   const auto t0 = std::chrono::steady_clock::now();
   std::vector<Fr> z(count);
   Fr u = Fr::one(), tmp;
   bool canon = !u_override || kzg_fr_load(u_override, &u);
   for (uint64_t k = 0; k < count; ++k) canon &= kzg_fr_load(points + 4 * k, &z[k]) && kzg_fr_load(proofs[k].evaluation, &tmp);
-  if (!canon) KZG_FAIL(PLONK_ERR_DATA, "non-canonical scalar");
+  if (!canon) API_FAIL(PLONK_ERR_DATA, "non-canonical scalar");
   KzgKey* kk = key->k;
   Ctx& c = *kk->c;
   CTX_ENTER(c, api_fn);
   HIP_TRY(hipSetDevice(c.device));
   KzgWork& w = kzg_work(&c);
   const uint64_t npts = 1 + 2 * count, nterms = 3 * count + 1;
-  PTRY_K(check_reserve(w, npts, nterms));
+  PTRY(check_reserve(w, npts, nterms));
   // the point table [g | C_0 W_0 | C_1 W_1 ...]: decoded and subgroup-checked on the device
   std::vector<uint8_t> comp(48 * npts);
   memcpy(comp.data(), kk->opening_key, 48);
@@ -616,10 +591,10 @@ int plonk_kzg_batch_check(plonk_kzg_key* key, const uint64_t* points, const plon
     memcpy(comp.data() + 48 * (2 + 2 * k), proofs[k].witness, 48);
   }
   std::vector<int32_t> st;
-  PTRY_K(decode_points(&c, comp.data(), (uint32_t)npts, w.at<uint8_t>(KzgWork::COMP), w.at<G1Affine>(KzgWork::PTS),
+  PTRY(decode_points(&c, comp.data(), (uint32_t)npts, w.at<uint8_t>(KzgWork::COMP), w.at<G1Affine>(KzgWork::PTS),
                        w.at<int32_t>(KzgWork::KIND), &st));
   for (uint64_t i = 0; i < npts; ++i)
-    if (st[i] == VDEC_BAD) KZG_FAIL(PLONK_ERR_POINT, "a commitment is not a valid compressed point of G1");
+    if (st[i] == VDEC_BAD) API_FAIL(PLONK_ERR_POINT, "a commitment is not a valid compressed point of G1");
   const auto t1 = std::chrono::steady_clock::now();
   if (!u_override) u = kzg_batch_challenge(label, label_len, z.data(), proofs, count);
   kk->last_u = u;
@@ -629,7 +604,7 @@ int plonk_kzg_batch_check(plonk_kzg_key* key, const uint64_t* points, const plon
   HIP_TRY(hipMemcpyAsync(w.p[KzgWork::SC], sc.data(), 32 * nterms, hipMemcpyHostToDevice, c.stream));
   HIP_TRY(hipMemcpyAsync(w.p[KzgWork::IDS], ids.data(), 4 * nterms, hipMemcpyHostToDevice, c.stream));
   H1 sums[2];
-  PTRY_K(msm_run(&c, w.at<const uint32_t>(KzgWork::SC), w.at<const uint32_t>(KzgWork::IDS), count, 2 * count + 1,
+  PTRY(msm_run(&c, w.at<const uint32_t>(KzgWork::SC), w.at<const uint32_t>(KzgWork::IDS), count, 2 * count + 1,
                  w.at<const G1Affine>(KzgWork::PTS), w.at<const int32_t>(KzgWork::KIND), w.at<G1>(KzgWork::PART), sums));
   const auto t3 = std::chrono::steady_clock::now();
   const bool ok = pairing_check(sums, kk->x_h, kk->h);
@@ -644,7 +619,7 @@ int plonk_kzg_batch_check(plonk_kzg_key* key, const uint64_t* points, const plon
     info->ms_msm = ms_between(t2, t3);
     info->ms_pairing = ms_between(t3, t4);
   }
-  if (!ok) KZG_FAIL(PLONK_ERR_VERIFY, "the batch of openings does not verify (Error::PairingCheckFailure)");
+  if (!ok) API_FAIL(PLONK_ERR_VERIFY, "the batch of openings does not verify (Error::PairingCheckFailure)");
   return PLONK_OK;
   });
 }
@@ -652,12 +627,12 @@ int plonk_kzg_batch_check(plonk_kzg_key* key, const uint64_t* points, const plon
 int plonk_srs_check(plonk_kzg_key* key, const uint8_t seed32[32]) {
   const char* const api_fn = __func__;
   return plonk::api_guard(api_fn, [&]() -> int {
-  if (!key || !seed32) KZG_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
+  if (!key || !seed32) API_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
   KzgKey* kk = key->k;
   Ctx& c = *kk->c;
   CTX_ENTER(c, api_fn);
   HIP_TRY(hipSetDevice(c.device));
-  if (c.nccl_comm) KZG_FAIL(PLONK_ERR_STATE, "a context with a communicator holds only a range of the commit key");
+  if (c.nccl_comm) API_FAIL(PLONK_ERR_STATE, "a context with a communicator holds only a range of the commit key");
   if (!c.srs_table || !c.srs_n) return PLONK_ERR_NO_SRS;
   const uint64_t N = c.srs_n;
   const Fr r = kzg_srs_challenge(seed32, N, kk->opening_key);
@@ -665,24 +640,24 @@ int plonk_srs_check(plonk_kzg_key* key, const uint8_t seed32[32]) {
   KzgWork& w = kzg_work(&c);
   // t[0] = 1 for P_0, then t[1] = 0, t[2 + i] = r^i: sum A reads t + 2 (N - 1 terms over P_0 ..), sum B reads t + 1 (N terms:
   // the same scalars one place further, P_1 ..)
-  PTRY_K(w.need(KzgWork::POWERS, sizeof(Fr) * (N + 2)));
+  PTRY(w.need(KzgWork::POWERS, sizeof(Fr) * (N + 2)));
   Fr* t = w.at<Fr>(KzgWork::POWERS);
   const Fr head[2] = {Fr::one(), Fr::zero()};
   HIP_TRY(hipMemcpyAsync(t, head, sizeof head, hipMemcpyHostToDevice, c.stream));
-  PTRY_K(poly_power_array(&c, t + 2, N - 1, r));
-  PTRY_K(msm_reserve(&c, N));
+  PTRY(poly_power_array(&c, t + 2, N - 1, r));
+  PTRY(msm_reserve(&c, N));
   const Fr* sc[3] = {t, t + 2, t + 1};
   const uint64_t m[3] = {1, N - 1, N};
   const int cnt = N > 1 ? 3 : 1;
   G1 s[3];
-  PTRY_K(msm_group_sums(&c, sc, m, cnt, s));
+  PTRY(msm_group_sums(&c, sc, m, cnt, s));
   uint8_t p0[97];
   xyzz_to_affine97_host(s[0], p0);
   if (p0[96] || memcmp(p0, kk->g_aff.x.l, 48) || memcmp(p0 + 48, kk->g_aff.y.l, 48))
-    KZG_FAIL(PLONK_ERR_VERIFY, "the first point of the commit key is not the opening key's g");
+    API_FAIL(PLONK_ERR_VERIFY, "the first point of the commit key is not the opening key's g");
   if (N > 1) {
     const H1 sums[2] = {h1_of_g1(s[1]), h1_of_g1(s[2])};
-    if (!pairing_check(sums, kk->x_h, kk->h)) KZG_FAIL(PLONK_ERR_VERIFY, "the commit key is not the powers of the opening key's tau");
+    if (!pairing_check(sums, kk->x_h, kk->h)) API_FAIL(PLONK_ERR_VERIFY, "the commit key is not the powers of the opening key's tau");
   }
   return PLONK_OK;
   });

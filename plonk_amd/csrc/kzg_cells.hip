@@ -27,10 +27,7 @@
 #include "kzg_domain.hpp"
 #include "kzg_evals.hpp"
 #include "kzg_cells.hpp"
-#include "kzg_slot.cuh"
-
-#define PTRY_C(expr) do { int _rc = (expr); if (_rc) return _rc; } while (0)
-#define KZC_FAIL(code, msg) return (plonk::set_last_error(api_fn, msg, __FILE__, __LINE__), code)
+#include "devmem.cuh"
 
 namespace plonk {
 
@@ -125,7 +122,7 @@ int kzc_table_build(Ctx* c, uint32_t log_n, uint32_t log_cell, const GlvScalar* 
   HIP_TRY(hipGetLastError());
   for (uint64_t u = 0; u < l; u += KZD_MAX_CHUNK) {   // grid.y of the batched transform
     const uint32_t cnt = (uint32_t)(l - u < KZD_MAX_CHUNK ? l - u : KZD_MAX_CHUNK);
-    PTRY_C(kzd_transform(c, (G1RSlot*)table + u * size, size, log_r + 1, cnt, false, tw, tw_log, nullptr, nullptr));
+    PTRY(kzd_transform(c, (G1RSlot*)table + u * size, size, log_r + 1, cnt, false, tw, tw_log, nullptr, nullptr));
   }
   return PLONK_OK;
 }
@@ -177,10 +174,10 @@ int kzc_reduce(Ctx* c, void* ws, uint64_t stride, uint32_t log_r, uint64_t slice
 // ---- the state a handle holds for these calls ------------------------------------------------------------------------------
 namespace {
 
-struct KzgCells {
+struct KzcBufs {
   enum { WS, F, G, EVALS, CELLS, TMP, OUT48, DESC, META, NBUF };   // grow-only
-  void* p[NBUF] = {};
-  uint64_t cap[NBUF] = {};
+};
+struct KzgCells : KzcBufs, DevBufs<KzcBufs::NBUF> {
   G1RSlot* table[KZD_MAX_LOG + 1] = {};   // by log_cell: built by the first call with that cell size
   Fr* ntt_tw[KZD_MAX_LOG + 1] = {};       // by log_cell: w_(2r)^e, e < r, where kzc_ntt_kernel takes the size
   uint64_t table_bytes = 0;
@@ -189,30 +186,12 @@ struct KzgCells {
   ~KzgCells() {
     for (G1RSlot* t : table) (void)hipFree(t);
     for (Fr* t : ntt_tw) (void)hipFree(t);
-    for (int i = 0; i < NBUF; ++i) (void)hipFree(p[i]);
   }
-  int need(int i, uint64_t bytes) {
-    if (bytes <= cap[i]) return PLONK_OK;
-    (void)hipFree(p[i]);
-    p[i] = nullptr;
-    cap[i] = 0;
-    HIP_TRY(hipMalloc(&p[i], bytes));
-    cap[i] = bytes;
-    return PLONK_OK;
-  }
-  template <class T>
-  T* at(int i) const { return (T*)p[i]; }
 };
 
 KzgCells* kzc_state(void** slot) {
   if (!*slot) *slot = new KzgCells();
   return (KzgCells*)*slot;
-}
-
-Fr kzc_root(uint32_t log_size) {   // the generator of the size-2^log_size domain, as ntt.hip derives it
-  Fr w = fr_root_of_unity();
-  for (uint32_t i = log_size; i < 32; ++i) w = w.sqr();
-  return w;
 }
 
 int table_ready(const KzdView& v, KzgCells* e, uint32_t log_cell, uint32_t* built) {
@@ -221,7 +200,7 @@ int table_ready(const KzdView& v, KzgCells* e, uint32_t log_cell, uint32_t* buil
   const uint32_t log_size = v.log_n - log_cell + 1;
   if (log_size <= KZC_NTT_MAX_LOG && !e->ntt_tw[log_cell]) {   // the powers the scalar transform reads: at most 32 KiB
     std::vector<Fr> pw(1ull << (log_size - 1));
-    const Fr w = kzc_root(log_size);
+    const Fr w = fr_domain_root(log_size);
     Fr x = Fr::one();
     for (Fr& y : pw) {
       y = x;
@@ -263,15 +242,15 @@ int cells_body(const KzdView& v, KzgCells* e, uint32_t log_cell, const void* con
   info.slices = plan.slices;
   info.chunk_polys = chunk;
   info.workspace_bytes = plan.ws_bytes;
-  PTRY_C(table_ready(v, e, log_cell, &info.built_table));
-  PTRY_C(e->need(KzgCells::WS, plan.ws_bytes));
-  PTRY_C(e->need(KzgCells::F, sizeof(Fr) * n * chunk));
-  PTRY_C(e->need(KzgCells::G, sizeof(Fr) * 2 * n * chunk));
-  PTRY_C(e->need(KzgCells::EVALS, sizeof(Fr) * n * chunk));
-  PTRY_C(e->need(KzgCells::CELLS, sizeof(Fr) * n * chunk));
-  PTRY_C(e->need(KzgCells::TMP, sizeof(Fr) * 2 * n));
-  PTRY_C(e->need(KzgCells::OUT48, 48 * r * chunk));
-  if (commitments48) PTRY_C(msm_reserve(&c, n));
+  PTRY(table_ready(v, e, log_cell, &info.built_table));
+  PTRY(e->need(KzgCells::WS, plan.ws_bytes));
+  PTRY(e->need(KzgCells::F, sizeof(Fr) * n * chunk));
+  PTRY(e->need(KzgCells::G, sizeof(Fr) * 2 * n * chunk));
+  PTRY(e->need(KzgCells::EVALS, sizeof(Fr) * n * chunk));
+  PTRY(e->need(KzgCells::CELLS, sizeof(Fr) * n * chunk));
+  PTRY(e->need(KzgCells::TMP, sizeof(Fr) * 2 * n));
+  PTRY(e->need(KzgCells::OUT48, 48 * r * chunk));
+  if (commitments48) PTRY(msm_reserve(&c, n));
   G1RSlot* ws = e->at<G1RSlot>(KzgCells::WS);
   Fr* f = e->at<Fr>(KzgCells::F);
   Fr* g = e->at<Fr>(KzgCells::G);
@@ -289,28 +268,28 @@ int cells_body(const KzdView& v, KzgCells* e, uint32_t log_cell, const void* con
       if (trimmed[first + b])
         HIP_TRY(hipMemcpyAsync(f + (uint64_t)b * n, polys[first + b], sizeof(Fr) * trimmed[first + b], hipMemcpyDefault, c.stream));
     // cell values: the ordinary forward transform in cell-major order; G^(u) = NTT_2r of the gathered coefficients
-    PTRY_C(kzc_gather(&c, f, L, log_cell, cnt, g));
+    PTRY(kzc_gather(&c, f, L, log_cell, cnt, g));
     for (uint32_t b = 0; b < cnt; ++b) {
-      PTRY_C(ntt_device(&c, f + (uint64_t)b * n, ev + (uint64_t)b * n, tmp, L, false, false, n));
+      PTRY(ntt_device(&c, f + (uint64_t)b * n, ev + (uint64_t)b * n, tmp, L, false, false, n));
       for (uint64_t u = 0; u < l && log_r + 1 > KZC_NTT_MAX_LOG; ++u) {
         Fr* gu = g + (uint64_t)b * 2 * n + u * size;
-        PTRY_C(ntt_device(&c, gu, gu, tmp, log_r + 1, false, false, size));
+        PTRY(ntt_device(&c, gu, gu, tmp, log_r + 1, false, false, size));
       }
     }
-    if (log_r + 1 <= KZC_NTT_MAX_LOG) PTRY_C(kzc_ntt(&c, g, log_r + 1, l, cnt, e->ntt_tw[log_cell]));
-    PTRY_C(kzc_transpose(&c, ev, L, log_cell, cnt, cl));
-    PTRY_C(kzc_mulacc(&c, e->table[log_cell], g, 2 * n, ws, stride, L, log_cell, plan.slices, cnt, size_inv));
+    if (log_r + 1 <= KZC_NTT_MAX_LOG) PTRY(kzc_ntt(&c, g, log_r + 1, l, cnt, e->ntt_tw[log_cell]));
+    PTRY(kzc_transpose(&c, ev, L, log_cell, cnt, cl));
+    PTRY(kzc_mulacc(&c, e->table[log_cell], g, 2 * n, ws, stride, L, log_cell, plan.slices, cnt, size_inv));
     info.scalar_muls += 2 * n * cnt;
-    PTRY_C(kzc_reduce(&c, ws, stride, log_r, plan.slices, cnt));
-    PTRY_C(kzd_transform(&c, ws, stride, log_r + 1, cnt, true, v.tw, L + 1, &info.stage_launches, &info.scalar_muls));
-    PTRY_C(kzd_extract(&c, ws, stride, log_r, cnt));
-    PTRY_C(kzd_transform(&c, ws + r, stride, log_r, cnt, false, v.tw, L + 1, &info.stage_launches, &info.scalar_muls));
-    PTRY_C(kzd_finish(&c, ws, stride, r, log_r, cnt, true, out48));
+    PTRY(kzc_reduce(&c, ws, stride, log_r, plan.slices, cnt));
+    PTRY(kzd_transform(&c, ws, stride, log_r + 1, cnt, true, v.tw, L + 1, &info.stage_launches, &info.scalar_muls));
+    PTRY(kzd_extract(&c, ws, stride, log_r, cnt));
+    PTRY(kzd_transform(&c, ws + r, stride, log_r, cnt, false, v.tw, L + 1, &info.stage_launches, &info.scalar_muls));
+    PTRY(kzd_finish(&c, ws, stride, r, log_r, cnt, true, out48));
     HIP_TRY(hipMemcpyAsync((uint8_t*)cells + sizeof(Fr) * n * first, cl, sizeof(Fr) * n * cnt, hipMemcpyDefault, c.stream));
     HIP_TRY(hipMemcpyAsync((uint8_t*)proofs48 + 48 * r * first, out48, 48 * r * cnt, hipMemcpyDefault, c.stream));
     if (commitments48) {
       comm.resize(48ull * cnt);
-      PTRY_C(kzd_commit(&c, f, n, trimmed + first, cnt, comm.data()));
+      PTRY(kzd_commit(&c, f, n, trimmed + first, cnt, comm.data()));
       HIP_TRY(hipMemcpyAsync((uint8_t*)commitments48 + 48 * first, comm.data(), 48ull * cnt, hipMemcpyDefault, c.stream));
     }
     HIP_TRY(hipStreamSynchronize(c.stream));   // the chunk's buffers are reused by the next one
@@ -323,26 +302,26 @@ int cells_body(const KzdView& v, KzgCells* e, uint32_t log_cell, const void* con
 
 int cells_impl(const char* api_fn, plonk_kzg_domain* dom, uint32_t log_cell, const void* const* polys, const uint64_t* lens, uint64_t count,
                void* cells, void* proofs48, void* commitments48, bool resident) {
-  if (!dom) KZC_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
+  if (!dom) API_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
   const KzdView v = kzd_view(dom);
-  if (kzc_check_cell(v.log_n, log_cell)) KZC_FAIL(PLONK_ERR_ARG, "invalid argument: log_cell must be in [1, log_n - 1]");
-  if (count > KZD_MAX_COUNT) KZC_FAIL(PLONK_ERR_ARG, "invalid argument: at most 65536 polynomials per call");
-  if (count && (!polys || !lens || !cells || !proofs48)) KZC_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
+  if (kzc_check_cell(v.log_n, log_cell)) API_FAIL(PLONK_ERR_ARG, "invalid argument: log_cell must be in [1, log_n - 1]");
+  if (count > KZD_MAX_COUNT) API_FAIL(PLONK_ERR_ARG, "invalid argument: at most 65536 polynomials per call");
+  if (count && (!polys || !lens || !cells || !proofs48)) API_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
   for (uint64_t i = 0; i < count; ++i)
-    if (lens[i] && !polys[i]) KZC_FAIL(PLONK_ERR_ARG, "invalid argument: polys[i] is NULL with lens[i] > 0");
+    if (lens[i] && !polys[i]) API_FAIL(PLONK_ERR_ARG, "invalid argument: polys[i] is NULL with lens[i] > 0");
   Ctx& c = *v.c;
   CTX_ENTER(c, api_fn);
   HIP_TRY(hipSetDevice(c.device));
-  if (!kzd_view(dom).key_current) KZC_FAIL(PLONK_ERR_STATE, "the domain is bound to a commit key that was replaced on its context");
-  if (c.nccl_comm) KZC_FAIL(PLONK_ERR_STATE, "a context with a communicator holds only a range of the commit key");
+  if (!kzd_view(dom).key_current) API_FAIL(PLONK_ERR_STATE, "the domain is bound to a commit key that was replaced on its context");
+  if (c.nccl_comm) API_FAIL(PLONK_ERR_STATE, "a context with a communicator holds only a range of the commit key");
   if (!count) return PLONK_OK;
   KzgCells* e = kzc_state(v.cells);
   std::vector<uint64_t> trimmed(count);
   if (resident) {
-    PTRY_C(e->need(KzgCells::DESC, sizeof(KzdDesc) * count));
-    PTRY_C(e->need(KzgCells::META, 16 * count));
+    PTRY(e->need(KzgCells::DESC, sizeof(KzdDesc) * count));
+    PTRY(e->need(KzgCells::META, 16 * count));
   }
-  PTRY_C(kzd_lengths(api_fn, &c, v.log_n, polys, lens, count, resident, e->at<KzdDesc>(KzgCells::DESC),
+  PTRY(kzd_lengths(api_fn, &c, v.log_n, polys, lens, count, resident, e->at<KzdDesc>(KzgCells::DESC),
                      e->at<unsigned long long>(KzgCells::META), trimmed.data()));
   const int rc = cells_body(kzd_view(dom), e, log_cell, polys, trimmed.data(), count, cells, proofs48, commitments48);
   if (rc != PLONK_OK) (void)hipStreamSynchronize(c.stream);   // an error leaves nothing of the call queued
@@ -379,13 +358,13 @@ int plonk_kzg_open_cells_dev(plonk_kzg_domain* dom, uint32_t log_cell, const voi
 int plonk_kzg_cell_points(plonk_kzg_domain* dom, uint32_t log_cell, uint64_t* x, uint64_t* shift) {
   const char* const api_fn = __func__;
   return plonk::api_guard(api_fn, [&]() -> int {
-  if (!dom || !x) KZC_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
+  if (!dom || !x) API_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
   const KzdView v = kzd_view(dom);
-  if (kzc_check_cell(v.log_n, log_cell)) KZC_FAIL(PLONK_ERR_ARG, "invalid argument: log_cell must be in [1, log_n - 1]");
+  if (kzc_check_cell(v.log_n, log_cell)) API_FAIL(PLONK_ERR_ARG, "invalid argument: log_cell must be in [1, log_n - 1]");
   Ctx& c = *v.c;
   CTX_ENTER(c, api_fn);
-  if (!kzd_view(dom).key_current) KZC_FAIL(PLONK_ERR_STATE, "the domain is bound to a commit key that was replaced on its context");
-  const Fr w = kzc_root(v.log_n), phi = kzc_root(v.log_n - log_cell);
+  if (!kzd_view(dom).key_current) API_FAIL(PLONK_ERR_STATE, "the domain is bound to a commit key that was replaced on its context");
+  const Fr w = fr_domain_root(v.log_n), phi = fr_domain_root(v.log_n - log_cell);
   Fr a = Fr::one(), b = Fr::one();
   for (uint64_t k = 0; k < (1ull << (v.log_n - log_cell)); ++k) {
     memcpy(x + 4 * k, a.l, 32);
@@ -400,11 +379,11 @@ int plonk_kzg_cell_points(plonk_kzg_domain* dom, uint32_t log_cell, uint64_t* x,
 int plonk_kzg_cells_last(plonk_kzg_domain* dom, plonk_kzg_cells_info* out) {
   const char* const api_fn = __func__;
   return plonk::api_guard(api_fn, [&]() -> int {
-  if (!dom || !out) KZC_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
+  if (!dom || !out) API_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
   const KzdView v = kzd_view(dom);
   Ctx& c = *v.c;
   CTX_ENTER(c, api_fn);
-  if (!kzd_view(dom).key_current) KZC_FAIL(PLONK_ERR_STATE, "the domain is bound to a commit key that was replaced on its context");
+  if (!kzd_view(dom).key_current) API_FAIL(PLONK_ERR_STATE, "the domain is bound to a commit key that was replaced on its context");
   const KzgCells* e = (const KzgCells*)*v.cells;
   plonk_kzg_cells_info info = {};
   if (e) {

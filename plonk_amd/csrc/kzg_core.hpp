@@ -24,6 +24,12 @@ HD bool kzg_fr_load(const uint64_t limbs[4], Fr* out) {
   return false;   // == q
 }
 
+// coefficients (4 limbs each) up to the last non-zero one: Polynomial::from_coefficients_vec's trim on the host
+HD uint64_t host_trimmed(const uint64_t* p, uint64_t len) {
+  while (len && !(p[4 * len - 4] | p[4 * len - 3] | p[4 * len - 2] | p[4 * len - 1])) --len;
+  return len;
+}
+
 // batch_challenge (key.rs:571-591) on a fresh Transcript::new(label)
 HD Fr kzg_batch_challenge(const uint8_t* label, size_t label_len, const Fr* points, const plonk_kzg_proof* proofs, uint64_t count) {
   Transcript tr(label, label_len);

@@ -32,10 +32,7 @@
 #include "kzg_domain.hpp"
 #include "kzg_evals.hpp"
 #include "kzg_cells.hpp"
-#include "kzg_slot.cuh"
-
-#define PTRY_D(expr) do { int _rc = (expr); if (_rc) return _rc; } while (0)
-#define KZD_FAIL(code, msg) return (plonk::set_last_error(api_fn, msg, __FILE__, __LINE__), code)
+#include "devmem.cuh"
 
 namespace plonk { struct KzgDomain; }
 struct plonk_kzg_domain {
@@ -179,17 +176,11 @@ __global__ void kzd_scan_kernel(const KzdDesc* __restrict__ desc, unsigned long 
 // ---- launchers (kzg_domain.hpp) ------------------------------------------------------------------------------------------
 static dim3 kzd_grid(uint64_t lanes, uint32_t batch) { return dim3((uint32_t)((lanes + KZD_LANES - 1) / KZD_LANES), batch); }
 
-static Fr kzd_root(uint32_t log_size) {   // the generator of the size-2^log_size domain, as ntt.hip derives it
-  Fr w = fr_root_of_unity();
-  for (uint32_t i = log_size; i < 32; ++i) w = w.sqr();
-  return w;
-}
-
 int kzd_twiddles_create(Ctx* c, uint32_t tw_log, GlvScalar** out_dev) {
   const uint64_t count = 1ull << (tw_log - 1);
   GlvScalar* t = nullptr;
   HIP_TRY(hipMalloc((void**)&t, sizeof(GlvScalar) * count));
-  hipLaunchKernelGGL(kzd_twiddle_kernel, kzd_grid(count, 1), dim3(KZD_LANES), 0, c->stream, kzd_root(tw_log), count, t);
+  hipLaunchKernelGGL(kzd_twiddle_kernel, kzd_grid(count, 1), dim3(KZD_LANES), 0, c->stream, fr_domain_root(tw_log), count, t);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
     (void)hipFree(t);
@@ -250,58 +241,32 @@ int kzd_load_raw(Ctx* c, const G1Affine* xy96, uint64_t count, void* slots) {
 }
 
 // ---- the handle ------------------------------------------------------------------------------------------------------------
-struct KzgDomain {
+struct KzdBufs {
   enum { WS, F, G, EVALS, TMP, OUT48, DESC, META, NBUF };   // grow-only buffers of the open calls
+};
+struct KzgDomain : KzdBufs, DevBufs<KzdBufs::NBUF> {
   Ctx* c = nullptr;
   uint32_t log_n = 0;
   uint64_t srs_gen = 0;
   G1RSlot* A = nullptr;          // DFT_N(a), bit-reversed: N slots
   GlvScalar* tw = nullptr;       // w_N^e, e < n
   uint64_t fixed_bytes = 0;      // A + tw
-  void* p[NBUF] = {};
-  uint64_t cap[NBUF] = {};
   uint64_t ws_cap = KZD_WS_CAP_DEFAULT;
   plonk_kzg_domain_info last = {};
   void* evals = nullptr;         // the Lagrange points and workspace of the evaluation-form calls (kzg_evals.hip); not in device_bytes()
   void* cells = nullptr;         // the A^(u) tables and workspace of the cell proofs (kzg_cells.hip); not in device_bytes()
-  ~KzgDomain() {
+  ~KzgDomain() {   // in this order: the cell state, the evaluation-form state, the fixed buffers; the base frees the grow-only ones last
     kzc_release(cells);
     kze_release(evals);
     (void)hipFree(A);
     (void)hipFree(tw);
-    for (int i = 0; i < NBUF; ++i) (void)hipFree(p[i]);
   }
-  int need(int i, uint64_t bytes) {
-    if (bytes <= cap[i]) return PLONK_OK;
-    (void)hipFree(p[i]);
-    p[i] = nullptr;
-    cap[i] = 0;
-    HIP_TRY(hipMalloc(&p[i], bytes));
-    cap[i] = bytes;
-    return PLONK_OK;
-  }
-  template <class T>
-  T* at(int i) const { return (T*)p[i]; }
-  uint64_t device_bytes() const {
-    uint64_t s = fixed_bytes;
-    for (int i = 0; i < NBUF; ++i) s += cap[i];
-    return s;
-  }
+  uint64_t device_bytes() const { return fixed_bytes + bytes(); }
 };
 
 KzdView kzd_view(plonk_kzg_domain* dom) {
   KzgDomain* d = dom->d;
   return KzdView{d->c, d->log_n, d->srs_gen == d->c->srs_gen, d->tw, &d->evals, &d->cells, d->ws_cap};
-}
-
-static void identity48(uint8_t out[48]) {
-  memset(out, 0, 48);
-  out[0] = 0xC0;
-}
-
-static uint64_t host_trimmed(const uint64_t* p, uint64_t len) {
-  while (len && !(p[4 * len - 4] | p[4 * len - 3] | p[4 * len - 2] | p[4 * len - 1])) --len;
-  return len;
 }
 
 static int domain_create_body(Ctx& c, uint32_t log_n, KzgDomain* d) {
@@ -311,10 +276,10 @@ static int domain_create_body(Ctx& c, uint32_t log_n, KzgDomain* d) {
   d->srs_gen = c.srs_gen;
   HIP_TRY(hipMalloc((void**)&d->A, sizeof(G1RSlot) * N));
   d->fixed_bytes = sizeof(G1RSlot) * N + sizeof(GlvScalar) * n;
-  PTRY_D(kzd_twiddles_create(&c, log_n + 1, &d->tw));
+  PTRY(kzd_twiddles_create(&c, log_n + 1, &d->tw));
   hipLaunchKernelGGL(kzd_load_kernel, kzd_grid(N, 1), dim3(KZD_LANES), 0, c.stream, (const G1AffineR*)c.srs_table, n - 1, N, d->A);
   HIP_TRY(hipGetLastError());
-  PTRY_D(kzd_transform(&c, d->A, N, log_n + 1, 1, false, d->tw, log_n + 1, nullptr, nullptr));
+  PTRY(kzd_transform(&c, d->A, N, log_n + 1, 1, false, d->tw, log_n + 1, nullptr, nullptr));
   HIP_TRY(hipStreamSynchronize(c.stream));
   d->last.log_n = log_n;
   d->last.workspace_cap_bytes = d->ws_cap;
@@ -336,7 +301,7 @@ int kzd_commit(Ctx* c, const Fr* f, uint64_t n, const uint64_t* m, uint32_t cnt,
       sc[g] = f + (uint64_t)i * n; mm[g] = m[i]; which[g] = i; ++g;
     }
     if (g == MSM_MAX_BATCH || (i == cnt && g)) {
-      PTRY_D(msm_group_sums(c, sc, mm, g, sums));
+      PTRY(msm_group_sums(c, sc, mm, g, sums));
       batch_xyzz_to_affine97(sums, g, aff);
       for (int k = 0; k < g; ++k) g1_compress97(aff[k], out48 + 48ull * which[k]);
       g = 0;
@@ -352,13 +317,13 @@ static int domain_open_body(KzgDomain* d, const void* const* polys, const uint64
   const uint64_t n = 1ull << L, N = 2 * n;
   const KzdPlan plan = kzd_plan(L, count, d->ws_cap);
   const uint64_t chunk = plan.chunk_polys;
-  PTRY_D(d->need(KzgDomain::WS, plan.ws_bytes));
-  PTRY_D(d->need(KzgDomain::F, sizeof(Fr) * n * chunk));
-  PTRY_D(d->need(KzgDomain::G, sizeof(Fr) * N * chunk));
-  PTRY_D(d->need(KzgDomain::EVALS, sizeof(Fr) * n * chunk));
-  PTRY_D(d->need(KzgDomain::TMP, sizeof(Fr) * N));
-  PTRY_D(d->need(KzgDomain::OUT48, 48 * n * chunk));
-  if (commitments48) PTRY_D(msm_reserve(&c, n));
+  PTRY(d->need(KzgDomain::WS, plan.ws_bytes));
+  PTRY(d->need(KzgDomain::F, sizeof(Fr) * n * chunk));
+  PTRY(d->need(KzgDomain::G, sizeof(Fr) * N * chunk));
+  PTRY(d->need(KzgDomain::EVALS, sizeof(Fr) * n * chunk));
+  PTRY(d->need(KzgDomain::TMP, sizeof(Fr) * N));
+  PTRY(d->need(KzgDomain::OUT48, 48 * n * chunk));
+  if (commitments48) PTRY(msm_reserve(&c, n));
   G1RSlot* ws = d->at<G1RSlot>(KzgDomain::WS);
   Fr* f = d->at<Fr>(KzgDomain::F);
   Fr* g = d->at<Fr>(KzgDomain::G);
@@ -383,20 +348,20 @@ static int domain_open_body(KzgDomain* d, const void* const* polys, const uint64
     hipLaunchKernelGGL(kzd_reverse_kernel, dim3((uint32_t)((N + 255) / 256), cnt), dim3(256), 0, c.stream, (const Fr*)f, n, g);
     HIP_TRY(hipGetLastError());
     for (uint32_t b = 0; b < cnt; ++b) {
-      PTRY_D(ntt_device(&c, f + (uint64_t)b * n, ev + (uint64_t)b * n, tmp, L, false, false, n));
-      PTRY_D(ntt_device(&c, g + (uint64_t)b * N, g + (uint64_t)b * N, tmp, L + 1, false, false, N));
+      PTRY(ntt_device(&c, f + (uint64_t)b * n, ev + (uint64_t)b * n, tmp, L, false, false, n));
+      PTRY(ntt_device(&c, g + (uint64_t)b * N, g + (uint64_t)b * N, tmp, L + 1, false, false, N));
     }
-    PTRY_D(kzd_pointwise(&c, d->A, g, N, ws, N, L + 1, cnt, n_inv));
+    PTRY(kzd_pointwise(&c, d->A, g, N, ws, N, L + 1, cnt, n_inv));
     info.scalar_muls += N * cnt;
-    PTRY_D(kzd_transform(&c, ws, N, L + 1, cnt, true, d->tw, L + 1, &info.stage_launches, &info.scalar_muls));
-    PTRY_D(kzd_extract(&c, ws, N, L, cnt));
-    PTRY_D(kzd_transform(&c, ws + n, N, L, cnt, false, d->tw, L + 1, &info.stage_launches, &info.scalar_muls));
-    PTRY_D(kzd_finish(&c, ws, N, n, L, cnt, true, out48));
+    PTRY(kzd_transform(&c, ws, N, L + 1, cnt, true, d->tw, L + 1, &info.stage_launches, &info.scalar_muls));
+    PTRY(kzd_extract(&c, ws, N, L, cnt));
+    PTRY(kzd_transform(&c, ws + n, N, L, cnt, false, d->tw, L + 1, &info.stage_launches, &info.scalar_muls));
+    PTRY(kzd_finish(&c, ws, N, n, L, cnt, true, out48));
     HIP_TRY(hipMemcpyAsync((uint8_t*)evaluations + sizeof(Fr) * n * first, ev, sizeof(Fr) * n * cnt, hipMemcpyDefault, c.stream));
     HIP_TRY(hipMemcpyAsync((uint8_t*)witnesses48 + 48 * n * first, out48, 48 * n * cnt, hipMemcpyDefault, c.stream));
     if (commitments48) {
       comm.resize(48ull * cnt);
-      PTRY_D(kzd_commit(&c, f, n, trimmed + first, cnt, comm.data()));
+      PTRY(kzd_commit(&c, f, n, trimmed + first, cnt, comm.data()));
       HIP_TRY(hipMemcpyAsync((uint8_t*)commitments48 + 48 * first, comm.data(), 48ull * cnt, hipMemcpyDefault, c.stream));
     }
     HIP_TRY(hipStreamSynchronize(c.stream));   // the chunk's buffers are reused by the next one
@@ -432,9 +397,9 @@ int kzd_lengths(const char* api_fn, Ctx* c, uint32_t log_n, const void* const* p
     if (e == hipSuccess) e = hipMemcpyAsync(meta.data(), meta_dev, 16 * count, hipMemcpyDeviceToHost, c->stream);
     const hipError_t es = hipStreamSynchronize(c->stream);
     if (e == hipSuccess) e = es;
-    if (e != hipSuccess) KZD_FAIL(PLONK_ERR_HIP, hipGetErrorString(e));
+    if (e != hipSuccess) API_FAIL(PLONK_ERR_HIP, hipGetErrorString(e));
     for (uint64_t i = 0; i < count; ++i) {
-      if (meta[2 * i + 1]) KZD_FAIL(PLONK_ERR_DATA, "non-canonical coefficient");
+      if (meta[2 * i + 1]) API_FAIL(PLONK_ERR_DATA, "non-canonical coefficient");
       trimmed[i] = meta[2 * i];
     }
   } else {
@@ -443,7 +408,7 @@ int kzd_lengths(const char* api_fn, Ctx* c, uint32_t log_n, const void* const* p
       trimmed[i] = host_trimmed(p, lens[i]);
       Fr t;
       for (uint64_t k = 0; k < trimmed[i]; ++k)
-        if (!kzg_fr_load(p + 4 * k, &t)) KZD_FAIL(PLONK_ERR_DATA, "non-canonical coefficient");
+        if (!kzg_fr_load(p + 4 * k, &t)) API_FAIL(PLONK_ERR_DATA, "non-canonical coefficient");
     }
   }
   for (uint64_t i = 0; i < count; ++i)
@@ -453,25 +418,25 @@ int kzd_lengths(const char* api_fn, Ctx* c, uint32_t log_n, const void* const* p
 
 static int domain_open_impl(const char* api_fn, plonk_kzg_domain* dom, const void* const* polys, const uint64_t* lens, uint64_t count,
                             void* evaluations, void* witnesses48, void* commitments48, bool resident) {
-  if (!dom) KZD_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
-  if (count > KZD_MAX_COUNT) KZD_FAIL(PLONK_ERR_ARG, "invalid argument: at most 65536 polynomials per call");
-  if (count && (!polys || !lens || !evaluations || !witnesses48)) KZD_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
+  if (!dom) API_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
+  if (count > KZD_MAX_COUNT) API_FAIL(PLONK_ERR_ARG, "invalid argument: at most 65536 polynomials per call");
+  if (count && (!polys || !lens || !evaluations || !witnesses48)) API_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
   for (uint64_t i = 0; i < count; ++i)
-    if (lens[i] && !polys[i]) KZD_FAIL(PLONK_ERR_ARG, "invalid argument: polys[i] is NULL with lens[i] > 0");
+    if (lens[i] && !polys[i]) API_FAIL(PLONK_ERR_ARG, "invalid argument: polys[i] is NULL with lens[i] > 0");
   KzgDomain* d = dom->d;
   Ctx& c = *d->c;
   CTX_ENTER(c, api_fn);
   HIP_TRY(hipSetDevice(c.device));
-  if (d->srs_gen != c.srs_gen) KZD_FAIL(PLONK_ERR_STATE, "the domain is bound to a commit key that was replaced on its context");
-  if (c.nccl_comm) KZD_FAIL(PLONK_ERR_STATE, "a context with a communicator holds only a range of the commit key");
+  if (d->srs_gen != c.srs_gen) API_FAIL(PLONK_ERR_STATE, "the domain is bound to a commit key that was replaced on its context");
+  if (c.nccl_comm) API_FAIL(PLONK_ERR_STATE, "a context with a communicator holds only a range of the commit key");
   if (!count) return PLONK_OK;
   // lengths without trailing zeros and the canonical-form check, before anything is queued or written
   std::vector<uint64_t> trimmed(count);
   if (resident) {
-    PTRY_D(d->need(KzgDomain::DESC, sizeof(KzdDesc) * count));
-    PTRY_D(d->need(KzgDomain::META, 16 * count));
+    PTRY(d->need(KzgDomain::DESC, sizeof(KzdDesc) * count));
+    PTRY(d->need(KzgDomain::META, 16 * count));
   }
-  PTRY_D(kzd_lengths(api_fn, &c, d->log_n, polys, lens, count, resident, d->at<KzdDesc>(KzgDomain::DESC),
+  PTRY(kzd_lengths(api_fn, &c, d->log_n, polys, lens, count, resident, d->at<KzdDesc>(KzgDomain::DESC),
                      d->at<unsigned long long>(KzgDomain::META), trimmed.data()));
   const int rc = domain_open_body(d, polys, trimmed.data(), count, evaluations, witnesses48, commitments48);
   if (rc != PLONK_OK) (void)hipStreamSynchronize(c.stream);   // an error leaves nothing of the call queued
@@ -487,14 +452,14 @@ extern "C" {
 int plonk_kzg_domain_create(plonk_ctx* ctx, uint32_t log_n, plonk_kzg_domain** out) {
   const char* const api_fn = __func__;
   return plonk::api_guard(api_fn, [&]() -> int {
-  if (!ctx || !out) KZD_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
+  if (!ctx || !out) API_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
   *out = nullptr;
   Ctx& c = ctx->c;
   CTX_ENTER(c, api_fn);
   HIP_TRY(hipSetDevice(c.device));
   switch (kzd_check_create(log_n, c.nccl_comm != nullptr, c.srs_table != nullptr && c.srs_n != 0, c.srs_n)) {
-    case PLONK_ERR_ARG: KZD_FAIL(PLONK_ERR_ARG, "invalid argument: log_n must be in [1, 20]");
-    case PLONK_ERR_STATE: KZD_FAIL(PLONK_ERR_STATE, "a context with a communicator holds only a range of the commit key");
+    case PLONK_ERR_ARG: API_FAIL(PLONK_ERR_ARG, "invalid argument: log_n must be in [1, 20]");
+    case PLONK_ERR_STATE: API_FAIL(PLONK_ERR_STATE, "a context with a communicator holds only a range of the commit key");
     case PLONK_ERR_NO_SRS: return PLONK_ERR_NO_SRS;
     case PLONK_ERR_DEGREE: return PLONK_ERR_DEGREE;
     default: break;
@@ -523,12 +488,12 @@ void plonk_kzg_domain_destroy(plonk_kzg_domain* dom) {
 int plonk_kzg_domain_points(plonk_kzg_domain* dom, uint64_t* out) {
   const char* const api_fn = __func__;
   return plonk::api_guard(api_fn, [&]() -> int {
-  if (!dom || !out) KZD_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
+  if (!dom || !out) API_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
   KzgDomain* d = dom->d;
   Ctx& c = *d->c;
   CTX_ENTER(c, api_fn);
-  if (d->srs_gen != c.srs_gen) KZD_FAIL(PLONK_ERR_STATE, "the domain is bound to a commit key that was replaced on its context");
-  const Fr w = kzd_root(d->log_n);
+  if (d->srs_gen != c.srs_gen) API_FAIL(PLONK_ERR_STATE, "the domain is bound to a commit key that was replaced on its context");
+  const Fr w = fr_domain_root(d->log_n);
   Fr x = Fr::one();
   for (uint64_t i = 0; i < (1ull << d->log_n); ++i) {
     memcpy(out + 4 * i, x.l, 32);
@@ -557,11 +522,11 @@ int plonk_kzg_open_domain_dev(plonk_kzg_domain* dom, const void* const* polys_de
 int plonk_kzg_domain_last(plonk_kzg_domain* dom, plonk_kzg_domain_info* out) {
   const char* const api_fn = __func__;
   return plonk::api_guard(api_fn, [&]() -> int {
-  if (!dom || !out) KZD_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
+  if (!dom || !out) API_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
   KzgDomain* d = dom->d;
   Ctx& c = *d->c;
   CTX_ENTER(c, api_fn);
-  if (d->srs_gen != c.srs_gen) KZD_FAIL(PLONK_ERR_STATE, "the domain is bound to a commit key that was replaced on its context");
+  if (d->srs_gen != c.srs_gen) API_FAIL(PLONK_ERR_STATE, "the domain is bound to a commit key that was replaced on its context");
   *out = d->last;
   out->device_bytes = d->device_bytes();
   out->workspace_cap_bytes = d->ws_cap;

@@ -25,104 +25,19 @@
 #include "plonk_internal.hpp"
 #include "api_guard.hpp"
 #include "poly.hpp"
-#include "fr29.cuh"
+#include "devmem.cuh"
 #include "hostg1.hpp"
 #include "kzg_core.hpp"
 #include "kzg_domain.hpp"
 #include "kzg_evals.hpp"
 
-#define PTRY_E(expr) do { int _rc = (expr); if (_rc) return _rc; } while (0)
-#define KZE_FAIL(code, msg) return (plonk::set_last_error(api_fn, msg, __FILE__, __LINE__), code)
-
 namespace plonk {
 
 namespace {
 
-// Fp28 / G1R in memory: each coordinate padded to 16 words (64 B), as the slots of kzg_domain.hip
-struct alignas(16) G1RSlot {
-  Fp28Slot X, Y, ZZ, ZZZ;
-};
-static_assert(sizeof(G1RSlot) == KZD_SLOT_BYTES, "slot size");
 static_assert(sizeof(G1Affine) == KZE_POINT_BYTES, "point size");
-__device__ __forceinline__ Fp28 ld_f28(const Fp28Slot* p) {
-  const uint4* q = reinterpret_cast<const uint4*>(p);
-  const uint4 a = q[0], b = q[1], c = q[2], d = q[3];
-  Fp28 r;
-  r.l[0] = a.x; r.l[1] = a.y; r.l[2] = a.z; r.l[3] = a.w;
-  r.l[4] = b.x; r.l[5] = b.y; r.l[6] = b.z; r.l[7] = b.w;
-  r.l[8] = c.x; r.l[9] = c.y; r.l[10] = c.z; r.l[11] = c.w;
-  r.l[12] = d.x; r.l[13] = d.y;
-  return r;
-}
-__device__ __forceinline__ void st_f28(Fp28Slot* p, const Fp28& v) {
-  uint4* q = reinterpret_cast<uint4*>(p);
-  q[0] = make_uint4(v.l[0], v.l[1], v.l[2], v.l[3]);
-  q[1] = make_uint4(v.l[4], v.l[5], v.l[6], v.l[7]);
-  q[2] = make_uint4(v.l[8], v.l[9], v.l[10], v.l[11]);
-  q[3] = make_uint4(v.l[12], v.l[13], 0u, 0u);
-}
-__device__ __forceinline__ G1R ld_g1r(const G1RSlot* p) {
-  G1R r;
-  r.X = ld_f28(&p->X); r.Y = ld_f28(&p->Y); r.ZZ = ld_f28(&p->ZZ); r.ZZZ = ld_f28(&p->ZZZ);
-  return r;
-}
-__device__ __forceinline__ void st_g1r(G1RSlot* p, const G1R& v) {
-  st_f28(&p->X, v.X); st_f28(&p->Y, v.Y); st_f28(&p->ZZ, v.ZZ); st_f28(&p->ZZZ, v.ZZZ);
-}
-__device__ __forceinline__ Fr ldf(const Fr* p) {
-  const uint4* q = reinterpret_cast<const uint4*>(p);
-  const uint4 a = q[0], b = q[1];
-  Fr r;
-  r.l[0] = a.x; r.l[1] = a.y; r.l[2] = a.z; r.l[3] = a.w;
-  r.l[4] = b.x; r.l[5] = b.y; r.l[6] = b.z; r.l[7] = b.w;
-  return r;
-}
-__device__ __forceinline__ void stf(Fr* p, const Fr& v) {
-  uint4* q = reinterpret_cast<uint4*>(p);
-  q[0] = make_uint4(v.l[0], v.l[1], v.l[2], v.l[3]);
-  q[1] = make_uint4(v.l[4], v.l[5], v.l[6], v.l[7]);
-}
-
-// reduced-radix operands as kernel arguments, as poly.hip passes them: x * R'' ("twiddle form") or the re-sliced R form
-struct Tw {
-  uint32_t w[9];
-};
-__device__ __forceinline__ Fr29 tw29(const Tw& t) {
-  Fr29 r;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) r.l[i] = t.w[i];
-  return r;
-}
-Tw tw_of(const Fr& x) {   // host: x (R form) -> x * R''
-  const Fr29 t = Fr29::twiddle_from_fr(x);
-  Tw r;
-  for (int i = 0; i < 9; ++i) r.w[i] = t.l[i];
-  return r;
-}
-Tw tw_plain(const Fr& x) {   // host: the re-sliced R-form value
-  const Fr29 t = Fr29::from_fr(x);
-  Tw r;
-  for (int i = 0; i < 9; ++i) r.w[i] = t.l[i];
-  return r;
-}
-__device__ __forceinline__ Fr29 ld_slot(const void* base, uint64_t idx) {
-  const uint4* q = reinterpret_cast<const uint4*>(reinterpret_cast<const Fr29Slot*>(base) + idx);
-  const uint4 a = q[0], b = q[1];
-  const uint32_t c = reinterpret_cast<const Fr29Slot*>(base)[idx].w[8];
-  Fr29 r;
-  r.l[0] = a.x; r.l[1] = a.y; r.l[2] = a.z; r.l[3] = a.w;
-  r.l[4] = b.x; r.l[5] = b.y; r.l[6] = b.z; r.l[7] = b.w;
-  r.l[8] = c;
-  return r;
-}
 
 constexpr uint32_t KZE_POINT_LANES = 64;   // one wave per workgroup in the point kernels, as kzg_domain.hip
-
-Fr kze_root(uint32_t log_size) {   // the generator of the size-2^log_size domain, as ntt.hip derives it
-  Fr w = fr_root_of_unity();
-  for (uint32_t i = log_size; i < 32; ++i) w = w.sqr();
-  return w;
-}
 
 }  // namespace
 
@@ -162,7 +77,7 @@ __global__ void __launch_bounds__(256) kze_scan_kernel(const Fr* const* __restri
   const Fr* p = vecs[blockIdx.y];
   unsigned long long bad = 0;
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-    const Fr x = ldf(p + i);
+    const Fr x = ld_fr(p + i);
     bool lt = false;
     for (int k = 7; k >= 0; --k)
       if (x.l[k] != FrP::MOD[k]) { lt = x.l[k] < FrP::MOD[k]; break; }
@@ -175,7 +90,7 @@ __global__ void __launch_bounds__(256) kze_denoms_kernel(Fr w, Fr z, uint64_t n,
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const Fr d = w.pow_u64(i) - z;
-  stf(den + i, d);
+  st_fr(den + i, d);
   if (d.is_zero()) meta->m = i;   // at most one lane: the w^i are distinct
 }
 
@@ -198,7 +113,7 @@ __global__ void __launch_bounds__(KZE_FOLD_T) kze_fold_kernel(KzeFoldArgs a, Tw 
   } else {   // (1 + z d_i) in data form, then into twiddle form
     const Fr29 zt = tw29(zt_), conv = tw29(conv_), one = tw29(one_plain);
 #define KZE_WEIGHT(k) \
-  if (i##k < a.n) u##k = Fr29::mul(Fr29::add_csub(Fr29::mul(Fr29::from_fr(ldf(a.inv + i##k)), zt), one), conv);
+  if (i##k < a.n) u##k = Fr29::mul(Fr29::add_csub(Fr29::mul(Fr29::from_fr(ld_fr(a.inv + i##k)), zt), one), conv);
     KZE_WEIGHT(0) KZE_WEIGHT(1) KZE_WEIGHT(2) KZE_WEIGHT(3)
 #undef KZE_WEIGHT
   }
@@ -208,7 +123,7 @@ __global__ void __launch_bounds__(KZE_FOLD_T) kze_fold_kernel(KzeFoldArgs a, Tw 
     Fr29 h = Fr29::zero();
 #define KZE_STEP(k)                                   \
   if (i##k < a.n) {                                   \
-    const Fr29 e = Fr29::from_fr(ldf(p + i##k));      \
+    const Fr29 e = Fr29::from_fr(ld_fr(p + i##k));    \
     f##k = Fr29::add_csub(f##k, Fr29::mul(e, vt));    \
     h = Fr29::add_csub(h, Fr29::mul(e, u##k));        \
   }
@@ -221,13 +136,13 @@ __global__ void __launch_bounds__(KZE_FOLD_T) kze_fold_kernel(KzeFoldArgs a, Tw 
       for (int w = 0; w < 9; ++w) o.l[w] = __shfl_down(h.l[w], off, 64);
       h = Fr29::add_csub(h, o);
     }
-    if (!lane) stf(a.partial + (uint64_t)j * nwaves + wave, h.to_fr());
+    if (!lane) st_fr(a.partial + (uint64_t)j * nwaves + wave, h.to_fr());
   }
 #define KZE_STORE(k)                                                                  \
   if (i##k < a.n) {                                                                   \
     Fr29 r = f##k;                                                                    \
-    if (a.accumulate) r = Fr29::add_csub(r, Fr29::from_fr(ldf(a.fold + i##k)));       \
-    stf(a.fold + i##k, r.to_fr());                                                    \
+    if (a.accumulate) r = Fr29::add_csub(r, Fr29::from_fr(ld_fr(a.fold + i##k)));     \
+    st_fr(a.fold + i##k, r.to_fr());                                                  \
   }
   KZE_STORE(0) KZE_STORE(1) KZE_STORE(2) KZE_STORE(3)
 #undef KZE_STORE
@@ -237,14 +152,14 @@ __global__ void __launch_bounds__(256) kze_final_kernel(const Fr* __restrict__ p
   __shared__ Fr sh[256];
   const uint32_t t = threadIdx.x;
   Fr acc = Fr::zero();
-  for (uint32_t w = t; w < nwaves; w += 256) acc = acc + ldf(partial + (uint64_t)blockIdx.x * nwaves + w);
+  for (uint32_t w = t; w < nwaves; w += 256) acc = acc + ld_fr(partial + (uint64_t)blockIdx.x * nwaves + w);
   sh[t] = acc;
   __syncthreads();
   for (uint32_t h = 128; h; h >>= 1) {
     if (t < h) sh[t] = sh[t] + sh[t + h];
     __syncthreads();
   }
-  if (!t) stf(evals + blockIdx.x, sh[0] * scale);
+  if (!t) st_fr(evals + blockIdx.x, sh[0] * scale);
 }
 
 // in_domain: lane m has inv == 0, so its q is 0 for now and contributes nothing to the sum
@@ -255,8 +170,8 @@ __global__ void __launch_bounds__(KZE_Q_T) kze_quotient_kernel(const Fr* __restr
   const uint64_t i = (uint64_t)blockIdx.x * KZE_Q_T + t;
   Fr v = Fr::zero();
   if (i < n) {
-    v = (ldf(fold + i) - Y) * ldf(inv + i);
-    stf(q + i, v);
+    v = (ld_fr(fold + i) - Y) * ld_fr(inv + i);
+    st_fr(q + i, v);
   }
   if (!in_domain) return;   // (uniform over the grid)
   sh[t] = i < n ? v * w.pow_u64(i) : Fr::zero();
@@ -265,21 +180,21 @@ __global__ void __launch_bounds__(KZE_Q_T) kze_quotient_kernel(const Fr* __restr
     if (t < h) sh[t] = sh[t] + sh[t + h];
     __syncthreads();
   }
-  if (!t) stf(qpart + blockIdx.x, sh[0]);
+  if (!t) st_fr(qpart + blockIdx.x, sh[0]);
 }
 __global__ void __launch_bounds__(256) kze_qfix_kernel(const Fr* __restrict__ qpart, uint32_t nblocks, Fr neg_w_inv_m, uint64_t m,
                                                        Fr* __restrict__ q) {
   __shared__ Fr sh[256];
   const uint32_t t = threadIdx.x;
   Fr acc = Fr::zero();
-  for (uint32_t b = t; b < nblocks; b += 256) acc = acc + ldf(qpart + b);
+  for (uint32_t b = t; b < nblocks; b += 256) acc = acc + ld_fr(qpart + b);
   sh[t] = acc;
   __syncthreads();
   for (uint32_t h = 128; h; h >>= 1) {
     if (t < h) sh[t] = sh[t] + sh[t + h];
     __syncthreads();
   }
-  if (!t) stf(q + m, sh[0] * neg_w_inv_m);
+  if (!t) st_fr(q + m, sh[0] * neg_w_inv_m);
 }
 
 // ---- launchers (kzg_evals.hpp) -----------------------------------------------------------------------------------------------
@@ -313,7 +228,7 @@ int kze_scan(Ctx* c, const Fr* const* vecs, uint32_t first, uint32_t cnt, uint64
 
 int kze_denominators(Ctx* c, uint32_t log_n, const Fr& z, Fr* den, KzeMeta* meta) {
   const uint64_t n = 1ull << log_n;
-  hipLaunchKernelGGL(kze_denoms_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, c->stream, kze_root(log_n), z, n, den, meta);
+  hipLaunchKernelGGL(kze_denoms_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, c->stream, fr_domain_root(log_n), z, n, den, meta);
   HIP_TRY(hipGetLastError());
   return PLONK_OK;
 }
@@ -332,7 +247,7 @@ int kze_fold_eval(Ctx* c, const KzeFoldArgs& a, Fr* evals) {
 int kze_quotient(Ctx* c, uint32_t log_n, const Fr* fold, const Fr* inv, const Fr& Y, uint64_t m, Fr* q, Fr* qpart) {
   const uint64_t n = 1ull << log_n;
   if (m != KZE_NONE && m >= n) return (set_last_error("invalid argument", __func__, __FILE__, __LINE__), PLONK_ERR_ARG);
-  const Fr w = kze_root(log_n);
+  const Fr w = fr_domain_root(log_n);
   const uint32_t blocks = kze_quotient_blocks(n);
   hipLaunchKernelGGL(kze_quotient_kernel, dim3(blocks), dim3(KZE_Q_T), 0, c->stream, fold, inv, Y, n, w, m != KZE_NONE ? 1 : 0, q, qpart);
   if (m != KZE_NONE)
@@ -344,38 +259,19 @@ int kze_quotient(Ctx* c, uint32_t log_n, const Fr* fold, const Fr* inv, const Fr
 // ---- the state a handle holds for these calls ------------------------------------------------------------------------------
 namespace {
 
-struct KzgEvals {
+struct KzeBufs {
   enum { DEN, FOLD, Q, PARTIAL, EVALS, VPOW, VECS, META, QPART, NBUF };   // grow-only
-  void* p[NBUF] = {};
-  uint64_t cap[NBUF] = {};
+};
+struct KzgEvals : KzeBufs, DevBufs<KzeBufs::NBUF> {
   G1Affine* lag = nullptr;      // [L_i(tau)] G, i < n
   uint64_t lag_bytes = 0;
   plonk_kzg_evals_info last = {};
-  ~KzgEvals() {
-    (void)hipFree(lag);
-    for (int i = 0; i < NBUF; ++i) (void)hipFree(p[i]);
-  }
-  int need(int i, uint64_t bytes) {
-    if (bytes <= cap[i]) return PLONK_OK;
-    (void)hipFree(p[i]);
-    p[i] = nullptr;
-    cap[i] = 0;
-    HIP_TRY(hipMalloc(&p[i], bytes));
-    cap[i] = bytes;
-    return PLONK_OK;
-  }
-  template <class T>
-  T* at(int i) const { return (T*)p[i]; }
+  ~KzgEvals() { (void)hipFree(lag); }
 };
 
 KzgEvals* kze_state(const KzdView& v) {
   if (!*v.evals) *v.evals = new KzgEvals();
   return (KzgEvals*)*v.evals;
-}
-
-void identity48(uint8_t out[48]) {
-  memset(out, 0, 48);
-  out[0] = 0xC0;
 }
 
 // the points, built by the first call that commits
@@ -407,7 +303,7 @@ int commit_values(Ctx* c, const KzgEvals* e, const Fr* s, uint64_t n, uint8_t ou
   const int rc = msm_points_run(c, in, n, nullptr, &sum);
   c->last_points = keep;
   c->last_points_valid = keep_valid;
-  PTRY_E(rc);
+  PTRY(rc);
   uint8_t aff[1][97];
   batch_xyzz_to_affine97(&sum, 1, aff);
   g1_compress97(aff[0], out48);
@@ -426,13 +322,13 @@ int for_groups(Ctx* c, const void* const* vecs, uint64_t count, uint64_t n, bool
     for (uint64_t first = 0; first < count; first += per) {
       const uint32_t cnt = (uint32_t)(count - first < per ? count - first : per);
       for (uint32_t k = 0; k < cnt; ++k) ptrs[k] = (const Fr*)vecs[first + k];
-      PTRY_E(fn((uint32_t)first, cnt, ptrs.data()));
+      PTRY(fn((uint32_t)first, cnt, ptrs.data()));
     }
     return PLONK_OK;
   }
   Fr* stage[2];
   hipEvent_t up[2], done[2];
-  PTRY_E(kzg_stage_reserve(c, plan.stage_values, stage, up, done));
+  PTRY(kzg_stage_reserve(c, plan.stage_values, stage, up, done));
   HIP_TRY(hipStreamSynchronize(c->stream));   // the copy stream is not ordered behind what the main stream still runs
   uint64_t g = 0;
   for (uint64_t first = 0; first < count; first += per, ++g) {
@@ -445,7 +341,7 @@ int for_groups(Ctx* c, const void* const* vecs, uint64_t count, uint64_t n, bool
     }
     HIP_TRY(hipEventRecord(up[b], c->copy_stream));
     HIP_TRY(hipStreamWaitEvent(c->stream, up[b], 0));
-    PTRY_E(fn((uint32_t)first, cnt, ptrs.data()));
+    PTRY(fn((uint32_t)first, cnt, ptrs.data()));
     HIP_TRY(hipEventRecord(done[b], c->stream));
   }
   return PLONK_OK;
@@ -475,32 +371,32 @@ int evals_body(const char* api_fn, const KzdView& dv, KzgEvals* e, const EvalsCa
   info.msm_launches = plan.msm_launches;
   info.msm_terms = plan.msm_terms;
   // ---- checks that need the device: canonical values of the resident form, the lane m ----
-  PTRY_E(e->need(KzgEvals::META, sizeof(KzeMeta)));
-  PTRY_E(e->need(KzgEvals::VECS, sizeof(Fr*) * count));
-  if (a.open) PTRY_E(e->need(KzgEvals::DEN, sizeof(Fr) * n));
+  PTRY(e->need(KzgEvals::META, sizeof(KzeMeta)));
+  PTRY(e->need(KzgEvals::VECS, sizeof(Fr*) * count));
+  if (a.open) PTRY(e->need(KzgEvals::DEN, sizeof(Fr) * n));
   KzeMeta mh = {KZE_NONE, 0};
   if (a.resident || in_domain) {
     HIP_TRY(hipMemcpyAsync(e->p[KzgEvals::META], &mh, sizeof mh, hipMemcpyHostToDevice, c.stream));
     if (a.resident) {
       HIP_TRY(hipMemcpyAsync(e->p[KzgEvals::VECS], a.vecs, sizeof(Fr*) * count, hipMemcpyHostToDevice, c.stream));
       for (uint64_t first = 0; first < count; first += 32768)   // grid.y
-        PTRY_E(kze_scan(&c, e->at<const Fr*>(KzgEvals::VECS), (uint32_t)first, (uint32_t)(count - first < 32768 ? count - first : 32768), n,
+        PTRY(kze_scan(&c, e->at<const Fr*>(KzgEvals::VECS), (uint32_t)first, (uint32_t)(count - first < 32768 ? count - first : 32768), n,
                         e->at<KzeMeta>(KzgEvals::META)));
     }
-    if (a.open) PTRY_E(kze_denominators(&c, L, a.z, e->at<Fr>(KzgEvals::DEN), e->at<KzeMeta>(KzgEvals::META)));
+    if (a.open) PTRY(kze_denominators(&c, L, a.z, e->at<Fr>(KzgEvals::DEN), e->at<KzeMeta>(KzgEvals::META)));
     HIP_TRY(hipMemcpyAsync(&mh, e->p[KzgEvals::META], sizeof mh, hipMemcpyDeviceToHost, c.stream));
     HIP_TRY(hipStreamSynchronize(c.stream));
-    if (mh.bad) KZE_FAIL(PLONK_ERR_DATA, "a value is not a canonical residue");
-    if (in_domain != (mh.m != KZE_NONE) || (in_domain && mh.m >= n)) KZE_FAIL(PLONK_ERR_STATE, "the device and the host disagree on whether the point lies in the domain");
+    if (mh.bad) API_FAIL(PLONK_ERR_DATA, "a value is not a canonical residue");
+    if (in_domain != (mh.m != KZE_NONE) || (in_domain && mh.m >= n)) API_FAIL(PLONK_ERR_STATE, "the device and the host disagree on whether the point lies in the domain");
   } else if (a.open) {
-    PTRY_E(kze_denominators(&c, L, a.z, e->at<Fr>(KzgEvals::DEN), e->at<KzeMeta>(KzgEvals::META)));
+    PTRY(kze_denominators(&c, L, a.z, e->at<Fr>(KzgEvals::DEN), e->at<KzeMeta>(KzgEvals::META)));
   }
   info.in_domain_index = mh.m;
   // ---- from here on the call writes ----
-  if (plan.msm_launches) PTRY_E(lagrange_ready(dv, e, &info.built_points));
+  if (plan.msm_launches) PTRY(lagrange_ready(dv, e, &info.built_points));
   if (!a.open) {
-    PTRY_E(for_groups(&c, a.vecs, count, n, a.resident, plan, [&](uint32_t first, uint32_t cnt, const Fr* const* ptrs) -> int {
-      for (uint32_t k = 0; k < cnt; ++k) PTRY_E(commit_values(&c, e, ptrs[k], n, a.commitments48 + 48ull * (first + k)));
+    PTRY(for_groups(&c, a.vecs, count, n, a.resident, plan, [&](uint32_t first, uint32_t cnt, const Fr* const* ptrs) -> int {
+      for (uint32_t k = 0; k < cnt; ++k) PTRY(commit_values(&c, e, ptrs[k], n, a.commitments48 + 48ull * (first + k)));
       return PLONK_OK;
     }));
     info.lagrange_bytes = e->lag_bytes;
@@ -508,12 +404,12 @@ int evals_body(const char* api_fn, const KzdView& dv, KzgEvals* e, const EvalsCa
     return PLONK_OK;
   }
   const uint32_t nwaves = kze_fold_waves(n);
-  PTRY_E(e->need(KzgEvals::FOLD, sizeof(Fr) * n));
-  PTRY_E(e->need(KzgEvals::PARTIAL, sizeof(Fr) * KZE_GROUP * nwaves));
-  PTRY_E(e->need(KzgEvals::EVALS, sizeof(Fr) * count));
-  PTRY_E(e->need(KzgEvals::VPOW, sizeof(Fr29Slot) * count));
-  PTRY_E(poly_batch_inverse(&c, e->at<Fr>(KzgEvals::DEN), n));
-  PTRY_E(poly_kzg_powers(&c, e->p[KzgEvals::VPOW], (uint32_t)count, a.v));
+  PTRY(e->need(KzgEvals::FOLD, sizeof(Fr) * n));
+  PTRY(e->need(KzgEvals::PARTIAL, sizeof(Fr) * KZE_GROUP * nwaves));
+  PTRY(e->need(KzgEvals::EVALS, sizeof(Fr) * count));
+  PTRY(e->need(KzgEvals::VPOW, sizeof(Fr29Slot) * count));
+  PTRY(poly_batch_inverse(&c, e->at<Fr>(KzgEvals::DEN), n));
+  PTRY(poly_kzg_powers(&c, e->p[KzgEvals::VPOW], (uint32_t)count, a.v));
   KzeFoldArgs fa;
   fa.vecs = e->at<const Fr*>(KzgEvals::VECS);
   fa.vpow = e->p[KzgEvals::VPOW];
@@ -525,7 +421,7 @@ int evals_body(const char* api_fn, const KzdView& dv, KzgEvals* e, const EvalsCa
   fa.z = a.z;
   fa.scale = kze_eval_scale(a.z, L);
   std::vector<const Fr*> staged(a.resident ? 0 : count);   // the host form's device addresses, alive until the call's last copy has run
-  PTRY_E(for_groups(&c, a.vecs, count, n, a.resident, plan, [&](uint32_t first, uint32_t cnt, const Fr* const* ptrs) -> int {
+  PTRY(for_groups(&c, a.vecs, count, n, a.resident, plan, [&](uint32_t first, uint32_t cnt, const Fr* const* ptrs) -> int {
     if (!a.resident) {
       for (uint32_t k = 0; k < cnt; ++k) staged[first + k] = ptrs[k];
       HIP_TRY(hipMemcpyAsync(e->at<const Fr*>(KzgEvals::VECS) + first, staged.data() + first, sizeof(Fr*) * cnt, hipMemcpyHostToDevice, c.stream));
@@ -533,9 +429,9 @@ int evals_body(const char* api_fn, const KzdView& dv, KzgEvals* e, const EvalsCa
     fa.first = first;
     fa.count = cnt;
     fa.accumulate = first ? 1 : 0;
-    PTRY_E(kze_fold_eval(&c, fa, e->at<Fr>(KzgEvals::EVALS) + first));
+    PTRY(kze_fold_eval(&c, fa, e->at<Fr>(KzgEvals::EVALS) + first));
     if (a.commitments48)
-      for (uint32_t k = 0; k < cnt; ++k) PTRY_E(commit_values(&c, e, ptrs[k], n, a.commitments48 + 48ull * (first + k)));
+      for (uint32_t k = 0; k < cnt; ++k) PTRY(commit_values(&c, e, ptrs[k], n, a.commitments48 + 48ull * (first + k)));
     return PLONK_OK;
   }));
   std::vector<Fr> y(count);
@@ -547,10 +443,10 @@ int evals_body(const char* api_fn, const KzdView& dv, KzgEvals* e, const EvalsCa
       Y = Y + vp * y[j];
       vp = vp * a.v;
     }
-    PTRY_E(e->need(KzgEvals::Q, sizeof(Fr) * n));
-    PTRY_E(e->need(KzgEvals::QPART, sizeof(Fr) * kze_quotient_blocks(n)));
-    PTRY_E(kze_quotient(&c, L, e->at<Fr>(KzgEvals::FOLD), e->at<Fr>(KzgEvals::DEN), Y, mh.m, e->at<Fr>(KzgEvals::Q), e->at<Fr>(KzgEvals::QPART)));
-    PTRY_E(commit_values(&c, e, e->at<Fr>(KzgEvals::Q), n, a.witness48));
+    PTRY(e->need(KzgEvals::Q, sizeof(Fr) * n));
+    PTRY(e->need(KzgEvals::QPART, sizeof(Fr) * kze_quotient_blocks(n)));
+    PTRY(kze_quotient(&c, L, e->at<Fr>(KzgEvals::FOLD), e->at<Fr>(KzgEvals::DEN), Y, mh.m, e->at<Fr>(KzgEvals::Q), e->at<Fr>(KzgEvals::QPART)));
+    PTRY(commit_values(&c, e, e->at<Fr>(KzgEvals::Q), n, a.witness48));
   }
   memcpy(a.evaluations, y.data(), sizeof(Fr) * count);
   info.lagrange_bytes = e->lag_bytes;
@@ -562,23 +458,23 @@ int evals_impl(const char* api_fn, plonk_kzg_domain* dom, const void* const* vec
                const uint64_t* point, const uint64_t* v_challenge, uint64_t* evaluations, uint8_t* commitments48, uint8_t* witness48) {
   const int arg = open ? kze_check_open(dom != nullptr, vecs != nullptr, point != nullptr, v_challenge != nullptr, evaluations != nullptr, count)
                        : kze_check_commit(dom != nullptr, vecs != nullptr, commitments48 != nullptr, count);
-  if (arg != PLONK_OK) KZE_FAIL(PLONK_ERR_ARG, count > KZE_MAX_COUNT ? "invalid argument: at most 65536 vectors per call"
+  if (arg != PLONK_OK) API_FAIL(PLONK_ERR_ARG, count > KZE_MAX_COUNT ? "invalid argument: at most 65536 vectors per call"
                                                                       : "invalid argument: a required pointer is NULL");
   for (uint64_t i = 0; i < count; ++i)
-    if (!vecs[i]) KZE_FAIL(PLONK_ERR_ARG, "invalid argument: evals[i] is NULL");
+    if (!vecs[i]) API_FAIL(PLONK_ERR_ARG, "invalid argument: evals[i] is NULL");
   EvalsCall a = {vecs, count, resident, open, Fr::zero(), Fr::one(), evaluations, commitments48, witness48};
-  if (open && (!kzg_fr_load(point, &a.z) || (v_challenge && !kzg_fr_load(v_challenge, &a.v)))) KZE_FAIL(PLONK_ERR_DATA, "non-canonical scalar");
+  if (open && (!kzg_fr_load(point, &a.z) || (v_challenge && !kzg_fr_load(v_challenge, &a.v)))) API_FAIL(PLONK_ERR_DATA, "non-canonical scalar");
   const KzdView dv = kzd_view(dom);
   Ctx& c = *dv.c;
   CTX_ENTER(c, api_fn);
   HIP_TRY(hipSetDevice(c.device));
-  if (!dv.key_current) KZE_FAIL(PLONK_ERR_STATE, "the domain is bound to a commit key that was replaced on its context");
-  if (c.nccl_comm) KZE_FAIL(PLONK_ERR_STATE, "a context with a communicator holds only a range of the commit key");
+  if (!dv.key_current) API_FAIL(PLONK_ERR_STATE, "the domain is bound to a commit key that was replaced on its context");
+  if (c.nccl_comm) API_FAIL(PLONK_ERR_STATE, "a context with a communicator holds only a range of the commit key");
   if (!resident) {   // before anything is queued or written
     Fr t;
     for (uint64_t i = 0; i < count; ++i)
       for (uint64_t k = 0; k < (1ull << dv.log_n); ++k)
-        if (!kzg_fr_load((const uint64_t*)vecs[i] + 4 * k, &t)) KZE_FAIL(PLONK_ERR_DATA, "a value is not a canonical residue");
+        if (!kzg_fr_load((const uint64_t*)vecs[i] + 4 * k, &t)) API_FAIL(PLONK_ERR_DATA, "a value is not a canonical residue");
   }
   KzgEvals* e = kze_state(dv);
   if (!count) {
@@ -643,11 +539,11 @@ int plonk_kzg_open_evals_dev(plonk_kzg_domain* dom, const void* const* evals_dev
 int plonk_kzg_evals_last(plonk_kzg_domain* dom, plonk_kzg_evals_info* out) {
   const char* const api_fn = __func__;
   return plonk::api_guard(api_fn, [&]() -> int {
-  if (!dom || !out) KZE_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
+  if (!dom || !out) API_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
   const KzdView dv = kzd_view(dom);
   Ctx& c = *dv.c;
   CTX_ENTER(c, api_fn);
-  if (!dv.key_current) KZE_FAIL(PLONK_ERR_STATE, "the domain is bound to a commit key that was replaced on its context");
+  if (!dv.key_current) API_FAIL(PLONK_ERR_STATE, "the domain is bound to a commit key that was replaced on its context");
   const KzgEvals* e = (const KzgEvals*)*dv.evals;
   plonk_kzg_evals_info info = {};
   info.log_n = dv.log_n;

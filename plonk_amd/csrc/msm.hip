@@ -30,90 +30,13 @@
 
 #include "plonk_internal.hpp"
 #include "curve28.cuh"
-#include "fr29.cuh"
+#include "devmem.cuh"
 
 namespace plonk {
 
 
 static constexpr uint32_t MSM_KSL = 32;   // entries per slice from 2^18 terms on (msm_ksl: shorter slices, 3-6 per bucket, for smaller m)
 static constexpr uint32_t MSM_CHUNK = 16; // buckets per chunk in the weighted reduction
-
-__device__ __forceinline__ Fr ld_fr_g(const Fr* p) {
-  const uint4* q = reinterpret_cast<const uint4*>(p);
-  uint4 a = q[0], b = q[1];
-  Fr r;
-  r.l[0] = a.x; r.l[1] = a.y; r.l[2] = a.z; r.l[3] = a.w;
-  r.l[4] = b.x; r.l[5] = b.y; r.l[6] = b.z; r.l[7] = b.w;
-  return r;
-}
-__device__ __forceinline__ Fp ld_fp(const Fp* p) {
-  const uint4* q = reinterpret_cast<const uint4*>(p);
-  uint4 a = q[0], b = q[1], c = q[2];
-  Fp r;
-  r.l[0] = a.x; r.l[1] = a.y; r.l[2] = a.z; r.l[3] = a.w;
-  r.l[4] = b.x; r.l[5] = b.y; r.l[6] = b.z; r.l[7] = b.w;
-  r.l[8] = c.x; r.l[9] = c.y; r.l[10] = c.z; r.l[11] = c.w;
-  return r;
-}
-__device__ __forceinline__ void st_fp(Fp* p, const Fp& v) {
-  uint4* q = reinterpret_cast<uint4*>(p);
-  q[0] = make_uint4(v.l[0], v.l[1], v.l[2], v.l[3]);
-  q[1] = make_uint4(v.l[4], v.l[5], v.l[6], v.l[7]);
-  q[2] = make_uint4(v.l[8], v.l[9], v.l[10], v.l[11]);
-}
-__device__ __forceinline__ G1Affine ld_aff(const G1Affine* p) {
-  G1Affine a;
-  a.x = ld_fp(&p->x);
-  a.y = ld_fp(&p->y);
-  return a;
-}
-__device__ __forceinline__ void st_aff(G1Affine* p, const G1Affine& a) {
-  st_fp(&p->x, a.x);
-  st_fp(&p->y, a.y);
-}
-__device__ __forceinline__ G1 ld_g1(const G1* p) {
-  G1 r;
-  r.X = ld_fp(&p->X); r.Y = ld_fp(&p->Y); r.ZZ = ld_fp(&p->ZZ); r.ZZZ = ld_fp(&p->ZZZ);
-  return r;
-}
-__device__ __forceinline__ void st_g1(G1* p, const G1& v) {
-  st_fp(&p->X, v.X); st_fp(&p->Y, v.Y); st_fp(&p->ZZ, v.ZZ); st_fp(&p->ZZZ, v.ZZZ);
-}
-
-// ---- Fp28 / G1R in memory: each coordinate padded to 16 words (64 B) ------------------
-struct alignas(16) G1RSlot {
-  Fp28Slot X, Y, ZZ, ZZZ;
-};
-__device__ __forceinline__ Fp28 ld_f28(const Fp28Slot* p) {
-  const uint4* q = reinterpret_cast<const uint4*>(p);
-  const uint4 a = q[0], b = q[1], c = q[2], d = q[3];
-  Fp28 r;
-  r.l[0] = a.x; r.l[1] = a.y; r.l[2] = a.z; r.l[3] = a.w;
-  r.l[4] = b.x; r.l[5] = b.y; r.l[6] = b.z; r.l[7] = b.w;
-  r.l[8] = c.x; r.l[9] = c.y; r.l[10] = c.z; r.l[11] = c.w;
-  r.l[12] = d.x; r.l[13] = d.y;
-  return r;
-}
-__device__ __forceinline__ void st_f28(Fp28Slot* p, const Fp28& v) {
-  uint4* q = reinterpret_cast<uint4*>(p);
-  q[0] = make_uint4(v.l[0], v.l[1], v.l[2], v.l[3]);
-  q[1] = make_uint4(v.l[4], v.l[5], v.l[6], v.l[7]);
-  q[2] = make_uint4(v.l[8], v.l[9], v.l[10], v.l[11]);
-  q[3] = make_uint4(v.l[12], v.l[13], 0u, 0u);
-}
-__device__ __forceinline__ G1R ld_g1r(const G1RSlot* p) {
-  G1R r;
-  r.X = ld_f28(&p->X); r.Y = ld_f28(&p->Y); r.ZZ = ld_f28(&p->ZZ); r.ZZZ = ld_f28(&p->ZZZ);
-  return r;
-}
-__device__ __forceinline__ void st_g1r(G1RSlot* p, const G1R& v) {
-  st_f28(&p->X, v.X); st_f28(&p->Y, v.Y); st_f28(&p->ZZ, v.ZZ); st_f28(&p->ZZZ, v.ZZZ);
-}
-__device__ __forceinline__ G1R g1r_neg(const G1R& p) {   // -P: Y -> 16p - Y (Y < 8p), canonicalised
-  G1R r = p;
-  if (!p.is_identity()) r.Y = Fp28::sub<16>(Fp28::zero(), p.Y).canon();
-  return r;
-}
 
 #if PLONK_MSM_NB_BITS == 15   // ---- shared code: compiled once (the 2^15-bucket build of this file) ----
 // ---------------------------------------------------------------------------
@@ -1130,9 +1053,7 @@ int lagrange_points_device(Ctx* c, uint32_t L, G1Affine* out_dev) {
   G1RSlot* v = nullptr;
   HIP_TRY(hipMalloc((void**)&v, sizeof(G1RSlot) * n));
   hipLaunchKernelGGL(ecfft_load_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, row0, v, n);
-  Fr w = fr_root_of_unity();
-  for (uint32_t i = L; i < 32; ++i) w = w.sqr();
-  const Fr w_inv = w.inv();
+  const Fr w_inv = fr_domain_root(L).inv();
   for (uint64_t half = n / 2; half >= 1; half >>= 1)
     hipLaunchKernelGGL(ecfft_stage_kernel, dim3((uint32_t)((n / 2 + 63) / 64)), dim3(64), 0, st, v, n, half, w_inv);
   const Fr n_inv = Fr::from_u64(n).inv().from_mont();

@@ -27,11 +27,10 @@
 #include "plonk_internal.hpp"
 #include "api_guard.hpp"
 #include "curve28.cuh"
+#include "devmem.cuh"
 #include "g1codec.cuh"
 #include "hostg1.hpp"
 #include "msm_points_core.hpp"
-
-#define PTRY_P(expr) do { int _rc = (expr); if (_rc) return _rc; } while (0)
 
 namespace plonk {
 
@@ -39,36 +38,6 @@ void prof_begin(Ctx* c, int slot);   // capi.hip
 void prof_end(Ctx* c, int slot);
 
 namespace {
-
-// Fp28 / G1R in memory: each coordinate padded to 16 words (64 B), as the commit-key tables of msm.hip
-struct alignas(16) G1RSlot {
-  Fp28Slot X, Y, ZZ, ZZZ;
-};
-__device__ __forceinline__ Fp28 ld_f28(const Fp28Slot* p) {
-  const uint4* q = reinterpret_cast<const uint4*>(p);
-  const uint4 a = q[0], b = q[1], c = q[2], d = q[3];
-  Fp28 r;
-  r.l[0] = a.x; r.l[1] = a.y; r.l[2] = a.z; r.l[3] = a.w;
-  r.l[4] = b.x; r.l[5] = b.y; r.l[6] = b.z; r.l[7] = b.w;
-  r.l[8] = c.x; r.l[9] = c.y; r.l[10] = c.z; r.l[11] = c.w;
-  r.l[12] = d.x; r.l[13] = d.y;
-  return r;
-}
-__device__ __forceinline__ void st_f28(Fp28Slot* p, const Fp28& v) {
-  uint4* q = reinterpret_cast<uint4*>(p);
-  q[0] = make_uint4(v.l[0], v.l[1], v.l[2], v.l[3]);
-  q[1] = make_uint4(v.l[4], v.l[5], v.l[6], v.l[7]);
-  q[2] = make_uint4(v.l[8], v.l[9], v.l[10], v.l[11]);
-  q[3] = make_uint4(v.l[12], v.l[13], 0u, 0u);
-}
-__device__ __forceinline__ G1R ld_g1r(const G1RSlot* p) {
-  G1R r;
-  r.X = ld_f28(&p->X); r.Y = ld_f28(&p->Y); r.ZZ = ld_f28(&p->ZZ); r.ZZZ = ld_f28(&p->ZZZ);
-  return r;
-}
-__device__ __forceinline__ void st_g1r(G1RSlot* p, const G1R& v) {
-  st_f28(&p->X, v.X); st_f28(&p->Y, v.Y); st_f28(&p->ZZ, v.ZZ); st_f28(&p->ZZZ, v.ZZZ);
-}
 
 constexpr uint32_t MP_BAD_DECODE = 1, MP_BAD_CHECK = 2;
 struct MpMeta {            // what the host reads back after the scan
@@ -370,27 +339,12 @@ __global__ void __launch_bounds__(64) mp_wsum_kernel(const G1RSlot* __restrict__
 // ---- host side --------------------------------------------------------------------------------------------------------
 namespace {
 
-struct MpWork {   // the context's grow-only workspace (Ctx::points_ws)
+struct MpBufs {
   enum { POINTS, SCALARS, AFF, AFF_FP, KIND, GLV, COUNTS, OFF, CUR, SLICE_OFF, ENTRIES, PARTIAL, BUCKETS, HEAVY, CHUNK, WSUM,
          META, SC, IDS, PART, NBUF };
-  void* p[NBUF] = {};
-  uint64_t cap[NBUF] = {};
-  ~MpWork() {
-    for (int i = 0; i < NBUF; ++i) (void)hipFree(p[i]);
-  }
-  int need(int i, uint64_t bytes) {
-    if (!bytes) bytes = 16;
-    if (bytes <= cap[i]) return PLONK_OK;
-    (void)hipFree(p[i]);
-    p[i] = nullptr;
-    cap[i] = 0;
-    HIP_TRY(hipMalloc(&p[i], bytes));
-    cap[i] = bytes;
-    return PLONK_OK;
-  }
-  template <class T>
-  T* at(int i) const { return (T*)p[i]; }
 };
+// the context's grow-only workspace (Ctx::points_ws); a request for 0 bytes allocates 16
+struct MpWork : MpBufs, DevBufs<MpBufs::NBUF, 16> {};
 
 MpWork& mp_work(Ctx* c) {
   if (!c->points_ws) c->points_ws = new MpWork();
@@ -422,17 +376,17 @@ inline dim3 term_grid(uint64_t m) { return dim3((uint32_t)((m + MP_TERM_LANES - 
 int mp_run_per_term(Ctx* c, MpWork& w, const MpInput& in, uint64_t m, G1* sum) {
   const hipStream_t st = c->stream;
   H1 sums[2];
-  PTRY_P(w.need(MpWork::PART, sizeof(G1) * 2 * VERIFY_MSM_MAX_BLOCKS));
+  PTRY(w.need(MpWork::PART, sizeof(G1) * 2 * VERIFY_MSM_MAX_BLOCKS));
   if (in.sc) {
-    PTRY_P(msm_run(c, in.sc, in.ids, m, 0, in.pts, in.kind, w.at<G1>(MpWork::PART), sums));
+    PTRY(msm_run(c, in.sc, in.ids, m, 0, in.pts, in.kind, w.at<G1>(MpWork::PART), sums));
     *sum = g1_of_h1(sums[0]);
     return PLONK_OK;
   }
-  PTRY_P(w.need(MpWork::AFF_FP, sizeof(G1Affine) * m));
-  PTRY_P(w.need(MpWork::KIND, 4 * m));
-  PTRY_P(w.need(MpWork::SC, 32 * m));
-  PTRY_P(w.need(MpWork::IDS, 4 * m));
-  PTRY_P(w.need(MpWork::META, sizeof(MpMeta)));
+  PTRY(w.need(MpWork::AFF_FP, sizeof(G1Affine) * m));
+  PTRY(w.need(MpWork::KIND, 4 * m));
+  PTRY(w.need(MpWork::SC, 32 * m));
+  PTRY(w.need(MpWork::IDS, 4 * m));
+  PTRY(w.need(MpWork::META, sizeof(MpMeta)));
   MpMeta* meta = w.at<MpMeta>(MpWork::META);
   HIP_TRY(hipMemsetAsync(meta, 0, sizeof(MpMeta), st));
   hipLaunchKernelGGL(mp_points_kernel, term_grid(m), dim3(MP_TERM_LANES), 0, st, in, (uint32_t)m, (G1AffineR*)nullptr,
@@ -445,7 +399,7 @@ int mp_run_per_term(Ctx* c, MpWork& w, const MpInput& in, uint64_t m, G1* sum) {
   HIP_TRY(hipMemcpyAsync(&mh, meta, sizeof mh, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   if (mh.bad) return mp_bad_point(mh.bad);
-  PTRY_P(msm_run(c, w.at<uint32_t>(MpWork::SC), w.at<uint32_t>(MpWork::IDS), m, 0, w.at<G1Affine>(MpWork::AFF_FP),
+  PTRY(msm_run(c, w.at<uint32_t>(MpWork::SC), w.at<uint32_t>(MpWork::IDS), m, 0, w.at<G1Affine>(MpWork::AFF_FP),
                  w.at<int32_t>(MpWork::KIND), w.at<G1>(MpWork::PART), sums));
   *sum = g1_of_h1(sums[0]);
   return PLONK_OK;
@@ -454,19 +408,19 @@ int mp_run_per_term(Ctx* c, MpWork& w, const MpInput& in, uint64_t m, G1* sum) {
 int mp_run_buckets(Ctx* c, MpWork& w, const MpInput& in, uint64_t m, const MpPlan& plan, plonk_msm_points_info* info, G1* sum) {
   const hipStream_t st = c->stream;
   const uint32_t cb = plan.c, W = plan.windows, nb = mp_buckets(cb), nbt = W * nb, ksl = plan.slice_entries;
-  PTRY_P(w.need(MpWork::AFF, sizeof(G1AffineR) * m));
-  PTRY_P(w.need(MpWork::KIND, 4 * m));
-  PTRY_P(w.need(MpWork::GLV, sizeof(GlvScalar) * m));
-  PTRY_P(w.need(MpWork::COUNTS, 4ull * nbt));
-  PTRY_P(w.need(MpWork::OFF, 4ull * (nbt + 1)));
-  PTRY_P(w.need(MpWork::CUR, 4ull * nbt));
-  PTRY_P(w.need(MpWork::SLICE_OFF, 4ull * (nbt + 1)));
-  PTRY_P(w.need(MpWork::BUCKETS, sizeof(G1RSlot) * (uint64_t)nbt));
-  PTRY_P(w.need(MpWork::HEAVY, 4ull * nbt));
+  PTRY(w.need(MpWork::AFF, sizeof(G1AffineR) * m));
+  PTRY(w.need(MpWork::KIND, 4 * m));
+  PTRY(w.need(MpWork::GLV, sizeof(GlvScalar) * m));
+  PTRY(w.need(MpWork::COUNTS, 4ull * nbt));
+  PTRY(w.need(MpWork::OFF, 4ull * (nbt + 1)));
+  PTRY(w.need(MpWork::CUR, 4ull * nbt));
+  PTRY(w.need(MpWork::SLICE_OFF, 4ull * (nbt + 1)));
+  PTRY(w.need(MpWork::BUCKETS, sizeof(G1RSlot) * (uint64_t)nbt));
+  PTRY(w.need(MpWork::HEAVY, 4ull * nbt));
   const uint32_t per_window = (nb + MP_WIN_SPAN - 1) / MP_WIN_SPAN;
-  PTRY_P(w.need(MpWork::CHUNK, sizeof(G1RSlot) * (uint64_t)W * per_window));
-  PTRY_P(w.need(MpWork::WSUM, sizeof(G1) * W));
-  PTRY_P(w.need(MpWork::META, sizeof(MpMeta)));
+  PTRY(w.need(MpWork::CHUNK, sizeof(G1RSlot) * (uint64_t)W * per_window));
+  PTRY(w.need(MpWork::WSUM, sizeof(G1) * W));
+  PTRY(w.need(MpWork::META, sizeof(MpMeta)));
   MpMeta* meta = w.at<MpMeta>(MpWork::META);
   uint32_t* counts = w.at<uint32_t>(MpWork::COUNTS);
   uint32_t* off = w.at<uint32_t>(MpWork::OFF);
@@ -499,8 +453,8 @@ int mp_run_buckets(Ctx* c, MpWork& w, const MpInput& in, uint64_t m, const MpPla
     *sum = G1::identity();
     return PLONK_OK;
   }
-  PTRY_P(w.need(MpWork::ENTRIES, 4ull * mh.entries));
-  PTRY_P(w.need(MpWork::PARTIAL, sizeof(G1RSlot) * (uint64_t)mh.slices));
+  PTRY(w.need(MpWork::ENTRIES, 4ull * mh.entries));
+  PTRY(w.need(MpWork::PARTIAL, sizeof(G1RSlot) * (uint64_t)mh.slices));
   hipLaunchKernelGGL(mp_scatter_kernel, term_grid(m), dim3(MP_TERM_LANES), 0, st, w.at<const GlvScalar>(MpWork::GLV), (uint32_t)m, cb,
                      w.at<uint32_t>(MpWork::CUR), w.at<uint32_t>(MpWork::ENTRIES));
   HIP_TRY(hipGetLastError());
@@ -604,7 +558,7 @@ int plonk_msm_points(plonk_ctx* ctx, const uint8_t* points, const uint64_t* scal
                      uint8_t out_xy_inf[97]) {
   const char* const api_fn = __func__;
   return plonk::api_guard(api_fn, [&]() -> int {
-  PTRY_P(mp_check_args(api_fn, ctx, points, scalars, m, opts, out_xy_inf));
+  PTRY(mp_check_args(api_fn, ctx, points, scalars, m, opts, out_xy_inf));
   Ctx& c = ctx->c;
   CTX_ENTER(c, api_fn);
   HIP_TRY(hipSetDevice(c.device));
@@ -613,15 +567,15 @@ int plonk_msm_points(plonk_ctx* ctx, const uint8_t* points, const uint64_t* scal
   in.flags = opts ? opts->flags : 0;
   if (m) {
     const uint64_t pbytes = (in.flags & PLONK_POINTS_COMPRESSED ? 48ull : 96ull) * m;
-    PTRY_P(w.need(MpWork::POINTS, pbytes));
-    PTRY_P(w.need(MpWork::SCALARS, 32 * m));
+    PTRY(w.need(MpWork::POINTS, pbytes));
+    PTRY(w.need(MpWork::SCALARS, 32 * m));
     HIP_TRY(hipMemcpyAsync(w.p[MpWork::POINTS], points, pbytes, hipMemcpyHostToDevice, c.stream));
     HIP_TRY(hipMemcpyAsync(w.p[MpWork::SCALARS], scalars, 32 * m, hipMemcpyHostToDevice, c.stream));
     in.points = w.at<const uint8_t>(MpWork::POINTS);
     in.scalars = w.at<const Fr>(MpWork::SCALARS);
   }
   G1 sum;
-  PTRY_P(msm_points_run(&c, in, m, opts, &sum));
+  PTRY(msm_points_run(&c, in, m, opts, &sum));
   batch_xyzz_to_affine97(&sum, 1, reinterpret_cast<uint8_t (*)[97]>(out_xy_inf));
   return PLONK_OK;
   });
@@ -631,7 +585,7 @@ int plonk_msm_points_dev(plonk_ctx* ctx, const void* points_dev, const void* sca
                          const plonk_msm_points_opts* opts, void* out97_dev) {
   const char* const api_fn = __func__;
   return plonk::api_guard(api_fn, [&]() -> int {
-  PTRY_P(mp_check_args(api_fn, ctx, points_dev, scalars_dev, m, opts, out97_dev));
+  PTRY(mp_check_args(api_fn, ctx, points_dev, scalars_dev, m, opts, out97_dev));
   Ctx& c = ctx->c;
   CTX_ENTER(c, api_fn);
   HIP_TRY(hipSetDevice(c.device));
@@ -640,7 +594,7 @@ int plonk_msm_points_dev(plonk_ctx* ctx, const void* points_dev, const void* sca
   in.points = (const uint8_t*)points_dev;
   in.scalars = (const Fr*)scalars_dev;
   G1 sum;
-  PTRY_P(msm_points_run(&c, in, m, opts, &sum));
+  PTRY(msm_points_run(&c, in, m, opts, &sum));
   uint8_t out[1][97];
   batch_xyzz_to_affine97(&sum, 1, out);
   HIP_TRY(hipMemcpyAsync(out97_dev, out[0], 97, hipMemcpyHostToDevice, c.stream));

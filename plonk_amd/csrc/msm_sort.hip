@@ -26,7 +26,7 @@
 // pairs + a two-pass onesweep.  A bucket that attracts a large share of the digits (equal
 // coefficients) only makes one workgroup loop longer; nothing overflows.
 #include "plonk_internal.hpp"
-#include "fr29.cuh"
+#include "devmem.cuh"
 
 namespace plonk {
 namespace PLONK_MSM_NS {   // compiled once per bucket count (plonk_internal.hpp)
@@ -84,18 +84,9 @@ template <> struct TmpPlanes<uint64_t> {
 // tile-local form staged in LDS by msm_partition: fine (4) | sign (1) | table row (8) | scalar inside the tile (11)
 static_assert(TILE <= 2048, "tile-local word: 11 bits of scalar index");
 
-__device__ __forceinline__ Fr ld_scalar(const Fr* p);
 // scalar i of commitment kb: the main array below the split, the tail array above
 __device__ __forceinline__ Fr ld_scalar_at(const MsmBatch& bt, int kb, uint64_t i) {
-  return i < bt.split[kb] ? ld_scalar(bt.scalars[kb] + i) : ld_scalar(bt.tail[kb] + (i - bt.split[kb]));
-}
-__device__ __forceinline__ Fr ld_scalar(const Fr* p) {
-  const uint4* q = reinterpret_cast<const uint4*>(p);
-  const uint4 a = q[0], b = q[1];
-  Fr r;
-  r.l[0] = a.x; r.l[1] = a.y; r.l[2] = a.z; r.l[3] = a.w;
-  r.l[4] = b.x; r.l[5] = b.y; r.l[6] = b.z; r.l[7] = b.w;
-  return r;
+  return i < bt.split[kb] ? ld_fr(bt.scalars[kb] + i) : ld_fr(bt.tail[kb] + (i - bt.split[kb]));
 }
 
 // Montgomery scalar -> canonical integer: (x * 2^256) * 32 / 2^261 = x in reduced radix, exact canonicalisation

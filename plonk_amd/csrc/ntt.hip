@@ -33,7 +33,7 @@
 // tests/ntt_model.py mirrors the index arithmetic below (same names) and is
 // checked against the oracle on CPU.
 #include "plonk_internal.hpp"
-#include "fr29.cuh"
+#include "devmem.cuh"
 #include <type_traits>
 #include <utility>
 
@@ -83,20 +83,6 @@ struct NttPass {
   const Fr29Slot* w512;   // w_512^e, e < 256 (direction specific), L1-resident
 };
 
-__device__ __forceinline__ Fr ld_fr(const Fr* p) {
-  const uint4* q = reinterpret_cast<const uint4*>(p);
-  uint4 a = q[0], b = q[1];
-  Fr r;
-  r.l[0] = a.x; r.l[1] = a.y; r.l[2] = a.z; r.l[3] = a.w;
-  r.l[4] = b.x; r.l[5] = b.y; r.l[6] = b.z; r.l[7] = b.w;
-  return r;
-}
-__device__ __forceinline__ void st_fr(Fr* p, const Fr& v) {
-  uint4* q = reinterpret_cast<uint4*>(p);
-  q[0] = make_uint4(v.l[0], v.l[1], v.l[2], v.l[3]);
-  q[1] = make_uint4(v.l[4], v.l[5], v.l[6], v.l[7]);
-}
-
 // LDS planes: data[l * 2048 + idx]
 __device__ __forceinline__ Fr29 lds_get(const uint32_t* base, int stride, int idx) {
   Fr29 r;
@@ -107,22 +93,6 @@ __device__ __forceinline__ Fr29 lds_get(const uint32_t* base, int stride, int id
 __device__ __forceinline__ void lds_put(uint32_t* base, int stride, int idx, const Fr29& v) {
 #pragma unroll
   for (int l = 0; l < Fr29::N; ++l) base[l * stride + idx] = v.l[l];
-}
-__device__ __forceinline__ Fr29 ld_tw(const Fr29Slot* p) {
-  const uint4* q = reinterpret_cast<const uint4*>(p);
-  const uint4 a = q[0], b = q[1];
-  const uint32_t c = p->w[8];
-  Fr29 r;
-  r.l[0] = a.x; r.l[1] = a.y; r.l[2] = a.z; r.l[3] = a.w;
-  r.l[4] = b.x; r.l[5] = b.y; r.l[6] = b.z; r.l[7] = b.w;
-  r.l[8] = c;
-  return r;
-}
-__device__ __forceinline__ void st_tw(Fr29Slot* p, const Fr29& v) {
-  uint4* q = reinterpret_cast<uint4*>(p);
-  q[0] = make_uint4(v.l[0], v.l[1], v.l[2], v.l[3]);
-  q[1] = make_uint4(v.l[4], v.l[5], v.l[6], v.l[7]);
-  q[2] = make_uint4(v.l[8], 0u, 0u, 0u);
 }
 
 // tests/ntt_model.py: elem_index
@@ -425,8 +395,7 @@ void ntt_plan(uint32_t L, int r[3], int* npass) {   // tests/ntt_model.py: plan
 }
 
 static Fr host_omega(uint32_t L, bool inverse) {   // domain.rs:142-145,155
-  Fr g = fr_root_of_unity();
-  for (uint32_t i = L; i < 32; ++i) g = g.sqr();
+  const Fr g = fr_domain_root(L);
   return inverse ? g.inv() : g;
 }
 

@@ -21,10 +21,47 @@
       return PLONK_ERR_HIP;                                              \
     }                                                                    \
   } while (0)
+// pass a non-zero return code of an internal call on to the caller
+#define PTRY(expr) do { int _rc = (expr); if (_rc) return _rc; } while (0)
+// leave an entry point (which has its name in `api_fn`) with `code` and `msg` as the last-error text
+#define API_FAIL(code, msg) return (plonk::set_last_error(api_fn, msg, __FILE__, __LINE__), code)
 
 namespace plonk {
 
 void set_last_error(const char* what, const char* detail, const char* file, int line);
+
+// Grow-only device buffers, named by the enum of the struct that holds them: need() leaves a buffer that is large enough
+// alone and replaces a smaller one (its contents are lost), so a call whose sizes fit an earlier one allocates nothing.
+// EMPTY_BYTES: what a request for 0 bytes allocates (0: nothing, p[i] may stay null).
+template <int NBUF, uint64_t EMPTY_BYTES = 0>
+struct DevBufs {
+  void* p[NBUF] = {};
+  uint64_t cap[NBUF] = {};
+  DevBufs() = default;
+  DevBufs(const DevBufs&) = delete;
+  DevBufs& operator=(const DevBufs&) = delete;
+  ~DevBufs() {
+    for (int i = 0; i < NBUF; ++i) (void)hipFree(p[i]);
+  }
+  int need(int i, uint64_t bytes) {
+    if (!bytes) bytes = EMPTY_BYTES;
+    if (bytes <= cap[i]) return PLONK_OK;
+    (void)hipFree(p[i]);
+    p[i] = nullptr;
+    cap[i] = 0;
+    HIP_TRY(hipMalloc(&p[i], bytes));
+    cap[i] = bytes;
+    return PLONK_OK;
+  }
+  template <class T>
+  T* at(int i) const { return (T*)p[i]; }
+  uint64_t bytes() const {
+    uint64_t s = 0;
+    for (int i = 0; i < NBUF; ++i) s += cap[i];
+    return s;
+  }
+};
+
 struct Ctx;
 // A context whose collective timed out without its stream ever draining (comm_sync, Ctx::comm_poisoned) has a dead kernel at
 // the head of its main stream: anything queued behind it never runs and anything that waits for the stream never returns.

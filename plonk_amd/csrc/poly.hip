@@ -15,25 +15,12 @@
 #include <cstdlib>
 
 #include "plonk_internal.hpp"
-#include "fr29.cuh"
+#include "devmem.cuh"
 #include "fp_safegcd.cuh"
 #include "poly.hpp"
 
 namespace plonk {
 
-__device__ __forceinline__ Fr ldf(const Fr* p) {
-  const uint4* q = reinterpret_cast<const uint4*>(p);
-  uint4 a = q[0], b = q[1];
-  Fr r;
-  r.l[0] = a.x; r.l[1] = a.y; r.l[2] = a.z; r.l[3] = a.w;
-  r.l[4] = b.x; r.l[5] = b.y; r.l[6] = b.z; r.l[7] = b.w;
-  return r;
-}
-__device__ __forceinline__ void stf(Fr* p, const Fr& v) {
-  uint4* q = reinterpret_cast<uint4*>(p);
-  q[0] = make_uint4(v.l[0], v.l[1], v.l[2], v.l[3]);
-  q[1] = make_uint4(v.l[4], v.l[5], v.l[6], v.l[7]);
-}
 __device__ __forceinline__ Fr small(uint32_t v, const Fr& one) {   // v * 1 in Montgomery form, v <= 128
   Fr acc = Fr::zero();
   Fr p = one;
@@ -49,7 +36,7 @@ __device__ __forceinline__ Fr small(uint32_t v, const Fr& one) {   // v * 1 in M
 // ---------------------------------------------------------------------------
 __global__ void fill_zero_kernel(Fr* p, uint64_t n) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) stf(p + i, Fr::zero());
+  if (i < n) st_fr(p + i, Fr::zero());
 }
 
 // blind_poly_with_blinders (prover.rs:139-152): c[i] -= b_i ; c[n + i] = b_i
@@ -59,9 +46,9 @@ __global__ void fill_zero_kernel(Fr* p, uint64_t n) {
 __global__ void blind_kernel(Fr* coeffs, uint64_t n, BlindArgs a) {
   const int i = threadIdx.x;
   if (i < a.count) {
-    const Fr low = (uint64_t)i >= n ? a.b[i - n] : ldf(coeffs + i);
-    stf(coeffs + i, low - a.b[i]);
-    if (n + i >= (uint64_t)a.count) stf(coeffs + n + i, a.b[i]);
+    const Fr low = (uint64_t)i >= n ? a.b[i - n] : ld_fr(coeffs + i);
+    st_fr(coeffs + i, low - a.b[i]);
+    if (n + i >= (uint64_t)a.count) st_fr(coeffs + n + i, a.b[i]);
   }
 }
 
@@ -72,11 +59,11 @@ __global__ void split_t_kernel(Fr* __restrict__ t, uint64_t n, uint64_t np, Fr* 
   const int part = blockIdx.y;   // 0..2
   if (i >= np) return;
   Fr v = Fr::zero();
-  if (i < n) v = ldf(t + (uint64_t)part * n + i);
+  if (i < n) v = ld_fr(t + (uint64_t)part * n + i);
   else if (i == n) v = a.b[part];                   // t_low += b12 X^n, t_mid += b13 X^n, t_high += b14 X^n
   if (part >= 1 && i == 0) v = v - a.b[part - 1];   // t_mid -= b12, t_high -= b13
-  stf(out + (uint64_t)part * np + i, v);
-  if (part == 0 && i == n + 1) stf(t + 3 * n, ldf(t + 3 * n) - a.b[2]);   // t_fourth -= b14 (nobody reads t[3n])
+  st_fr(out + (uint64_t)part * np + i, v);
+  if (part == 0 && i == n + 1) st_fr(t + 3 * n, ld_fr(t + 3 * n) - a.b[2]);   // t_fourth -= b14 (nobody reads t[3n])
 }
 
 // highest index with a non-zero coefficient + 1 (Polynomial::from_coefficients_vec trim, polynomial.rs:79).
@@ -85,7 +72,7 @@ __global__ void __launch_bounds__(256) trimmed_len_kernel(const Fr* __restrict__
   __shared__ unsigned long long sh[256];
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   unsigned long long v = 0;
-  if (i < n && !ldf(p + i).is_zero()) v = i + 1;
+  if (i < n && !ld_fr(p + i).is_zero()) v = i + 1;
   sh[threadIdx.x] = v;
   __syncthreads();
   for (int d = 128; d >= 1; d >>= 1) {
@@ -108,8 +95,8 @@ __global__ void __launch_bounds__(256) sigma_evals_kernel(const uint32_t* __rest
   if (i >= n) return;
   const uint32_t m = map[(uint64_t)col * n + i];
   const uint32_t to = m >> 30;
-  const Fr r = ldf(roots + (m & 0x3FFFFFFFu));
-  stf(out + (uint64_t)col * stride + i, to ? r * a.ks[to] : r);
+  const Fr r = ld_fr(roots + (m & 0x3FFFFFFFu));
+  st_fr(out + (uint64_t)col * stride + i, to ? r * a.ks[to] : r);
 }
 // Wire columns of a proof from the witness values (prover.rs:446-460): column `col`, row i takes the value
 // of witness idx[col][i]; rows past the last gate are zero.
@@ -118,41 +105,21 @@ __global__ void __launch_bounds__(256) gather_wires_kernel(const uint32_t* __res
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t col = blockIdx.y;
   if (i >= n) return;
-  stf(wires + (uint64_t)col * n + i, i < constraints ? ldf(values + idx[(uint64_t)col * constraints + i]) : Fr::zero());
+  st_fr(wires + (uint64_t)col * n + i, i < constraints ? ld_fr(values + idx[(uint64_t)col * constraints + i]) : Fr::zero());
 }
 
 __global__ void scatter_pi_kernel(Fr* dense, const uint64_t* idx, const Fr* val, uint64_t count) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < count) stf(dense + idx[i], ldf(val + i));
+  if (i < count) st_fr(dense + idx[i], ld_fr(val + i));
 }
 
 // ---------------------------------------------------------------------------
 // Reduced-radix helpers for the O(n) kernels below.  Values in "twiddle form" x * R'' (fr29.cuh)
 // are closed under Fr29::mul (x R'' * y R'' / R'' = xy R''), so chains of data x data products
-// run there: one product converts in (twiddle_from_fr), one converts out (* R / R'').
+// run there: one product converts in (twiddle_from_fr), one converts out (* R / R'').  The kernel operand Tw and its
+// conversions (tw29, tw_of, tw_plain) are in devmem.cuh.
 // ---------------------------------------------------------------------------
-struct Tw {
-  uint32_t w[9];
-};
-__device__ __forceinline__ Fr29 tw29(const Tw& t) {
-  Fr29 r;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) r.l[i] = t.w[i];
-  return r;
-}
-static Tw tw_of(const Fr& x) {   // host: x (R form) -> x * R''
-  const Fr29 t = Fr29::twiddle_from_fr(x);
-  Tw r;
-  for (int i = 0; i < 9; ++i) r.w[i] = t.l[i];
-  return r;
-}
-static Tw tw_plain(const Fr& x) {   // host: re-sliced R-form value (multiplying a twiddle-form value by it converts back)
-  const Fr29 t = Fr29::from_fr(x);
-  Tw r;
-  for (int i = 0; i < 9; ++i) r.w[i] = t.l[i];
-  return r;
-}
-__device__ __forceinline__ Fr29 ld29_(const Fr* p) { return Fr29::from_fr(ldf(p)); }
+__device__ __forceinline__ Fr29 ld29_(const Fr* p) { return Fr29::from_fr(ld_fr(p)); }
 // x^e in twiddle form (e > 0 handled by square-and-multiply; e == 0 -> one_t)
 __device__ __forceinline__ Fr29 pow_tw(const Fr29& xt, uint64_t e, const Fr29& one_t) {
   Fr29 acc = one_t;
@@ -209,7 +176,7 @@ __global__ void __launch_bounds__(BI_T) batch_inverse_kernel(Fr* __restrict__ v,
     pre[k] = acc;
     const uint64_t i = base + (uint64_t)k * BI_T;
     if (i < n) {
-      const Fr x = ldf(v + i);
+      const Fr x = ld_fr(v + i);
       if (!x.is_zero()) {
         nz |= 1u << k;
         acc = Fr29::mul(acc, TW_IO ? Fr29::from_fr(x) : Fr29::mul(Fr29::from_fr(x), conv).csub_q());
@@ -249,9 +216,9 @@ __global__ void __launch_bounds__(BI_T) batch_inverse_kernel(Fr* __restrict__ v,
   for (int k = BI_E - 1; k >= 0; --k) {
     const uint64_t i = base + (uint64_t)k * BI_T;
     if ((nz >> k) & 1) {
-      const Fr29 xt = TW_IO ? Fr29::from_fr(ldf(v + i)) : Fr29::mul(Fr29::from_fr(ldf(v + i)), conv).csub_q();
+      const Fr29 xt = TW_IO ? Fr29::from_fr(ld_fr(v + i)) : Fr29::mul(Fr29::from_fr(ld_fr(v + i)), conv).csub_q();
       const Fr29 inv_t = Fr29::mul(suf, pre[k]);
-      stf(v + i, TW_IO ? inv_t.to_fr() : Fr29::mul(inv_t, one_r).to_fr());
+      st_fr(v + i, TW_IO ? inv_t.to_fr() : Fr29::mul(inv_t, one_r).to_fr());
       suf = Fr29::mul(suf, xt);
     }
   }
@@ -285,7 +252,7 @@ __global__ void __launch_bounds__(SCAN_T) scan_block_kernel(Fr* __restrict__ dat
     const uint64_t li = base + k;
     if (li < n) {
       const uint64_t gi = REV ? (n - 1 - li) : li;
-      acc = sop<MUL>(acc, ldf(data + gi));
+      acc = sop<MUL>(acc, ld_fr(data + gi));
     }
     v[k] = acc;
   }
@@ -300,13 +267,13 @@ __global__ void __launch_bounds__(SCAN_T) scan_block_kernel(Fr* __restrict__ dat
     __syncthreads();
   }
   const Fr excl = t ? sh[t - 1] : sid<MUL>();
-  if (t == SCAN_T - 1) stf(totals + blockIdx.x, sh[t]);
+  if (t == SCAN_T - 1) st_fr(totals + blockIdx.x, sh[t]);
 #pragma unroll
   for (int k = 0; k < SCAN_E; ++k) {
     const uint64_t li = base + k;
     if (li < n) {
       const uint64_t gi = REV ? (n - 1 - li) : li;
-      stf(data + gi, sop<MUL>(excl, v[k]));
+      st_fr(data + gi, sop<MUL>(excl, v[k]));
     }
   }
 }
@@ -320,7 +287,7 @@ __global__ void __launch_bounds__(SCAN_T) scan_totals_kernel(Fr* __restrict__ to
   Fr acc = sid<MUL>();
   for (uint32_t k = 0; k < per; ++k) {
     const uint32_t i = t * per + k;
-    if (i < nb) acc = sop<MUL>(acc, ldf(totals + i));
+    if (i < nb) acc = sop<MUL>(acc, ld_fr(totals + i));
   }
   sh[t] = acc;
   __syncthreads();
@@ -336,8 +303,8 @@ __global__ void __launch_bounds__(SCAN_T) scan_totals_kernel(Fr* __restrict__ to
   for (uint32_t k = 0; k < per; ++k) {
     const uint32_t i = t * per + k;
     if (i < nb) {
-      acc = sop<MUL>(acc, ldf(totals + i));
-      stf(totals + i, acc);
+      acc = sop<MUL>(acc, ld_fr(totals + i));
+      st_fr(totals + i, acc);
     }
   }
 }
@@ -345,14 +312,14 @@ __global__ void __launch_bounds__(SCAN_T) scan_totals_kernel(Fr* __restrict__ to
 template <bool MUL, bool REV>
 __global__ void __launch_bounds__(SCAN_T) scan_apply_kernel(Fr* __restrict__ data, uint64_t n, const Fr* __restrict__ totals) {
   if (blockIdx.x == 0) return;
-  const Fr off = ldf(totals + blockIdx.x - 1);
+  const Fr off = ld_fr(totals + blockIdx.x - 1);
   const uint64_t base = (uint64_t)blockIdx.x * SCAN_BLOCK + (uint64_t)threadIdx.x * SCAN_E;
 #pragma unroll
   for (int k = 0; k < SCAN_E; ++k) {
     const uint64_t li = base + k;
     if (li < n) {
       const uint64_t gi = REV ? (n - 1 - li) : li;
-      stf(data + gi, sop<MUL>(off, ldf(data + gi)));
+      st_fr(data + gi, sop<MUL>(off, ld_fr(data + gi)));
     }
   }
 }
@@ -419,11 +386,11 @@ __global__ void __launch_bounds__(SCAN_T) pscan_block_kernel(Fr* __restrict__ da
   }
   Fr29 tot;
   const Fr29 excl = ps_lanes(acc, sh, t, one_t, &tot);
-  if (t == 0) stf(totals + blockIdx.x, tot.to_fr());
+  if (t == 0) st_fr(totals + blockIdx.x, tot.to_fr());
   const Fr29 post = FINAL ? Fr29::mul(excl, tw29(a.one_r)) : excl;   // (x R'') * R / R'' = x R
 #pragma unroll
   for (int k = 0; k < E; ++k)
-    if (base + k < n) stf(data + base + k, Fr29::mul(post, v[k]).to_fr());
+    if (base + k < n) st_fr(data + base + k, Fr29::mul(post, v[k]).to_fr());
 }
 __global__ void __launch_bounds__(SCAN_T) pscan_totals_kernel(Fr* __restrict__ totals, uint32_t nb, uint32_t per, PScanArgs a) {
   __shared__ uint32_t sh[9][SCAN_T];
@@ -440,7 +407,7 @@ __global__ void __launch_bounds__(SCAN_T) pscan_totals_kernel(Fr* __restrict__ t
     const uint32_t i = t * per + k;
     if (i < nb) {
       acc = Fr29::mul(acc, ld29_(totals + i));
-      stf(totals + i, acc.to_fr());
+      st_fr(totals + i, acc.to_fr());
     }
   }
 }
@@ -453,7 +420,7 @@ __global__ void __launch_bounds__(SCAN_T) pscan_apply_kernel(Fr* __restrict__ da
   const uint64_t base = (uint64_t)blockIdx.x * (SCAN_T * E) + (uint64_t)threadIdx.x * E;
 #pragma unroll
   for (int k = 0; k < E; ++k)
-    if (base + k < n) stf(data + base + k, Fr29::mul(ld29_(data + base + k), off).to_fr());
+    if (base + k < n) st_fr(data + base + k, Fr29::mul(ld29_(data + base + k), off).to_fr());
 }
 uint32_t scan_prefix_blocks(uint64_t n) { const uint64_t blk = (uint64_t)SCAN_T * pscan_e(n); return (uint32_t)((n + blk - 1) / blk); }
 static void pscan_launch_block(Ctx* c, bool final, uint32_t nb, Fr* data, uint64_t n, Fr* totals, const PScanArgs& a) {
@@ -523,24 +490,14 @@ struct PermConst {
   Tw b32_t;      // 32 * beta: sigma (data form) * this = beta * sigma in twiddle form
   Tw one_t;
 };
-__device__ __forceinline__ Fr29 ld_slot(const void* base, uint64_t idx) {
-  const uint4* q = reinterpret_cast<const uint4*>(reinterpret_cast<const Fr29Slot*>(base) + idx);
-  const uint4 a = q[0], b = q[1];
-  const uint32_t c = reinterpret_cast<const Fr29Slot*>(base)[idx].w[8];
-  Fr29 r;
-  r.l[0] = a.x; r.l[1] = a.y; r.l[2] = a.z; r.l[3] = a.w;
-  r.l[4] = b.x; r.l[5] = b.y; r.l[6] = b.z; r.l[7] = b.w;
-  r.l[8] = c;
-  return r;
-}
 __global__ void __launch_bounds__(128) perm_terms_kernel(PermArgs a, PermConst k) {
   const uint64_t j0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (j0 >= a.count) return;
   const uint64_t i = a.first + j0;
   if (i == 0) {
     const Fr one = tw29(k.one_t).to_fr();
-    stf(a.num, one);
-    stf(a.den, one);
+    st_fr(a.num, one);
+    st_fr(a.den, one);
     return;
   }
   const uint64_t r = i - 1;
@@ -556,15 +513,15 @@ __global__ void __launch_bounds__(128) perm_terms_kernel(PermArgs a, PermConst k
     num = j ? Fr29::mul(num, nf) : nf;
     den = j ? Fr29::mul(den, df) : df;
   }
-  stf(a.num + i, num.to_fr());
-  stf(a.den + i, den.to_fr());
+  st_fr(a.num + i, num.to_fr());
+  st_fr(a.den + i, den.to_fr());
 }
 __global__ void mul_arrays_kernel(Fr* __restrict__ a, const Fr* __restrict__ b, uint64_t n, int* zero_flag) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const Fr y = ldf(b + i);
+  const Fr y = ld_fr(b + i);
   if (zero_flag && y.is_zero()) *zero_flag = 1;
-  stf(a + i, Fr29::mul(ld29_(a + i), Fr29::from_fr(y)).to_fr());   // twiddle form is closed under the product
+  st_fr(a + i, Fr29::mul(ld29_(a + i), Fr29::from_fr(y)).to_fr());   // twiddle form is closed under the product
 }
 
 // ---------------------------------------------------------------------------
@@ -583,7 +540,7 @@ __device__ __forceinline__ Fr delta4(const Fr& f, const Fr& one) {   // f (f-1)(
 // challenge constants are handed over as c * 2^(5k) * R'' (QuotientConst).  The range / logic /
 // fixed-base / curve-addition widgets — identically zero selectors in most circuits — run on
 // the exact 32-bit path from the same loaded values.
-__device__ __forceinline__ Fr29 ld29(const Fr* p) { return Fr29::from_fr(ldf(p)); }
+__device__ __forceinline__ Fr29 ld29(const Fr* p) { return Fr29::from_fr(ld_fr(p)); }
 __device__ __forceinline__ Fr29 c29(const uint32_t (&v)[9]) {
   Fr29 r;
 #pragma unroll
@@ -711,7 +668,7 @@ __global__ void __launch_bounds__(128, WIDGETS ? 2 : 4) quotient_kernel(Quotient
     }
     t = Fr29::add_csub(t, Fr29::mul(u, tw29(wc.one_r)));   // back to the data domain
   }
-  stf(q.out + i, Fr29::mul(t, c29(q.k.vinv[i & 7])).to_fr());
+  st_fr(q.out + i, Fr29::mul(t, c29(q.k.vinv[i & 7])).to_fr());
 }
 
 // t holds A = T mod (X^nq - g^nq) (nq coefficients).  T = T_lo + X^nq T_hi with deg T_hi <= 6, so
@@ -724,34 +681,34 @@ struct DealiasArgs {
 __global__ void dealias_kernel(Fr* __restrict__ t, uint64_t nq, DealiasArgs a) {
   const uint32_t k = threadIdx.x;
   if (k < 7) {
-    const Fr A = ldf(t + k);
-    stf(t + nq + k, (A - a.low[k]) * a.g_inv);
-    stf(t + k, a.low[k]);
+    const Fr A = ld_fr(t + k);
+    st_fr(t + nq + k, (A - a.low[k]) * a.g_inv);
+    st_fr(t + k, a.low[k]);
   } else if (k < 16) {
-    stf(t + nq + k, Fr::zero());
+    st_fr(t + nq + k, Fr::zero());
   }
 }
 
 // v[i] *= s  (one-off pre-scaling of key arrays for the kernel above)
 __global__ void scale_array_kernel(Fr* __restrict__ v, uint64_t n, Fr s) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) stf(v + i, ldf(v + i) * s);
+  if (i < n) st_fr(v + i, ld_fr(v + i) * s);
 }
 
 // Montgomery limbs -> canonical little-endian scalars (BlsScalar::to_bytes), for the serialisers
 __global__ void from_mont_kernel(const Fr* __restrict__ src, Fr* __restrict__ dst, uint64_t n) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) stf(dst + i, ldf(src + i).from_mont());
+  if (i < n) st_fr(dst + i, ld_fr(src + i).from_mont());
 }
 
 // L1 numerators on the coset: out[i] = v_h[i & 7] * n_inv  (to be multiplied by 1/(linear[i]-1))
 __global__ void l1_prepare_kernel(const Fr* __restrict__ linear, Fr* __restrict__ out, uint64_t n8) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n8) stf(out + i, ldf(linear + i) - Fr::one());
+  if (i < n8) st_fr(out + i, ld_fr(linear + i) - Fr::one());
 }
 __global__ void l1_finish_kernel(Fr* __restrict__ l1, uint64_t n8, L1Args a) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n8) stf(l1 + i, ldf(l1 + i) * a.vh[i & 7] * a.n_inv);
+  if (i < n8) st_fr(l1 + i, ld_fr(l1 + i) * a.vh[i & 7] * a.n_inv);
 }
 
 // ---------------------------------------------------------------------------
@@ -808,7 +765,7 @@ __global__ void __launch_bounds__(EV_T) eval_kernel(EvalArgsD a) {
     }
   }
   acc = eval_tree(acc, sh, pw + LE, t, 8);
-  if (t == 0) stf(a.partial + (uint64_t)blockIdx.y * a.max_blocks + blockIdx.x, acc.to_fr());
+  if (t == 0) st_fr(a.partial + (uint64_t)blockIdx.y * a.max_blocks + blockIdx.x, acc.to_fr());
 }
 template <int LE>
 __global__ void __launch_bounds__(EV_T) eval_final_kernel(EvalArgsD a, uint32_t nblocks, int levels, Fr* __restrict__ out) {
@@ -828,7 +785,7 @@ __global__ void __launch_bounds__(EV_T) eval_final_kernel(EvalArgsD a, uint32_t 
     }
   }
   acc = eval_tree(acc, sh, pw + 8 + LE, t, levels);
-  if (t == 0) stf(out + blockIdx.x, acc.to_fr());
+  if (t == 0) st_fr(out + blockIdx.x, acc.to_fr());
 }
 
 // out[i] = sum_k s_k * P_k[i]  (+ constant at i == 0); the scalars are in twiddle form
@@ -850,7 +807,7 @@ __global__ void __launch_bounds__(256) lincomb_kernel(LinCombArgsD a) {
   Fr29 acc = (i == 0) ? Fr29::from_fr(a.constant) : Fr29::zero();
   for (int k = 0; k < a.count; ++k)
     if (i < a.t[k].len) acc = Fr29::add_csub(acc, Fr29::mul(ld29_(a.t[k].p + i), tw29(a.t[k].st)));
-  stf(a.out + i, acc.to_fr());
+  st_fr(a.out + i, acc.to_fr());
 }
 
 // ruffini: q_i = z^-(i+1) * sum_{j > i} c_j z^j
@@ -876,7 +833,7 @@ template <int E>
 __global__ void __launch_bounds__(256) mul_powers_kernel(const Fr* __restrict__ src, Fr* __restrict__ dst, uint64_t n,
                                                          MulPowArgs a, uint64_t src_off, uint64_t exp_off) {
   const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (g == 0 && a.zero_at != ~0ull) stf(dst + a.zero_at, Fr::zero());
+  if (g == 0 && a.zero_at != ~0ull) st_fr(dst + a.zero_at, Fr::zero());
   const uint64_t wave = g >> 6, lane = g & 63;
   const uint64_t first = wave * (64 * E) + lane;
   if (first >= n) return;
@@ -897,7 +854,7 @@ __global__ void __launch_bounds__(256) mul_powers_kernel(const Fr* __restrict__ 
   for (int k = 0; k < E; ++k) {
     const uint64_t i = first + 64ull * k;
     if (i >= n) break;
-    stf(dst + i, Fr29::mul(Fr29::add_csub(ld29_(src + i + src_off), add), p).to_fr());
+    st_fr(dst + i, Fr29::mul(Fr29::add_csub(ld29_(src + i + src_off), add), p).to_fr());
     if (E > 1) p = Fr29::mul(p, step);
   }
 }
@@ -910,9 +867,9 @@ __global__ void __launch_bounds__(256) mul_powers_kernel(const Fr* __restrict__ 
 __global__ void fold_kernel(const Fr* __restrict__ src, Fr* __restrict__ dst, uint64_t n, uint32_t extra, Fr c) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  Fr v = ldf(src + i);
-  if (i < extra) v = v + c * ldf(src + n + i);
-  stf(dst + i, v);
+  Fr v = ld_fr(src + i);
+  if (i < extra) v = v + c * ld_fr(src + n + i);
+  st_fr(dst + i, v);
 }
 
 // send[(p * cpr + k) * stride + i] = F_k[p * per + i] (zero beyond n) for i < per, then F_k[0..8)
@@ -924,11 +881,11 @@ __global__ void shard_pack_kernel(ShardPackArgs a) {
   Fr v = Fr::zero();
   if (i < a.per) {
     const uint64_t idx = (uint64_t)peer * a.per + i;
-    if (idx < a.n) v = ldf(F + idx);
+    if (idx < a.n) v = ld_fr(F + idx);
   } else {
-    v = ldf(F + (i - a.per));
+    v = ld_fr(F + (i - a.per));
   }
-  stf(a.send + ((uint64_t)peer * a.cpr + k) * a.stride + i, v);
+  st_fr(a.send + ((uint64_t)peer * a.cpr + k) * a.stride + i, v);
 }
 
 // Per coefficient index i0 of this rank's range: the Q-point inverse DFT across the classes,
@@ -942,7 +899,7 @@ __global__ void __launch_bounds__(128) shard_combine_kernel(ShardCombineArgs a) 
   const uint64_t off = extra ? a.per + (i - a.cnt) : i;            // position inside a message
   Fr F[8];
   for (uint32_t j = 0; j < a.Q; ++j)
-    F[j] = ldf(a.recv + ((uint64_t)(j % a.W) * a.cpr + j / a.W) * a.stride + off);
+    F[j] = ld_fr(a.recv + ((uint64_t)(j % a.W) * a.cpr + j / a.W) * a.stride + off);
   auto dft = [&](uint32_t i1) {
     Fr acc = Fr::zero();
     for (uint32_t j = 0; j < a.Q; ++j) acc = acc + a.coef[i1][j] * F[j];
@@ -952,7 +909,7 @@ __global__ void __launch_bounds__(128) shard_combine_kernel(ShardCombineArgs a) 
     const uint64_t idx = a.lo + i;
     for (uint32_t i1 = 0; i1 < 4; ++i1) {
       if (i1 == 0 && a.Q == 4 && idx < 7) continue;               // aliased: restored by the extra lanes
-      stf(a.parts[i1] + idx, dft(i1));
+      st_fr(a.parts[i1] + idx, dft(i1));
     }
   } else {
     const uint64_t k = i - a.cnt;
@@ -960,11 +917,11 @@ __global__ void __launch_bounds__(128) shard_combine_kernel(ShardCombineArgs a) 
     Fr top;                                                       // t[4n + k]
     if (a.Q == 4) {
       top = (dft(0) - a.low[k]) * a.g4n_inv;                      // A[k] = t[k] + g^4n t[4n + k]
-      if (k >= a.lo && k < a.hi) stf(a.parts[0] + k, a.low[k]);
+      if (k >= a.lo && k < a.hi) st_fr(a.parts[0] + k, a.low[k]);
     } else {
       top = dft(4);
     }
-    if (a.n + k >= a.lo && a.n + k < a.hi) stf(a.parts[3] + a.n + k, top);
+    if (a.n + k >= a.lo && a.n + k < a.hi) st_fr(a.parts[3] + a.n + k, top);
   }
 }
 
@@ -972,11 +929,11 @@ __global__ void __launch_bounds__(128) shard_combine_kernel(ShardCombineArgs a) 
 __global__ void shard_split_fix_kernel(ShardSplitFix a) {
   if (threadIdx.x != 0) return;
   auto own = [&](uint64_t idx) { return idx >= a.lo && idx < a.hi; };
-  if (own(a.n)) { stf(a.parts[0] + a.n, a.b[0]); stf(a.parts[1] + a.n, a.b[1]); stf(a.parts[2] + a.n, a.b[2]); }
+  if (own(a.n)) { st_fr(a.parts[0] + a.n, a.b[0]); st_fr(a.parts[1] + a.n, a.b[1]); st_fr(a.parts[2] + a.n, a.b[2]); }
   if (own(0)) {
-    stf(a.parts[1], ldf(a.parts[1]) - a.b[0]);
-    stf(a.parts[2], ldf(a.parts[2]) - a.b[1]);
-    stf(a.parts[3], ldf(a.parts[3]) - a.b[2]);
+    st_fr(a.parts[1], ld_fr(a.parts[1]) - a.b[0]);
+    st_fr(a.parts[2], ld_fr(a.parts[2]) - a.b[1]);
+    st_fr(a.parts[3], ld_fr(a.parts[3]) - a.b[2]);
   }
 }
 
@@ -1233,12 +1190,6 @@ int poly_ruffini(Ctx* c, const Fr* src, Fr* dst, uint64_t len, const Fr& z, cons
 // KZG10 openings (kzg.hip): CommitKey::compute_aggregate_witness' sum and the evaluations of its polynomials in ONE
 // pass over the coefficients (reference key.rs:394-417 reads every polynomial twice: once to evaluate, once to fold).
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ void st_slot(void* base, uint64_t idx, const Fr29& v) {
-  uint32_t* w = reinterpret_cast<Fr29Slot*>(base)[idx].w;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) w[i] = v.l[i];
-  w[9] = 0; w[10] = 0; w[11] = 0;
-}
 // tab[i] = x^i in twiddle form, one lane per power (square-and-multiply: 2 log2(i) products)
 __global__ void __launch_bounds__(256) kzg_powers_kernel(void* __restrict__ tab, uint32_t count, Tw xt, Tw one_t) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1249,7 +1200,7 @@ __global__ void __launch_bounds__(256) kzg_powers_kernel(void* __restrict__ tab,
 __global__ void __launch_bounds__(256) power_array_kernel(Fr* __restrict__ out, uint64_t n, Tw xt, Tw one_t) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  stf(out + i, Fr29::mul(Fr29::from_fr(Fr::one()), pow_tw(tw29(xt), i, tw29(one_t))).to_fr());
+  st_fr(out + i, Fr29::mul(Fr29::from_fr(Fr::one()), pow_tw(tw29(xt), i, tw29(one_t))).to_fr());
 }
 // one workgroup per polynomial: the length without its trailing zeros (Polynomial::from_coefficients_vec, the degree
 // CommitKey::commit checks).  Chunks of 256 from the top; a polynomial whose leading coefficient is set takes one step.
@@ -1261,7 +1212,7 @@ __global__ void __launch_bounds__(256) kzg_trim_kernel(KzgDesc* __restrict__ des
     if (!threadIdx.x) best = 0;
     __syncthreads();
     const uint64_t lo = hi > 256 ? hi - 256 : 0, idx = lo + threadIdx.x;
-    if (idx < hi && !ldf(p + idx).is_zero()) atomicMax(&best, (unsigned long long)(idx + 1));
+    if (idx < hi && !ld_fr(p + idx).is_zero()) atomicMax(&best, (unsigned long long)(idx + 1));
     __syncthreads();
     const uint64_t b = best;
     __syncthreads();
@@ -1285,7 +1236,7 @@ __global__ void __launch_bounds__(KZG_FOLD_T) kzg_fold_eval_kernel(KzgFoldArgs a
   for (uint32_t i = 0; i < a.count; ++i) {
     const KzgDesc d = a.desc[a.first + i];
     if (wave_j0 >= d.len) {   // wave-uniform: nothing of this polynomial here
-      if (!lane) stf(a.partial + (uint64_t)i * nwaves + wave, Fr::zero());
+      if (!lane) st_fr(a.partial + (uint64_t)i * nwaves + wave, Fr::zero());
       continue;
     }
     const Fr29 vt = ld_slot(a.vpow, a.first + i);
@@ -1308,13 +1259,13 @@ __global__ void __launch_bounds__(KZG_FOLD_T) kzg_fold_eval_kernel(KzgFoldArgs a
       for (int w = 0; w < 9; ++w) o.l[w] = __shfl_down(h.l[w], off, 64);
       h = Fr29::add_csub(h, o);
     }
-    if (!lane) stf(a.partial + (uint64_t)i * nwaves + wave, h.to_fr());
+    if (!lane) st_fr(a.partial + (uint64_t)i * nwaves + wave, h.to_fr());
   }
 #define KZG_STORE(k)                                                      \
   if (j0 + (k) < a.len) {                                                 \
     Fr29 r = f[k];                                                        \
     if (a.accumulate) r = Fr29::add_csub(r, ld29_(a.fold + j0 + (k)));    \
-    stf(a.fold + j0 + (k), r.to_fr());                                    \
+    st_fr(a.fold + j0 + (k), r.to_fr());                                  \
   }
   KZG_STORE(0) KZG_STORE(1) KZG_STORE(2) KZG_STORE(3)
 #undef KZG_STORE
@@ -1324,19 +1275,19 @@ __global__ void __launch_bounds__(256) kzg_eval_final_kernel(const Fr* __restric
   __shared__ Fr sh[256];
   const uint32_t t = threadIdx.x;
   Fr acc = Fr::zero();
-  for (uint32_t w = t; w < nwaves; w += 256) acc = acc + ldf(partial + (uint64_t)blockIdx.x * nwaves + w);
+  for (uint32_t w = t; w < nwaves; w += 256) acc = acc + ld_fr(partial + (uint64_t)blockIdx.x * nwaves + w);
   sh[t] = acc;
   __syncthreads();
   for (uint32_t h = 128; h; h >>= 1) {
     if (t < h) sh[t] = sh[t] + sh[t + h];
     __syncthreads();
   }
-  if (!t) stf(evals + blockIdx.x, sh[0]);
+  if (!t) st_fr(evals + blockIdx.x, sh[0]);
 }
 __global__ void __launch_bounds__(256) shift_down_kernel(const Fr* __restrict__ src, Fr* __restrict__ dst, uint64_t len) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= len) return;
-  stf(dst + i, i + 1 < len ? ldf(src + i + 1) : Fr::zero());
+  st_fr(dst + i, i + 1 < len ? ld_fr(src + i + 1) : Fr::zero());
 }
 int poly_kzg_trim(Ctx* c, KzgDesc* desc_dev, uint32_t count) {
   if (!count) return PLONK_OK;

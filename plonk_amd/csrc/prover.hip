@@ -137,15 +137,8 @@ struct Prover {
 };
 
 // ---- host helpers -------------------------------------------------------------------
-static Fr omega_of(uint32_t L) {
-  Fr g = fr_root_of_unity();
-  for (uint32_t i = L; i < 32; ++i) g = g.sqr();
-  return g;
-}
 
 
-
-#define PTRY(expr) do { int _rc = (expr); if (_rc) return _rc; } while (0)
 
 // Work that does not depend on a Fiat-Shamir challenge (the coset FFTs of the wire, public-input
 // and z polynomials) is issued on the context's low-priority side stream so it fills the
@@ -616,7 +609,7 @@ static int prover_build(Ctx* c, const plonk_prover_desc* d, const CircuitSrc* ci
     // vanishing polynomial over the coset: qf distinct values g^n * w_qf^i - 1 (domain.rs:338-351) and
     // their inverses (prover.rs:78-91); the 8 slots repeat with period qf
     Fr point = fr_generator().pow_u64(n);
-    const Fr step = omega_of(L + p->lq).pow_u64(n);   // primitive qf-th root of unity
+    const Fr step = fr_domain_root(L + p->lq).pow_u64(n);   // primitive qf-th root of unity
     for (int i = 0; i < 8; ++i) {
       l1a.vh[i] = point - Fr::one();
       p->vinv[i] = l1a.vh[i].inv();
@@ -628,7 +621,7 @@ static int prover_build(Ctx* c, const plonk_prover_desc* d, const CircuitSrc* ci
     p->inv32 = Fr::from_u64(32).inv();
     p->edwards_d = (fr_small(10240) * fr_small(10241).inv()).neg();   // dusk_jubjub::EDWARDS_D
     p->gq_inv = fr_generator().pow_u64(p->n8).inv();                    // g^-(quotient domain size), de-aliasing
-    p->omega = omega_of(L);
+    p->omega = fr_domain_root(L);
     p->omega_inv = p->omega.inv();
     if (p->sharded) {   // coef[i1][j] = g^(-n i1) w_Q^(-j i1) / Q
       const Fr gn_inv = fr_generator().pow_u64(n).inv(), w_inv = step.inv(), q_inv = Fr::from_u64(p->Q).inv();
@@ -653,7 +646,7 @@ static int prover_build(Ctx* c, const plonk_prover_desc* d, const CircuitSrc* ci
   } else {
     // the same evaluations restricted to the classes this rank owns: size-n coset transforms with
     // shift g w_N^j, arrays laid out [polynomial][owned class][n]
-    const Fr wN = omega_of(L + p->lq);
+    const Fr wN = fr_domain_root(L + p->lq);
     for (uint32_t k = 0; k < p->cpr; ++k) {
       const uint32_t j = p->cls[k];
       const Fr shift = fr_generator() * wN.pow_u64(j);
@@ -1909,7 +1902,7 @@ constexpr uint64_t SER_DOMAIN = 8 + 4 + 5 * 32, SER_VK = 20 * 48 + 8, SER_RAW_PO
 // EvaluationDomain::to_bytes (domain.rs:59-79) of the domain of size 2^log
 void put_domain(uint8_t* p, uint32_t log) {
   const uint64_t size = 1ull << log;
-  const Fr gen = omega_of(log), size_fe = Fr::from_u64(size);
+  const Fr gen = fr_domain_root(log), size_fe = Fr::from_u64(size);
   put_le64(p, size);
   for (int i = 0; i < 4; ++i) p[8 + i] = (uint8_t)(log >> (8 * i));
   const Fr vals[5] = {size_fe, size_fe.inv(), gen, gen.inv(), fr_generator().inv()};
@@ -1994,7 +1987,7 @@ int plonk_prover_to_bytes(plonk_prover* pr, uint8_t* out, uint64_t cap, uint64_t
     w += SER_DOMAIN;
     uint8_t vh[8][32];
     Fr point = fr_generator().pow_u64(n);
-    const Fr step = omega_of(L + 3).pow_u64(n);
+    const Fr step = fr_domain_root(L + 3).pow_u64(n);
     for (int i = 0; i < 8; ++i) { put_scalar(vh[i], point - Fr::one()); point = point * step; }
     for (uint64_t i = 0; i < n8; ++i) memcpy(w + 32 * i, vh[i & 7], 32);
     w += 32 * n8;

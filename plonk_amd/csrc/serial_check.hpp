@@ -68,8 +68,7 @@ struct Domain {   // EvaluationDomain::new (domain.rs:122-158)
     log = (uint32_t)__builtin_ctzll(n);
     if (log >= 32) return false;   // TWO_ADACITY
     size = n;
-    group_gen = fr_root_of_unity();
-    for (uint32_t i = log; i < 32; ++i) group_gen = group_gen.sqr();
+    group_gen = fr_domain_root(log);
     size_fe = Fr::from_u64(n);
     size_inv = size_fe.inv();
     group_gen_inv = group_gen.inv();

@@ -45,8 +45,6 @@
 #include "hostpairing.hpp"
 #include "verify_core.hpp"
 
-#define PTRY_V(expr) do { int _rc = (expr); if (_rc) return _rc; } while (0)
-
 namespace plonk { struct Verifier; }
 struct plonk_verifier {
   plonk::Verifier* v;
@@ -419,7 +417,7 @@ static int batch_check(BatchState& b, const uint32_t* which, size_t m, bool* ok)
   idR[15] = 15;
   const auto tp = std::chrono::steady_clock::now();   // rho and the packing are host scalar work (ms_scalars), not MSM
   H1 sums[2];
-  PTRY_V(msm_device(v, b.sc_host.data(), b.id_host.data(), nL, nR, sums));
+  PTRY(msm_device(v, b.sc_host.data(), b.id_host.data(), nL, nR, sums));
   const auto t1 = std::chrono::steady_clock::now();
   *ok = pairing_check(sums, v->x_h, v->h);
   const auto t2 = std::chrono::steady_clock::now();
@@ -435,14 +433,14 @@ static int batch_check(BatchState& b, const uint32_t* which, size_t m, bool* ok)
 static int bisect(BatchState& b, std::vector<uint32_t>& which, size_t lo, size_t hi) {
   if (lo >= hi) return PLONK_OK;
   bool ok = false;
-  PTRY_V(batch_check(b, which.data() + lo, hi - lo, &ok));
+  PTRY(batch_check(b, which.data() + lo, hi - lo, &ok));
   if (ok) return PLONK_OK;
   if (hi - lo == 1) {
     b.ps[which[lo]].status = VS_REJECT;
     return PLONK_OK;
   }
   const size_t mid = lo + (hi - lo) / 2;
-  PTRY_V(bisect(b, which, lo, mid));
+  PTRY(bisect(b, which, lo, mid));
   return bisect(b, which, mid, hi);
 }
 
@@ -464,26 +462,11 @@ static void replay_task(void* arg, int index) {
 
 // ---- plonk_verify_mixed: the host side --------------------------------------------------------------------------------
 // The context's grow-only workspace of mixed calls (Ctx::verify_ws): a call whose sizes fit an earlier one allocates nothing.
-struct MixedWork {
+struct MixedBufs {
   enum { PTS, KIND, COMP, PROOFS, SLOT, PI_OFF, PI, SLOTS, PI_ROOT, STATUS, SCALARS, DIGEST, WHICH, ORDER, SEG, SEG_PT,
          WV, GPART, SC, IDS, PART, E_PRE, E_SUMS, E_VERDICT, NBUF };   // E_*: plonk_verify_each (pairing.hip)
-  void* p[NBUF] = {};
-  uint64_t cap[NBUF] = {};
-  ~MixedWork() {
-    for (int i = 0; i < NBUF; ++i) (void)hipFree(p[i]);
-  }
-  int need(int i, uint64_t bytes) {
-    if (bytes <= cap[i]) return PLONK_OK;
-    (void)hipFree(p[i]);
-    p[i] = nullptr;
-    cap[i] = 0;
-    HIP_TRY(hipMalloc(&p[i], bytes));
-    cap[i] = bytes;
-    return PLONK_OK;
-  }
-  template <class T>
-  T* at(int i) const { return (T*)p[i]; }
 };
+struct MixedWork : MixedBufs, DevBufs<MixedBufs::NBUF> {};
 
 void verify_ws_release(Ctx* c) {
   delete (MixedWork*)c->verify_ws;
@@ -548,27 +531,27 @@ static int mixed_front(MixedState& b, plonk_verifier* const* verifiers, uint32_t
     pi_off[k] = off;
     off += verifiers[circuit[k]]->v->core.pi_idx.size();
   }
-  PTRY_V(w.need(MixedWork::PTS, sizeof(G1Affine) * npts));
-  PTRY_V(w.need(MixedWork::KIND, 4 * npts));
-  PTRY_V(w.need(MixedWork::COMP, 48ull * PC_COUNT * count));
-  PTRY_V(w.need(MixedWork::PROOFS, PROOF_BYTES * count));
-  PTRY_V(w.need(MixedWork::SLOT, 4 * count));
-  PTRY_V(w.need(MixedWork::PI_OFF, 8 * count));
-  PTRY_V(w.need(MixedWork::PI, 32 * (pi_total ? pi_total : 1)));
-  PTRY_V(w.need(MixedWork::SLOTS, sizeof(MixedSlot) * nu));
-  PTRY_V(w.need(MixedWork::PI_ROOT, 32 * (roots.empty() ? 1 : roots.size())));
-  PTRY_V(w.need(MixedWork::STATUS, 4 * count));
-  PTRY_V(w.need(MixedWork::SCALARS, sizeof(ProofScalars) * count));
-  PTRY_V(w.need(MixedWork::DIGEST, 32 * count));
-  PTRY_V(w.need(MixedWork::WHICH, 4 * count));
-  PTRY_V(w.need(MixedWork::ORDER, 4 * count));
-  PTRY_V(w.need(MixedWork::SEG, 4 * (nu + 1)));
-  PTRY_V(w.need(MixedWork::SEG_PT, 4 * nu));
-  PTRY_V(w.need(MixedWork::WV, 32ull * (P_COUNT + 1) * count));
-  PTRY_V(w.need(MixedWork::GPART, 32 * nu));
-  PTRY_V(w.need(MixedWork::SC, 32 * nterms));
-  PTRY_V(w.need(MixedWork::IDS, 4 * nterms));
-  PTRY_V(w.need(MixedWork::PART, sizeof(G1) * 2 * VMSM_MAX_BLOCKS));
+  PTRY(w.need(MixedWork::PTS, sizeof(G1Affine) * npts));
+  PTRY(w.need(MixedWork::KIND, 4 * npts));
+  PTRY(w.need(MixedWork::COMP, 48ull * PC_COUNT * count));
+  PTRY(w.need(MixedWork::PROOFS, PROOF_BYTES * count));
+  PTRY(w.need(MixedWork::SLOT, 4 * count));
+  PTRY(w.need(MixedWork::PI_OFF, 8 * count));
+  PTRY(w.need(MixedWork::PI, 32 * (pi_total ? pi_total : 1)));
+  PTRY(w.need(MixedWork::SLOTS, sizeof(MixedSlot) * nu));
+  PTRY(w.need(MixedWork::PI_ROOT, 32 * (roots.empty() ? 1 : roots.size())));
+  PTRY(w.need(MixedWork::STATUS, 4 * count));
+  PTRY(w.need(MixedWork::SCALARS, sizeof(ProofScalars) * count));
+  PTRY(w.need(MixedWork::DIGEST, 32 * count));
+  PTRY(w.need(MixedWork::WHICH, 4 * count));
+  PTRY(w.need(MixedWork::ORDER, 4 * count));
+  PTRY(w.need(MixedWork::SEG, 4 * (nu + 1)));
+  PTRY(w.need(MixedWork::SEG_PT, 4 * nu));
+  PTRY(w.need(MixedWork::WV, 32ull * (P_COUNT + 1) * count));
+  PTRY(w.need(MixedWork::GPART, 32 * nu));
+  PTRY(w.need(MixedWork::SC, 32 * nterms));
+  PTRY(w.need(MixedWork::IDS, 4 * nterms));
+  PTRY(w.need(MixedWork::PART, sizeof(G1) * 2 * VMSM_MAX_BLOCKS));
   const hipStream_t st = c->stream;
   const auto t0 = std::chrono::steady_clock::now();
   // decode: the verifiers' VK points and g device to device, the proofs' commitments through verify_decode_kernel
@@ -664,7 +647,7 @@ static int mixed_check(MixedState& b, const uint32_t* which, size_t m, bool* ok)
   HIP_TRY(hipStreamSynchronize(st));   // the weighting is scalar work (ms_scalars), not MSM
   const auto tp = std::chrono::steady_clock::now();
   H1 sums[2];
-  PTRY_V(msm_run(c, sc, ids, nL, nR, w.at<const G1Affine>(MixedWork::PTS), w.at<const int32_t>(MixedWork::KIND),
+  PTRY(msm_run(c, sc, ids, nL, nR, w.at<const G1Affine>(MixedWork::PTS), w.at<const int32_t>(MixedWork::KIND),
                  w.at<G1>(MixedWork::PART), sums));
   const auto t1 = std::chrono::steady_clock::now();
   *ok = pairing_check(sums, *b.x_h, *b.h);
@@ -681,14 +664,14 @@ static int mixed_check(MixedState& b, const uint32_t* which, size_t m, bool* ok)
 static int mixed_bisect(MixedState& b, std::vector<uint32_t>& which, size_t lo, size_t hi) {
   if (lo >= hi) return PLONK_OK;
   bool ok = false;
-  PTRY_V(mixed_check(b, which.data() + lo, hi - lo, &ok));
+  PTRY(mixed_check(b, which.data() + lo, hi - lo, &ok));
   if (ok) return PLONK_OK;
   if (hi - lo == 1) {
     b.status[which[lo]] = VS_REJECT;
     return PLONK_OK;
   }
   const size_t mid = lo + (hi - lo) / 2;
-  PTRY_V(mixed_bisect(b, which, lo, mid));
+  PTRY(mixed_bisect(b, which, lo, mid));
   return mixed_bisect(b, which, mid, hi);
 }
 
@@ -731,7 +714,7 @@ int plonk_verifier_from_bytes(plonk_ctx* ctx, const uint8_t* blob, uint64_t len,
   *out = nullptr;
   uint8_t h96[96], xh96[96];
   std::unique_ptr<plonk::Verifier> v(new plonk::Verifier());
-  PTRY_V(plonk::parse_verifier_blob(blob, len, &v->core, v->g48, h96, xh96));
+  PTRY(plonk::parse_verifier_blob(blob, len, &v->core, v->g48, h96, xh96));
   memcpy(v->opening_key, v->g48, 48);
   memcpy(v->opening_key + 48, h96, 96);
   memcpy(v->opening_key + 144, xh96, 96);
@@ -740,12 +723,12 @@ int plonk_verifier_from_bytes(plonk_ctx* ctx, const uint8_t* blob, uint64_t len,
   CTX_ENTER(ctx->c, api_fn);
   HIP_TRY(hipSetDevice(ctx->c.device));
   v->c = &ctx->c;
-  PTRY_V(v->reserve(1));
+  PTRY(v->reserve(1));
   uint8_t comp16[16 * 48];
   for (int j = 0; j < 15; ++j) memcpy(comp16 + 48 * j, v->core.vk[j], 48);
   memcpy(comp16 + 15 * 48, v->g48, 48);
   std::vector<int32_t> st;
-  PTRY_V(plonk::decode_points(v.get(), comp16, 0, 16, &st));
+  PTRY(plonk::decode_points(v.get(), comp16, 0, 16, &st));
   for (int j = 0; j < 16; ++j)   // the host validated them: the device must agree
     if (st[j] == plonk::VDEC_BAD || (j == 15 && st[j] != plonk::VDEC_OK))
       return (plonk::set_last_error(api_fn, "device decoding of a verifier-key point disagrees with the host", __FILE__, __LINE__), PLONK_ERR_STATE);
@@ -787,7 +770,7 @@ int plonk_verify(plonk_verifier* vh, const uint8_t* proofs, const uint64_t* pi, 
   CTX_ENTER(vh->ctx->c, api_fn);
   Ctx* c = v->c;
   HIP_TRY(hipSetDevice(c->device));
-  PTRY_V(v->reserve(count));
+  PTRY(v->reserve(count));
   const auto t0 = std::chrono::steady_clock::now();
   // the 11 commitments of every proof, decoded and subgroup-checked on the device
   std::vector<uint8_t> comp(48ull * plonk::PC_COUNT * count);
@@ -796,7 +779,7 @@ int plonk_verify(plonk_verifier* vh, const uint8_t* proofs, const uint64_t* pi, 
   plonk::FinishPool* pool = count > 1 ? plonk::finish_pool_acquire(c) : nullptr;
   plonk::Armed helpers(pool);
   std::vector<int32_t> st;
-  PTRY_V(plonk::decode_points(v, comp.data(), 16, (uint32_t)(plonk::PC_COUNT * count), &st));
+  PTRY(plonk::decode_points(v, comp.data(), 16, (uint32_t)(plonk::PC_COUNT * count), &st));
   plonk::BatchState b;
   b.v = v;
   b.proofs = proofs;
@@ -818,7 +801,7 @@ int plonk_verify(plonk_verifier* vh, const uint8_t* proofs, const uint64_t* pi, 
   std::vector<uint32_t> which;
   for (uint64_t k = 0; k < count; ++k)
     if (b.ps[k].status == plonk::VS_OK) which.push_back((uint32_t)k);
-  PTRY_V(plonk::bisect(b, which, 0, which.size()));
+  PTRY(plonk::bisect(b, which, 0, which.size()));
   uint32_t rejected = 0;
   int rc = PLONK_OK;
   for (uint64_t k = 0; k < count; ++k) {
@@ -860,15 +843,15 @@ int plonk_test_verify_msm(plonk_ctx* ctx, const uint8_t* comp48, const uint32_t*
   HIP_TRY(hipSetDevice(ctx->c.device));
   plonk::Verifier v;
   v.c = &ctx->c;
-  PTRY_V(v.reserve((n + plonk::PC_COUNT - 1) / plonk::PC_COUNT));
+  PTRY(v.reserve((n + plonk::PC_COUNT - 1) / plonk::PC_COUNT));
   std::vector<int32_t> st;
-  PTRY_V(plonk::decode_points(&v, comp48, 16, (uint32_t)n, &st));
+  PTRY(plonk::decode_points(&v, comp48, 16, (uint32_t)n, &st));
   for (uint64_t i = 0; i < n; ++i)
     if (st[i] == plonk::VDEC_BAD) return (plonk::set_last_error(api_fn, "not a valid compressed point of G1", __FILE__, __LINE__), PLONK_ERR_POINT);
   std::vector<uint32_t> ids(n);
   for (uint64_t i = 0; i < n; ++i) ids[i] = (uint32_t)(16 + i);
   plonk::H1 sums[2];
-  PTRY_V(plonk::msm_device(&v, scalars, ids.data(), n, 0, sums));
+  PTRY(plonk::msm_device(&v, scalars, ids.data(), n, 0, sums));
   memset(out97, 0, 97);
   const plonk::G1Aff64 a = plonk::xyzz_to_aff(sums[0]);
   if (a.inf) { out97[96] = 1; return PLONK_OK; }
@@ -882,17 +865,17 @@ int plonk_verify_mixed(plonk_verifier* const* verifiers, uint32_t nverifiers, co
                        const uint64_t* pi, uint64_t pi_total, uint64_t count, int32_t* verdicts, plonk_verify_info* info) {
   const char* const api_fn = __func__;
   return plonk::api_guard(api_fn, [&]() -> int {
-  PTRY_V(plonk::mixed_args(api_fn, verifiers, nverifiers, circuit, proofs, pi, pi_total, count));
+  PTRY(plonk::mixed_args(api_fn, verifiers, nverifiers, circuit, proofs, pi, pi_total, count));
   if (count > 1 && !verdicts) return (plonk::set_last_error(api_fn, "invalid argument: verdicts is NULL and count > 1", __FILE__, __LINE__), PLONK_ERR_ARG);
   CTX_ENTER(verifiers[0]->ctx->c, api_fn);
   plonk::MixedState b;
   b.c = &verifiers[0]->ctx->c;
   HIP_TRY(hipSetDevice(b.c->device));
-  PTRY_V(plonk::mixed_front(b, verifiers, nverifiers, circuit, proofs, pi, pi_total, count));
+  PTRY(plonk::mixed_front(b, verifiers, nverifiers, circuit, proofs, pi, pi_total, count));
   std::vector<uint32_t> which;
   for (uint64_t k = 0; k < count; ++k)
     if (b.status[k] == plonk::VS_OK) which.push_back((uint32_t)k);
-  PTRY_V(plonk::mixed_bisect(b, which, 0, which.size()));
+  PTRY(plonk::mixed_bisect(b, which, 0, which.size()));
   uint32_t rejected = 0;
   int rc = PLONK_OK;
   for (uint64_t k = 0; k < count; ++k) {
@@ -927,7 +910,7 @@ int plonk_verify_each(plonk_verifier* const* verifiers, uint32_t nverifiers, con
   }
   if (!circuit && (count == 0 || count > (1ull << 24)))
     return (plonk::set_last_error(api_fn, "invalid argument: count must be in [1, 2^24]", __FILE__, __LINE__), PLONK_ERR_ARG);
-  PTRY_V(plonk::mixed_args(api_fn, verifiers, nverifiers, circuit, proofs, pi, pi_total, count));
+  PTRY(plonk::mixed_args(api_fn, verifiers, nverifiers, circuit, proofs, pi, pi_total, count));
   if (!verdicts) return (plonk::set_last_error(api_fn, "invalid argument: verdicts is NULL", __FILE__, __LINE__), PLONK_ERR_ARG);
   if (info) memset(info, 0, sizeof *info);
   CTX_ENTER(verifiers[0]->ctx->c, api_fn);
@@ -936,35 +919,35 @@ int plonk_verify_each(plonk_verifier* const* verifiers, uint32_t nverifiers, con
   Ctx* c = b.c;
   HIP_TRY(hipSetDevice(c->device));
   auto body = [&]() -> int {
-    PTRY_V(plonk::mixed_front(b, verifiers, nverifiers, circuit, proofs, pi, pi_total, count));
+    PTRY(plonk::mixed_front(b, verifiers, nverifiers, circuit, proofs, pi, pi_total, count));
     plonk::Verifier* v0 = verifiers[b.used[0]]->v;   // every verifier of the call has the same (g, h, x_h)
-    PTRY_V(plonk::pairing_tables_create(c, v0->x_h, v0->h, &v0->pair_tables));
+    PTRY(plonk::pairing_tables_create(c, v0->x_h, v0->h, &v0->pair_tables));
     plonk::MixedWork& w = *b.w;
     const uint64_t nterms = (uint64_t)plonk::VERIFY_EACH_TERMS * count;
-    PTRY_V(w.need(plonk::MixedWork::SC, 32 * nterms));
-    PTRY_V(w.need(plonk::MixedWork::IDS, 4 * nterms));
-    PTRY_V(w.need(plonk::MixedWork::E_PRE, 4 * count));
-    PTRY_V(w.need(plonk::MixedWork::E_SUMS, sizeof(G1) * 2 * count));
-    PTRY_V(w.need(plonk::MixedWork::E_VERDICT, 4 * count));
+    PTRY(w.need(plonk::MixedWork::SC, 32 * nterms));
+    PTRY(w.need(plonk::MixedWork::IDS, 4 * nterms));
+    PTRY(w.need(plonk::MixedWork::E_PRE, 4 * count));
+    PTRY(w.need(plonk::MixedWork::E_SUMS, sizeof(G1) * 2 * count));
+    PTRY(w.need(plonk::MixedWork::E_VERDICT, 4 * count));
     const auto t0 = std::chrono::steady_clock::now();
-    PTRY_V(plonk::verify_each_pack_launch(c, w.p[plonk::MixedWork::SCALARS], w.at<const uint32_t>(plonk::MixedWork::SLOT), b.pt_g,
+    PTRY(plonk::verify_each_pack_launch(c, w.p[plonk::MixedWork::SCALARS], w.at<const uint32_t>(plonk::MixedWork::SLOT), b.pt_g,
                                           b.pt_proof0, count, w.at<uint32_t>(plonk::MixedWork::SC), w.at<uint32_t>(plonk::MixedWork::IDS),
                                           w.at<int32_t>(plonk::MixedWork::E_PRE)));
     HIP_TRY(hipStreamSynchronize(c->stream));
     const double ms_pack = plonk::ms_since(t0);
     const auto t1 = std::chrono::steady_clock::now();
-    PTRY_V(plonk::each_sums_launch(c, w.at<const uint32_t>(plonk::MixedWork::SC), w.at<const uint32_t>(plonk::MixedWork::IDS), 2,
+    PTRY(plonk::each_sums_launch(c, w.at<const uint32_t>(plonk::MixedWork::SC), w.at<const uint32_t>(plonk::MixedWork::IDS), 2,
                                    plonk::VERIFY_EACH_TERMS - 2, count, w.at<const G1Affine>(plonk::MixedWork::PTS),
                                    w.at<const int32_t>(plonk::MixedWork::KIND), w.at<const int32_t>(plonk::MixedWork::E_PRE),
                                    w.at<G1>(plonk::MixedWork::E_SUMS)));
     HIP_TRY(hipStreamSynchronize(c->stream));
     const double ms_msm = plonk::ms_since(t1);
     const auto t2 = std::chrono::steady_clock::now();
-    PTRY_V(plonk::pairing_each_launch(c, v0->pair_tables, w.at<const G1>(plonk::MixedWork::E_SUMS),
+    PTRY(plonk::pairing_each_launch(c, v0->pair_tables, w.at<const G1>(plonk::MixedWork::E_SUMS),
                                       w.at<const int32_t>(plonk::MixedWork::E_PRE), count, w.at<int32_t>(plonk::MixedWork::E_VERDICT),
                                       nullptr));
     uint32_t checked = 0, rejected = 0;
-    PTRY_V(plonk::each_finish(c, w.at<const int32_t>(plonk::MixedWork::E_VERDICT), w.at<const int32_t>(plonk::MixedWork::E_PRE), count,
+    PTRY(plonk::each_finish(c, w.at<const int32_t>(plonk::MixedWork::E_VERDICT), w.at<const int32_t>(plonk::MixedWork::E_PRE), count,
                               verdicts, &checked, &rejected));
     if (info) {
       info->proofs = count;
@@ -995,13 +978,13 @@ int plonk_test_verify_replay(plonk_verifier* const* verifiers, uint32_t nverifie
                              uint32_t* scalars, uint8_t* digests) {
   const char* const api_fn = __func__;
   return plonk::api_guard(api_fn, [&]() -> int {
-  PTRY_V(plonk::mixed_args(api_fn, verifiers, nverifiers, circuit, proofs, pi, pi_total, count));
+  PTRY(plonk::mixed_args(api_fn, verifiers, nverifiers, circuit, proofs, pi, pi_total, count));
   if (!status || !scalars || !digests) return (plonk::set_last_error(api_fn, "invalid argument", __FILE__, __LINE__), PLONK_ERR_ARG);
   CTX_ENTER(verifiers[0]->ctx->c, api_fn);
   plonk::MixedState b;
   b.c = &verifiers[0]->ctx->c;
   HIP_TRY(hipSetDevice(b.c->device));
-  PTRY_V(plonk::mixed_front(b, verifiers, nverifiers, circuit, proofs, pi, pi_total, count));
+  PTRY(plonk::mixed_front(b, verifiers, nverifiers, circuit, proofs, pi, pi_total, count));
   std::vector<plonk::ProofScalars> ps(count);
   HIP_TRY(hipMemcpy(ps.data(), b.w->p[plonk::MixedWork::SCALARS], sizeof(plonk::ProofScalars) * count, hipMemcpyDeviceToHost));
   for (uint64_t k = 0; k < count; ++k) {

@@ -41,8 +41,7 @@ struct VerifierCore {
   void init_constants() {
     uint32_t L = 0;
     while ((1ull << L) < n) ++L;
-    omega = fr_root_of_unity();
-    for (uint32_t i = L; i < 32; ++i) omega = omega.sqr();
+    omega = fr_domain_root(L);
     n_inv = Fr::from_u64(n).inv();
     edwards_d = (fr_small(10240) * fr_small(10241).inv()).neg();   // dusk_jubjub::EDWARDS_D
     const Fr omega_inv = omega.inv();
