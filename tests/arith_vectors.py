@@ -6,7 +6,11 @@ Python integers only.  tests/test_field_host.py runs them through the g++ build 
 
 A family is a list of cases in a fixed order: the packed input record, and either the exact output record or a predicate on
 it (the raw Fp28 products promise a range and a residue, not a representative).  Cases are NOT grouped by kind: edge values
-sit beside random ones, so that the lanes of one wave take different paths."""
+sit beside random ones, so that the lanes of one wave take different paths.
+
+The pairing tower of pairing28.cuh (the last section) has a reference of its own, tests/pairing_tower_model.py, and two of
+its routines read the 47 KB PairingTables28: a family may name one blob of bytes (`shared`) that the harness turns into a
+read-only buffer once, before the cases run."""
 import functools
 import random
 import struct
@@ -329,6 +333,7 @@ class Family:
         self.inputs = []
         self.expect = []      # a tuple (the exact record) or a predicate on the unpacked record
         self.labels = []
+        self.shared = None    # bytes every case of the family reads beside its own record (handed over once, before the cases)
 
     def add(self, fields, expect, label=""):
         self.inputs.append(self.in_struct.pack(*fields))
@@ -374,6 +379,13 @@ class Family:
         for which, st in ((0, self.in_struct), (1, self.out_struct)):
             size = getattr(lib, f"{prefix}record_size_{self.name}")(which)
             assert size == st.size, (self.name, which, size, st.size)
+        if self.shared is not None:          # the harness turns the blob into its read-only buffer (the device twin uploads it)
+            share = getattr(lib, f"{prefix}shared_tables")
+            share.argtypes = [ctypes.c_char_p, ctypes.c_size_t]
+            share.restype = ctypes.c_int
+            rc = share(self.shared, len(self.shared))
+            if rc:
+                return rc, b""
         fn = getattr(lib, f"{prefix}case_{self.name}")
         fn.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int]
         fn.restype = ctypes.c_int
@@ -655,8 +667,443 @@ def _merlin():
     return f
 
 
+# ---- the pairing tower of pairing28.cuh against tests/pairing_tower_model.py ------------------------------------------------
+# Records are raw Fp28 limbs (14 words a coordinate, Montgomery with R' = 2^392); a raw value v stands for the residue
+# v / R'.  Every output coordinate must be normalised, below 2p (the header's contract) and of the model's residue.
+
+P28_RED, P28_ADD, P28_SUB, P28_NEG = range(4)
+F2R_ADD, F2R_SUB, F2R_NEG, F2R_CONJ, F2R_MUL_XI, F2R_MUL, F2R_SQR, F2R_MUL_FP, F2R_INV = range(9)
+F6R_ADD, F6R_SUB, F6R_NEG, F6R_MUL_V, F6R_MUL, F6R_INV, F6R_MUL_01, F6R_MUL_1 = range(8)
+F12R_MUL, F12R_SQR, F12R_CONJ, F12R_INV, F12R_MUL_014, F12R_MUL_LINE, F12R_MUL_LINE_GENERIC, F12R_IS_ONE, F12R_PUT = range(9)
+CYC_F4_SQR, CYC_SQR, CYC_POW_X = range(3)
+STAGE_AFF, STAGE_MILLER, STAGE_FINAL_EXP = range(3)
+PTOP = P >> (28 * 13)                   # p's top limb
+
+
+def mont28(x):
+    return x * FP28_R % P
+
+
+def res28(v):
+    return v * FP28_RINV % P
+
+
+@functools.lru_cache(None)
+def tower_coords():
+    """the operand class of one coordinate, as raw values below 2p: every residue in both representatives the contract
+    allows (x R' mod p, and that + p), the saturated-limb patterns, 2p - 1"""
+    rnd = random.Random(2800)
+    residues = [0, 1, 2, P - 1, P - 2, (P - 1) // 2] + [rnd.randrange(P) for _ in range(6)]
+    out = []
+    for x in residues:
+        out += [mont28(x), mont28(x) + P]
+    out += [value28(FP28_ONES)] + saturated_values(P, FP_VIEWS) + [2 * P - 1]
+    assert all(0 <= v < 2 * P for v in out)
+    return tuple(out)
+
+
+def _tm():
+    import pairing_tower_model as TM
+    return TM
+
+
+def _level(n):
+    """(nested model value of n residues, its residues, product, inverse, negation, conjugation or None) of Fp2 / Fp6 / Fp12"""
+    TM = _tm()
+    return {2: (tuple, list, TM.f2_mul, TM.f2_inv, TM.f2_neg, TM.f2_conj),
+            6: (TM.f6_of_coords, TM.f6_coords, TM.f6_mul, TM.f6_inv, TM.f6_neg, None),
+            12: (TM.f12_of_coords, TM.f12_coords, TM.f12_mul, TM.f12_inv, TM.f12_neg, TM.f12_conj)}[n]
+
+
+def tower_value(raw, n):
+    """the model's element for n raw coordinates"""
+    assert len(raw) == n
+    return _level(n)[0]([res28(v) for v in raw])
+
+
+def tower_raw(x, n, reps=0):
+    """raw coordinates of a model element: Montgomery form, coordinate i in its upper representative when bit i of reps is set"""
+    return [mont28(v) + (P if (reps >> i) & 1 else 0) for i, v in enumerate(_level(n)[1](x))]
+
+
+def tower_limbs(raw):
+    return [w for v in raw for w in limbs28(v)]
+
+
+@functools.lru_cache(None)
+def tower_elements(n):
+    """elements of n coordinates (2, 6, 12) as raw values: zero, one, one non-zero coordinate in each position, every
+    coordinate 2p - 1, the coordinate class dealt out n at a time (each of its values somewhere), and random ones"""
+    rnd = random.Random(2800 + n)
+    cs = list(tower_coords())
+    nonzero = [c for c in cs if c % P]
+    els = [[0] * n, [mont28(1)] + [0] * (n - 1), [2 * P - 1] * n]
+    for i in range(n):
+        els.append([0] * i + [nonzero[(5 * i + n) % len(nonzero)]] + [0] * (n - 1 - i))
+    deal = cs[:]
+    rnd.shuffle(deal)
+    for k in range(0, len(deal), n):
+        els.append([deal[(k + i) % len(deal)] for i in range(n)])
+    els += [[rnd.randrange(2 * P) for _ in range(n)] for _ in range(3)]
+    rnd.shuffle(els)                   # structured elements between random ones
+    return tuple(tuple(e) for e in els)
+
+
+@functools.lru_cache(None)
+def tower_mul_pairs(n):
+    """the operand pairs of the multiplicative routines beyond element x element: (x, x), (x, -x), (x, 1 / x) and, where the
+    level has one, (x, conj x) whose product lies in the field below; the second operand in mixed representatives"""
+    _, flat, _, inv, neg, conj = _level(n)
+    out = []
+    for j, x in enumerate(tower_elements(n)):
+        xm = tower_value(x, n)
+        out.append((x, x, "(x, x)"))
+        out.append((x, tuple(tower_raw(neg(xm), n, 0x555 * (j & 3))), "(x, -x)"))
+        if any(v % P for v in x):
+            out.append((x, tuple(tower_raw(inv(xm), n, 0xA5A >> (j % 5))), "(x, 1/x)"))
+        if conj:
+            out.append((x, tuple(tower_raw(conj(xm), n, j)), "(x, conj x)"))
+    return tuple(out)
+
+
+def tower_out(expect, offset=0):
+    """the predicate of an output of len(expect) coordinates from word `offset` of the record"""
+    expect = list(expect)
+
+    def check(rec, where):
+        for j, e in enumerate(expect):
+            ls = rec[offset + 14 * j:offset + 14 * j + 14]
+            assert all(x <= M28 for x in ls), ("coordinate not normalised", where, j)
+            v = value28(ls)
+            assert v < 2 * P, ("coordinate not below 2p", where, j)
+            assert res28(v) == e, ("wrong residue", where, j)
+    return check
+
+
+def _pick(seq, i, k):
+    """k entries of seq from a position that moves with i"""
+    return [seq[(7 * i + 3 * t) % len(seq)] for t in range(k)]
+
+
+def p28_red_inputs():
+    """normalised values below 64p around every threshold of the quotient estimate floor(top limb / (ptop + 1)), and around
+    multiples of p"""
+    vals = []
+    for q in range(64):
+        for top in (q * (PTOP + 1) - 1, q * (PTOP + 1), q * (PTOP + 1) + 1):
+            for low in (0, (1 << 364) - 1):
+                v = (top << 364) | low
+                if top >= 0 and v < 64 * P:
+                    vals.append(v)
+    for k in (1, 2, 4, 6, 63, 64):
+        vals += [v for v in (k * P - 1, k * P, k * P + 1) if v < 64 * P]
+    assert 64 * P - 1 in vals          # the largest normalised value of the range
+    return vals
+
+
+def _p28_red():
+    f = Family("p28_red", "I14I14I", "14I")
+    rnd = random.Random(2801)
+    cs = tower_coords()
+    z = [0] * 14
+    red = p28_red_inputs()
+    ends = [0, 2 * P - 1]              # both ends of the wrappers' operand range (normalised, below 2p)
+    pairs = [(a, b) for a in ends for b in ends] + [(a, b) for i, a in enumerate(cs) for b in _pick(cs, i, 2) + [ends[i & 1]]]
+    for i in range(max(len(red), len(pairs))):
+        if i < len(red):
+            f.add([P28_RED] + limbs28(red[i]) + z, tower_out([res28(red[i])]), "p28_red %x" % red[i])
+            v = rnd.randrange(64 * P)
+            f.add([P28_RED] + limbs28(v) + z, tower_out([res28(v)]), "p28_red random")
+        if i < len(pairs):
+            a, b = pairs[i]
+            f.add([P28_ADD] + limbs28(a) + limbs28(b), tower_out([res28(a + b)]), "p28_add")
+            f.add([P28_SUB] + limbs28(a) + limbs28(b), tower_out([res28(a - b)]), "p28_sub")
+            f.add([P28_NEG] + limbs28(a) + z, tower_out([res28(-a)]), "p28_neg")
+    # 64 quotients x 3 top limbs (q = 0 has no top limb below it) x 2 fillings of the low limbs, and 3 values around each of
+    # p, 2p, 4p, 6p, 63p and 64p less the two that are not below 64p: every one of them is below 64p and stays
+    assert len(f) == 2 * len(red) + 3 * len(pairs) and len(red) == (64 * 3 - 1) * 2 + (6 * 3 - 2)
+    return f
+
+
+def _f2r():
+    TM = _tm()
+    f = Family("f2r", "I28I28I14I", "28I")
+    els, cs = tower_elements(2), tower_coords()
+    z2, z1 = [0] * 28, [0] * 14
+    n0 = 0
+
+    def binary(op, x, y, fn, label):
+        f.add([op] + tower_limbs(x) + tower_limbs(y) + z1, tower_out(fn(tower_value(x, 2), tower_value(y, 2))), label)
+
+    for i, x in enumerate(els):
+        xm = tower_value(x, 2)
+        for y in _pick(els, i, 4):
+            binary(F2R_ADD, x, y, TM.f2_add, "add")
+            binary(F2R_MUL, x, y, TM.f2_mul, "mul")
+            binary(F2R_SUB, x, y, TM.f2_sub, "sub")
+        for op, fn, label in ((F2R_NEG, TM.f2_neg, "neg"), (F2R_CONJ, TM.f2_conj, "conj"), (F2R_MUL_XI, TM.f2_mul_xi, "mul_xi"), (F2R_SQR, TM.f2_sqr, "sqr")):
+            f.add([op] + tower_limbs(x) + z2 + z1, tower_out(fn(xm)), label)
+        for k in _pick(cs, i, 3):
+            f.add([F2R_MUL_FP] + tower_limbs(x) + z2 + limbs28(k), tower_out(TM.f2_mul_fp(xm, res28(k))), "mul_fp")
+        if any(v % P for v in x):          # the inverse of 0 is not specified
+            f.add([F2R_INV] + tower_limbs(x) + z2 + z1, tower_out(TM.f2_inv(xm)), "inv")
+            n0 += 1
+    # a^2 + b^2 with one of the two zero, in either representative of zero
+    one_zero = [(c, zero) for c in _pick([c for c in cs if c % P], 1, 6) for zero in (0, P)]
+    for a, zero in one_zero:
+        for x in ((a, zero), (zero, a)):
+            f.add([F2R_INV] + tower_limbs(x) + z2 + z1, tower_out(TM.f2_inv(tower_value(x, 2))), "inv, one coordinate zero")
+    pairs = tower_mul_pairs(2)
+    for x, y, label in pairs:
+        binary(F2R_MUL, x, y, TM.f2_mul, "mul " + label)
+        binary(F2R_ADD, x, y, TM.f2_add, "add " + label)
+        binary(F2R_SUB, x, y, TM.f2_sub, "sub " + label)
+    assert len(f) == len(els) * (12 + 4 + 3) + n0 + 2 * len(one_zero) + 3 * len(pairs) and n0 >= len(els) - 3
+    return f
+
+
+def _f6r():
+    TM = _tm()
+    f = Family("f6r", "II84I84I28I28I", "84I")
+    els, e2 = tower_elements(6), tower_elements(2)
+    z6, z2 = [0] * 84, [0] * 28
+    n0 = 0
+
+    def case(op, alias, x, y, a0, a1, want, label):
+        f.add([op, alias] + tower_limbs(x) + (tower_limbs(y) if y else z6) + (tower_limbs(a0) if a0 else z2) + (tower_limbs(a1) if a1 else z2),
+              tower_out(TM.f6_coords(want)), label + (" r == x", " r == y")[alias - 1] * (alias > 0))
+
+    for i, x in enumerate(els):
+        xm = tower_value(x, 6)
+        for t, y in enumerate(_pick(els, i, 3)):
+            ym = tower_value(y, 6)
+            case(F6R_MUL, (i + t) % 3, x, y, None, None, TM.f6_mul(xm, ym), "mul")
+            case(F6R_ADD, (i + t) & 1, x, y, None, None, TM.f6_add(xm, ym), "add")      # in place as f12r_mul calls them
+            case(F6R_SUB, (i + t + 1) & 1, x, y, None, None, TM.f6_sub(xm, ym), "sub")
+        case(F6R_NEG, 0, x, None, None, None, TM.f6_neg(xm), "neg")
+        case(F6R_MUL_V, i & 1, x, None, None, None, TM.f6_mul_v(xm), "mul_v")
+        for t, (a0, a1) in enumerate(zip(_pick(e2, i, 2), _pick(e2, i + 1, 2))):
+            am0, am1 = tower_value(a0, 2), tower_value(a1, 2)
+            case(F6R_MUL_01, (i + t) & 1, x, None, a0, a1, TM.f6_mul(xm, (am0, am1, TM.F2_ZERO)), "mul_01")
+            case(F6R_MUL_1, (i + t + 1) & 1, x, None, None, a1, TM.f6_mul(xm, (TM.F2_ZERO, am1, TM.F2_ZERO)), "mul_1")
+        if any(v % P for v in x):
+            case(F6R_INV, i & 1, x, None, None, None, TM.f6_inv(xm), "inv")                # in place as f12r_inv calls it
+            n0 += 1
+    pairs = tower_mul_pairs(6)
+    for j, (x, y, label) in enumerate(pairs):
+        case(F6R_MUL, j % 3, x, y, None, None, TM.f6_mul(tower_value(x, 6), tower_value(y, 6)), "mul " + label)
+    assert len(f) == len(els) * (9 + 2 + 4) + n0 + len(pairs) and n0 >= len(els) - 2
+    return f
+
+
+def _f12r_expect(residues, flag=0, put=None):
+    coords = tower_out(residues, 1)
+    put = list(put) if put else [0] * 144
+
+    def check(rec, where):
+        assert rec[0] == flag, ("flag", where)
+        coords(rec, where)
+        assert list(rec[169:]) == put, ("f12r_put", where)
+    return check
+
+
+def _f12r():
+    TM = _tm()
+    f = Family("f12r", "II168I168I84I14I14I", "I168I144I")
+    els, e2, cs = tower_elements(12), tower_elements(2), tower_coords()
+    z12, z3, z1 = [0] * 168, [0] * 84, [0] * 14
+    n0 = 0
+
+    def case(op, alias, x, y, want, label, line=None, px=0, py=0, flag=0, put=None):
+        ll = tower_limbs([c for c2 in line for c in c2]) if line else z3
+        f.add([op, alias] + tower_limbs(x) + (tower_limbs(y) if y else z12) + ll + limbs28(px) + limbs28(py),
+              _f12r_expect(TM.f12_coords(want), flag, put), label + (" r == x", " r == y")[alias - 1] * (alias > 0))
+
+    for i, x in enumerate(els):
+        xm = tower_value(x, 12)
+        for t, y in enumerate(_pick(els, i, 3)):
+            case(F12R_MUL, (i + t) % 3, x, y, TM.f12_mul(xm, tower_value(y, 12)), "mul")
+        case(F12R_SQR, i & 1, x, None, TM.f12_sqr(xm), "sqr")
+        case(F12R_CONJ, (i + 1) & 1, x, None, TM.f12_conj(xm), "conj")
+        if any(v % P for v in x):
+            case(F12R_INV, i & 1, x, None, TM.f12_inv(xm), "inv")
+            n0 += 1
+        # the sparse products against the model's DENSE product of the line element
+        for t in range(2):
+            line = _pick(e2, 3 * i + t, 3)
+            a0, a1, b1 = (tower_value(c, 2) for c in line)
+            case(F12R_MUL_014, (i + t) & 1, x, None, TM.f12_mul(xm, TM.sparse_014(a0, a1, b1)), "mul_014", line)
+            px, py = _pick(cs, 2 * i + t, 2)
+            want = TM.f12_mul(xm, TM.line_element(a0, a1, b1, res28(px), res28(py)))
+            case(F12R_MUL_LINE, 1, x, None, want, "mul_line", line, px, py)
+            case(F12R_MUL_LINE_GENERIC, 1, x, None, want, "mul_line_generic", line, px, py)
+        case(F12R_IS_ONE, 1, x, None, xm, "is_one", flag=1 if xm == TM.F12_ONE else 0)
+        case(F12R_PUT, 1, x, None, xm, "put", put=[w for c in TM.f12_coords(xm) for w in words(c, 12)])
+    pairs = tower_mul_pairs(12)
+    for j, (x, y, label) in enumerate(pairs):
+        case(F12R_MUL, j % 3, x, y, TM.f12_mul(tower_value(x, 12), tower_value(y, 12)), "mul " + label)
+    # is_one: 1 in both representatives, 1 with one coordinate stored as p, 1 with one other coordinate not 0 modulo p
+    one = [mont28(1)] + [0] * 11
+    ones = [(one, 1), ([mont28(1) + P] + [0] * 11, 1), ([1] + [0] * 11, 0), ([mont28(2)] + [0] * 11, 0), ([mont28(1) + 1] + [0] * 11, 0)]
+    for i in range(12):
+        ones.append((one[:i] + [one[i] + P] + one[i + 1:], 1))
+        if i:
+            ones.append((one[:i] + [(1, P - 1, P + 1, mont28(1), 2 * P - 1)[i % 5]] + one[i + 1:], 0))
+    for x, flag in ones:
+        case(F12R_IS_ONE, 1, x, None, tower_value(x, 12), "is_one: 1 and its neighbours", flag=flag)
+    assert len(f) == len(els) * (3 + 2 + 6 + 2) + n0 + len(pairs) + len(ones) and n0 >= len(els) - 1 and len(ones) == 5 + 12 + 11
+    return f
+
+
+@functools.lru_cache(None)
+def pairing_shared_blob():
+    """the compressed x_h || h of tests/kzg_ref.py, from which the harness fills the PairingTables28 the table families read"""
+    import g2_ref as G2
+    import kzg_ref as K
+    return G2.g2_compress(G2.g2_mul(G2.G2_GEN, K.TAU)) + G2.g2_compress(G2.G2_GEN)
+
+
+def _f12r_frob():
+    """expected values: the model's x^(p^k) as a power, never a table"""
+    TM = _tm()
+    f = Family("f12r_frob", "II168I", "168I")
+    f.shared = pairing_shared_blob()
+    els = tower_elements(12)
+    n = len(els[0])
+    structured = [e for e in els if sum(1 for v in e if v) == 1]
+    sel = [[mont28(1)] + [0] * 11, structured[0], structured[7], [2 * P - 1] * 12] + [e for e in els if all(v not in (0, 2 * P - 1) for v in e)][:3]
+    assert n == 12 and len(sel) == 7
+    for i, x in enumerate(sel):
+        for k in (1, 2, 3):
+            alias = (i + k) & 1
+            f.add([k, alias] + tower_limbs(x), tower_out(TM.f12_coords(TM.frobenius(tower_value(x, 12), k))), "frob %d%s" % (k, " r == x" * alias))
+    assert len(f) == 21
+    return f
+
+
+@functools.lru_cache(None)
+def cyclotomic_elements():
+    """(raw element, model element) of the cyclotomic subgroup: edge and random elements mapped there BY THE MODEL, their
+    conjugates, and 1; the raw forms in mixed representatives"""
+    TM = _tm()
+    els = tower_elements(12)
+    src = [e for e in els if sum(1 for v in e if v) == 1][:2] + [[2 * P - 1] * 12] + [e for e in els if all(v not in (0, 2 * P - 1) for v in e)][:3]
+    out = [([mont28(1)] + [0] * 11, TM.F12_ONE), ([mont28(1) + P] + [P] * 11, TM.F12_ONE)]
+    for j, x in enumerate(src):
+        m = TM.to_cyclotomic(tower_value(x, 12))
+        assert TM.f12_mul(m, TM.f12_conj(m)) == TM.F12_ONE
+        out.append((tower_raw(m, 12, 0x3C5 * j), m))
+        out.append((tower_raw(TM.f12_conj(m), 12, 0xC3A >> j), TM.f12_conj(m)))
+    return tuple(out)
+
+
+def _f12r_cyc():
+    TM = _tm()
+    f = Family("f12r_cyc", "II168I", "168I")
+    e2 = tower_elements(2)
+    cyc = cyclotomic_elements()
+    pow_cases = [cyc[0], cyc[2], cyc[3], cyc[-2]]                     # 1, m and conj(m), one more
+    for i in range(max(len(e2), len(cyc))):
+        if i < len(e2):
+            for b in _pick(e2, i, 2) + [e2[i]]:
+                c0, c1 = TM.f4_sqr(tower_value(e2[i], 2), tower_value(b, 2))
+                f.add([CYC_F4_SQR, 0] + tower_limbs(e2[i]) + tower_limbs(b) + [0] * 112,
+                      tower_out(list(c0) + list(c1) + [0] * 8), "f4r_sqr")      # the case body zeroes the rest
+        if i < len(cyc):
+            x, m = cyc[i]
+            f.add([CYC_SQR, i & 1] + tower_limbs(x), tower_out(TM.f12_coords(TM.f12_mul(m, m))), "cyc_sqr" + " in place" * (i & 1))
+            f.add([CYC_SQR, (i + 1) & 1] + tower_limbs(x), tower_out(TM.f12_coords(TM.f12_mul(m, m))), "cyc_sqr" + " in place" * ((i + 1) & 1))
+        if i < len(pow_cases):
+            x, m = pow_cases[i]
+            f.add([CYC_POW_X, 0] + tower_limbs(x), tower_out(TM.f12_coords(TM.cyc_pow_x(m))), "cyc_pow_x_28")
+    assert len(f) == 3 * len(e2) + 2 * len(cyc) + 4 and len(cyc) == 14
+    return f
+
+
+@functools.lru_cache(None)
+def pairing_stage_points():
+    """the G1 pairs (a, b) of the Miller cases: two random, one of KZG shape (e(a, x_h) e(b, h) = 1), every identity placement"""
+    import kzg_ref as K
+    rnd = random.Random(2807)
+    g = lambda k: E.g1_mul(E.G1_GEN, k % Q)      # noqa: E731
+    r = rnd.randrange(1, Q)
+    return ((g(rnd.randrange(1, Q)), g(rnd.randrange(1, Q))), (g(-r), g(r * K.TAU)), (None, g(rnd.randrange(1, Q))),
+            (g(rnd.randrange(1, Q)), g(rnd.randrange(1, Q))), (g(rnd.randrange(1, Q)), None), (None, None))
+
+
+def _pairing_stages():
+    """The Miller value is compared AFTER the final exponentiation: the model's final exponentiation of the product's Miller
+    output against the model's final exponentiation of the product of its own two Miller loops (the prepared lines of the
+    product are scaled by factors the final exponentiation removes, which the model does not reproduce)."""
+    import g2_ref as G2
+    import kzg_ref as K
+    TM = _tm()
+    f = Family("pairing_stages", "II48I28II28II168I", "I168I")
+    f.shared = pairing_shared_blob()
+    rnd = random.Random(2808)
+    xh = G2.g2_mul(G2.G2_GEN, K.TAU)
+    zg1, zaff, z12 = [0] * 48, [0] * 28, [0] * 168
+
+    def aff_out(inf, x, y):
+        coords = tower_out([x, y] + [0] * 10, 1)
+
+        def check(rec, where):
+            assert rec[0] == inf, ("inf", where)
+            coords(rec, where)
+        return check
+
+    def miller_out(a, b):
+        want = TM.final_exponentiation(TM.f12_mul(TM.miller_loop(a, xh), TM.miller_loop(b, G2.G2_GEN)))
+
+        def check(rec, where):
+            got = []
+            for j in range(12):
+                ls = rec[1 + 14 * j:15 + 14 * j]
+                assert all(x <= M28 for x in ls) and value28(ls) < 2 * P, ("coordinate not normalised or not below 2p", where, j)
+                got.append(res28(value28(ls)))
+            assert TM.final_exponentiation(TM.f12_of_coords(got)) == want, ("Miller value after the final exponentiation", where)
+        return check
+
+    def aff28(pt, reps):
+        return zaff + [1] if pt is None else limbs28(mont28(pt[0]) + P * (reps & 1)) + limbs28(mont28(pt[1]) + P * (reps >> 1)) + [0]
+
+    # XYZZ points with ZZ != 1: (x zz, y zzz, zz, zzz), zz = z^2, zzz = z^3; and the identity (ZZ = 0)
+    pt = E.g1_mul(E.G1_GEN, rnd.randrange(1, Q))
+    xyzz = []
+    for z in (1, 2, P - 1, rnd.randrange(2, P), rnd.randrange(2, P)):
+        zz, zzz = z * z % P, z * z * z % P
+        xyzz.append((fp_mont(pt[0] * zz % P) + fp_mont(pt[1] * zzz % P) + fp_mont(zz) + fp_mont(zzz), aff_out(0, pt[0], pt[1]), "g1aff28_of_g1 z = %x" % z))
+    xyzz.append((fp_mont(1) + fp_mont(1) + [0] * 24, aff_out(1, 0, 0), "g1aff28_of_g1 identity"))
+    units = [TM.f12_of_coords(rnd.randrange(P) for _ in range(12)) for _ in range(2)]
+    finals = [(tower_raw(units[0], 12, 0), units[0], 0), ([mont28(1)] + [0] * 11, TM.F12_ONE, 1), (tower_raw(units[1], 12, 0xB6D), units[1], 1),
+              ([mont28(1) + P] + [P] * 11, TM.F12_ONE, 0)]
+    millers = pairing_stage_points()
+    for i in range(6):                     # the stages side by side in the wave
+        g1, want, label = xyzz[i]
+        f.add([STAGE_AFF, 0] + g1 + zaff + [0] + zaff + [0] + z12, want, label)
+        a, b = millers[i]
+        f.add([STAGE_MILLER, 0] + zg1 + aff28(a, i) + aff28(b, i >> 1) + z12, miller_out(a, b),
+              "miller2_28 a %s, b %s" % ("identity" if a is None else "finite", "identity" if b is None else "finite"))
+        if i < len(finals):
+            x, xm, alias = finals[i]
+            f.add([STAGE_FINAL_EXP, alias] + zg1 + zaff + [0] + zaff + [0] + tower_limbs(x),
+                  _stage_final(TM.f12_coords(TM.final_exponentiation(xm))), "final_exponentiation_28" + " in place" * alias)
+    assert len(f) == 6 + 6 + 4
+    return f
+
+
+def _stage_final(residues):
+    coords = tower_out(residues, 1)
+
+    def check(rec, where):
+        assert rec[0] == 0, ("inf", where)
+        coords(rec, where)
+    return check
+
+
 _BUILDERS = {"fr": _fr, "fp": _fp, "g1": _g1, "g1_full": _g1_full, "fp28": _fp28, "fp28_raw": _fp28_raw, "g1r": _g1r, "glv": _glv, "fr29": _fr29,
-             "safegcd": _safegcd, "decompress": _decompress, "recode": _recode, "merlin": _merlin}
+             "safegcd": _safegcd, "decompress": _decompress, "recode": _recode, "merlin": _merlin, "p28_red": _p28_red, "f2r": _f2r, "f6r": _f6r,
+             "f12r": _f12r, "f12r_frob": _f12r_frob, "f12r_cyc": _f12r_cyc, "pairing_stages": _pairing_stages}
 FAMILIES = tuple(_BUILDERS)
 
 

@@ -414,6 +414,223 @@ HD void case_merlin(const MerlinIn&, MerlinOut& out) {
   for (int i = 0; i < 32; ++i) out.challenge[i] = c[i];
 }
 
+// ---- the pairing tower over Fp28 (pairing28.cuh) ------------------------------------------------------------------------
+// Raw limbs in and out: 14 words per coordinate (Montgomery, R = 2^392), 2 coordinates per Fp2, 6 per Fp6, 12 per Fp12 in
+// the order of the structs.  Compiled only into the PAIRING object of the device twin (the group is named on its command
+// line) and into the host twin: the header brings hostpairing.hpp with it, which the other objects need not parse.
+#if !defined(ARITH_GROUP) || defined(ARITH_GROUP_PAIRING)
+}  // namespace arith
+#include "../../plonk_amd/csrc/pairing28.cuh"
+namespace arith {
+#define ARITH_HAS_PAIRING 1
+
+// The one shared read-only buffer of the families that read the tables (Frobenius constants, prepared lines of x_h and
+// h): filled once by <prefix>shared_tables of the harness; the case bodies find it here, so that every family keeps the
+// two-argument body the runners expand.
+static const PairingTables28* h_pairing_tables = nullptr;
+#if defined(__HIPCC__)
+static __device__ const PairingTables28* d_pairing_tables = nullptr;
+#endif
+HD const PairingTables28* pairing_tables() {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return d_pairing_tables;
+#else
+  return h_pairing_tables;
+#endif
+}
+
+HD F2r ld_f2r(const uint32_t* w) { return {ld_fp28(w), ld_fp28(w + 14)}; }
+HD void st_f2r(uint32_t* w, const F2r& x) {
+  st_fp28(w, x.a);
+  st_fp28(w + 14, x.b);
+}
+// n Fp2 coefficients of an Fp6 (3) or Fp12 (6), which the structs hold back to back
+HD void ld_f2rs(F2r* c, const uint32_t* w, int n) {
+  for (int i = 0; i < n; ++i) c[i] = ld_f2r(w + 28 * i);
+}
+HD void st_f2rs(uint32_t* w, const F2r* c, int n) {
+  for (int i = 0; i < n; ++i) st_f2r(w + 28 * i, c[i]);
+}
+HD void zero_words(uint32_t* w, int n) {
+  for (int i = 0; i < n; ++i) w[i] = 0;
+}
+
+enum : uint32_t { P28_RED = 0, P28_ADD, P28_SUB, P28_NEG };
+struct P28RedIn { uint32_t op, a[14], b[14]; };
+struct P28RedOut { uint32_t r[14]; };
+HD void case_p28_red(const P28RedIn& in, P28RedOut& out) {
+  const Fp28 a = ld_fp28(in.a), b = ld_fp28(in.b);
+  Fp28 r = Fp28::zero();
+  switch (in.op) {
+    case P28_RED: r = p28_red(a); break;
+    case P28_ADD: r = p28_add(a, b); break;
+    case P28_SUB: r = p28_sub(a, b); break;
+    case P28_NEG: r = p28_neg(a); break;
+  }
+  st_fp28(out.r, r);
+}
+
+enum : uint32_t { F2R_ADD = 0, F2R_SUB, F2R_NEG, F2R_CONJ, F2R_MUL_XI, F2R_MUL, F2R_SQR, F2R_MUL_FP, F2R_INV };
+struct F2rIn { uint32_t op, x[28], y[28], k[14]; };
+struct F2rOut { uint32_t r[28]; };
+HD void case_f2r(const F2rIn& in, F2rOut& out) {
+  const F2r x = ld_f2r(in.x), y = ld_f2r(in.y);
+  F2r r = f2r_zero();
+  switch (in.op) {
+    case F2R_ADD: r = f2r_add(x, y); break;
+    case F2R_SUB: r = f2r_sub(x, y); break;
+    case F2R_NEG: r = f2r_neg(x); break;
+    case F2R_CONJ: r = f2r_conj(x); break;
+    case F2R_MUL_XI: r = f2r_mul_xi(x); break;
+    case F2R_MUL: r = f2r_mul(x, y); break;
+    case F2R_SQR: r = f2r_sqr(x); break;
+    case F2R_MUL_FP: r = f2r_mul_fp(x, ld_fp28(in.k)); break;
+    case F2R_INV: r = f2r_inv(x); break;
+  }
+  st_f2r(out.r, r);
+}
+
+// alias: 0 = the result in an object of its own, 1 = r == x, 2 = r == y (the aliasing the header's comments allow)
+enum : uint32_t { F6R_ADD = 0, F6R_SUB, F6R_NEG, F6R_MUL_V, F6R_MUL, F6R_INV, F6R_MUL_01, F6R_MUL_1 };
+struct F6rIn { uint32_t op, alias, x[84], y[84], a0[28], a1[28]; };
+struct F6rOut { uint32_t r[84]; };
+HD void case_f6r(const F6rIn& in, F6rOut& out) {
+  F6r x, y, sep;
+  ld_f2rs(&x.c0, in.x, 3);
+  ld_f2rs(&y.c0, in.y, 3);
+  ld_f2rs(&sep.c0, in.x, 3);
+  const F2r a0 = ld_f2r(in.a0), a1 = ld_f2r(in.a1);
+  F6r* r = in.alias == 1 ? &x : in.alias == 2 ? &y : &sep;
+  switch (in.op) {
+    case F6R_ADD: f6r_add(r, &x, &y); break;
+    case F6R_SUB: f6r_sub(r, &x, &y); break;
+    case F6R_NEG: f6r_neg(r, &x); break;
+    case F6R_MUL_V: f6r_mul_v(r, &x); break;
+    case F6R_MUL: f6r_mul(r, &x, &y); break;
+    case F6R_INV: f6r_inv(r, &x); break;
+    case F6R_MUL_01: f6r_mul_01(r, &x, &a0, &a1); break;
+    case F6R_MUL_1: f6r_mul_1(r, &x, &a1); break;
+  }
+  st_f2rs(out.r, &r->c0, 3);
+}
+
+// l = three Fp2 coefficients: (a0, a1, b1) of f12r_mul_014, (c0, c1, c2) of a line; flag = f12r_is_one, put = f12r_put
+enum : uint32_t { F12R_MUL = 0, F12R_SQR, F12R_CONJ, F12R_INV, F12R_MUL_014, F12R_MUL_LINE, F12R_MUL_LINE_GENERIC, F12R_IS_ONE, F12R_PUT };
+struct F12rIn { uint32_t op, alias, x[168], y[168], l[84], px[14], py[14]; };
+struct F12rOut { uint32_t flag, r[168], put[144]; };
+HD void case_f12r(const F12rIn& in, F12rOut& out) {
+  F12r x, y, sep;
+  ld_f2rs(&x.c0.c0, in.x, 6);
+  ld_f2rs(&y.c0.c0, in.y, 6);
+  ld_f2rs(&sep.c0.c0, in.x, 6);
+  Line28 l;
+  ld_f2rs(&l.c0, in.l, 3);
+  const Fp28 px = ld_fp28(in.px), py = ld_fp28(in.py);
+  F12r* r = in.alias == 1 ? &x : in.alias == 2 ? &y : &sep;
+  out.flag = 0;
+  zero_words(out.put, 144);
+  switch (in.op) {
+    case F12R_MUL: f12r_mul(r, &x, &y); break;
+    case F12R_SQR: f12r_sqr(r, &x); break;
+    case F12R_CONJ: f12r_conj(r, &x); break;
+    case F12R_INV: f12r_inv(r, &x); break;
+    case F12R_MUL_014: f12r_mul_014(r, &x, &l.c0, &l.c1, &l.c2); break;
+    case F12R_MUL_LINE: r = &x; f12r_mul_line(r, &l, &px, &py); break;                    // in place by its signature
+    case F12R_MUL_LINE_GENERIC: r = &x; f12r_mul_line_generic(r, &l, &px, &py); break;
+    case F12R_IS_ONE: r = &x; out.flag = f12r_is_one(&x) ? 1u : 0u; break;
+    case F12R_PUT: {
+      uint64_t w[72];
+      r = &x;
+      f12r_put(&x, w);
+      for (int i = 0; i < 72; ++i) {
+        out.put[2 * i] = (uint32_t)w[i];
+        out.put[2 * i + 1] = (uint32_t)(w[i] >> 32);
+      }
+      break;
+    }
+  }
+  st_f2rs(out.r, &r->c0.c0, 6);
+}
+
+struct F12rFrobIn { uint32_t k, alias, x[168]; };
+struct F12rFrobOut { uint32_t r[168]; };
+HD void case_f12r_frob(const F12rFrobIn& in, F12rFrobOut& out) {
+  F12r x, sep;
+  ld_f2rs(&x.c0.c0, in.x, 6);
+  ld_f2rs(&sep.c0.c0, in.x, 6);
+  F12r* r = in.alias == 1 ? &x : &sep;
+  f12r_frob(r, &x, (int)in.k, pairing_tables());
+  st_f2rs(out.r, &r->c0.c0, 6);
+}
+
+// F4_SQR: x holds a, b (56 words), r gets c0, c1; the other two take an element of the cyclotomic subgroup
+enum : uint32_t { CYC_F4_SQR = 0, CYC_SQR, CYC_POW_X };
+struct F12rCycIn { uint32_t op, alias, x[168]; };
+struct F12rCycOut { uint32_t r[168]; };
+HD void case_f12r_cyc(const F12rCycIn& in, F12rCycOut& out) {
+  F12r x, sep;
+  ld_f2rs(&x.c0.c0, in.x, 6);
+  ld_f2rs(&sep.c0.c0, in.x, 6);
+  F12r* r = in.alias == 1 ? &x : &sep;
+  switch (in.op) {
+    case CYC_F4_SQR: {
+      F2r c0, c1;
+      f4r_sqr(x.c0.c0, x.c0.c1, &c0, &c1);
+      r = &sep;
+      f12r_set_one(r);
+      r->c0.c0 = c0;
+      r->c0.c1 = c1;
+      break;
+    }
+    case CYC_SQR: f12r_cyc_sqr(r, &x); break;
+    case CYC_POW_X: r = &sep; cyc_pow_x_28(r, &x); break;   // r must not be f
+  }
+  st_f2rs(out.r, &r->c0.c0, 6);
+}
+
+// AFF: g1 = X, Y, ZZ, ZZZ (4 x 12 words, R = 2^384) -> inf, r[0..27] = x, y; MILLER: the affine points a, b (x, y, inf)
+// -> r = miller2_28; FINAL_EXP: x -> r (alias 1: in place)
+enum : uint32_t { STAGE_AFF = 0, STAGE_MILLER, STAGE_FINAL_EXP };
+struct PairingStagesIn { uint32_t op, alias, g1[48], a[28], a_inf, b[28], b_inf, x[168]; };
+struct PairingStagesOut { uint32_t inf, r[168]; };
+HD void case_pairing_stages(const PairingStagesIn& in, PairingStagesOut& out) {
+  F12r x, sep;
+  f12r_set_one(&sep);
+  F12r* r = &sep;
+  out.inf = 0;
+  switch (in.op) {
+    case STAGE_AFF: {
+      G1 p;
+      p.X = ld_fp(in.g1);
+      p.Y = ld_fp(in.g1 + 12);
+      p.ZZ = ld_fp(in.g1 + 24);
+      p.ZZZ = ld_fp(in.g1 + 36);
+      const G1Aff28 a = g1aff28_of_g1(p);
+      out.inf = a.inf;
+      sep.c0.c0 = F2r{a.x, a.y};
+      break;
+    }
+    case STAGE_MILLER: {
+      G1Aff28 a, b;
+      a.x = ld_fp28(in.a);
+      a.y = ld_fp28(in.a + 14);
+      a.inf = in.a_inf;
+      b.x = ld_fp28(in.b);
+      b.y = ld_fp28(in.b + 14);
+      b.inf = in.b_inf;
+      miller2_28(r, pairing_tables(), &a, &b);
+      break;
+    }
+    case STAGE_FINAL_EXP:
+      ld_f2rs(&x.c0.c0, in.x, 6);
+      if (in.alias == 1) r = &x;
+      final_exponentiation_28(r, &x, pairing_tables());
+      break;
+  }
+  st_f2rs(out.r, &r->c0.c0, 6);
+}
+#endif   // the pairing tower
+
 }  // namespace arith
 
 // Every family, once: X(name, input record, output record).  Both back ends expand this list into their runners
@@ -439,6 +656,14 @@ HD void case_merlin(const MerlinIn&, MerlinOut& out) {
   X(decompress, DecompressIn, DecompressOut) \
   X(recode, RecodeIn, RecodeOut)             \
   X(merlin, MerlinIn, MerlinOut)
+#define ARITH_FAMILIES_PAIRING(X)         \
+  X(p28_red, P28RedIn, P28RedOut)         \
+  X(f2r, F2rIn, F2rOut)                   \
+  X(f6r, F6rIn, F6rOut)                   \
+  X(f12r, F12rIn, F12rOut)                \
+  X(f12r_frob, F12rFrobIn, F12rFrobOut)   \
+  X(f12r_cyc, F12rCycIn, F12rCycOut)      \
+  X(pairing_stages, PairingStagesIn, PairingStagesOut)
 #define ARITH_FAMILIES(X)   \
   ARITH_FAMILIES_FIELD(X)   \
   ARITH_FAMILIES_G1(X)      \
@@ -446,4 +671,5 @@ HD void case_merlin(const MerlinIn&, MerlinOut& out) {
   ARITH_FAMILIES_G1R(X)     \
   ARITH_FAMILIES_GLV(X)     \
   ARITH_FAMILIES_INVERSE(X) \
-  ARITH_FAMILIES_CODEC(X)
+  ARITH_FAMILIES_CODEC(X)   \
+  ARITH_FAMILIES_PAIRING(X)

@@ -4,6 +4,7 @@
 // paths run divergently).  d_case_<family> copies in, launches, copies out and frees; it returns 0 or the first failing
 // HIP code (-1: the byte counts do not match n records).  Test code only.
 #include <hip/hip_runtime.h>
+#include <cstring>
 #include "arith_cases.hpp"
 
 namespace {
@@ -51,3 +52,33 @@ int run_family(const void* in, size_t in_bytes, void* out, size_t out_bytes, int
 #define ARITH_GROUP ARITH_FAMILIES
 #endif
 ARITH_GROUP(DEV_FAMILY)
+
+#ifdef ARITH_HAS_PAIRING
+// The shared buffer of the families that read PairingTables28 (their kernels are in this object, and so is the pointer
+// they read it through): blob = the compressed x_h || h, prepared and converted on the host by the product's
+// pairing_tables_fill, uploaded once and kept for the life of the process.  0, a HIP code, or a negative code for a bad blob.
+extern "C" int d_shared_tables(const void* blob, size_t bytes) {
+  using namespace plonk;
+  static PairingTables28 T;
+  static PairingTables28* dT = nullptr;
+  static uint8_t have[192];
+  if (bytes != sizeof have) return -1;
+  if (dT && memcmp(have, blob, sizeof have) == 0) return 0;
+  const uint8_t* b = (const uint8_t*)blob;
+  if (!g2_compressed_valid(b) || !g2_compressed_valid(b + 96)) return -3;
+  if (!pairing_tables_fill(g2_prepare(g2_decode_valid(b)), g2_prepare(g2_decode_valid(b + 96)), &T)) return -4;
+  PairingTables28* fresh = nullptr;
+  hipError_t rc = hipMalloc((void**)&fresh, sizeof T);
+  if (rc == hipSuccess) rc = hipMemcpy(fresh, &T, sizeof T, hipMemcpyHostToDevice);
+  const PairingTables28* ptr = fresh;
+  if (rc == hipSuccess) rc = hipMemcpyToSymbol(HIP_SYMBOL(arith::d_pairing_tables), &ptr, sizeof ptr);
+  if (rc != hipSuccess) {
+    if (fresh) (void)hipFree(fresh);
+    return (int)rc;
+  }
+  if (dT) (void)hipFree(dT);
+  dT = fresh;
+  memcpy(have, blob, sizeof have);
+  return 0;
+}
+#endif

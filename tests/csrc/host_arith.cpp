@@ -23,6 +23,23 @@ using namespace arith;
   extern "C" int h_record_size_##name(int which) { return (int)(which ? sizeof(Out) : sizeof(In)); }
 ARITH_FAMILIES(HOST_FAMILY)
 
+// The shared buffer of the families that read PairingTables28: blob = the compressed x_h || h (2 x 96 bytes), prepared
+// and converted once by the product's pairing_tables_fill.  0, or a negative code for a blob that is not two G2 points.
+extern "C" int h_shared_tables(const void* blob, size_t bytes) {
+  static PairingTables28 T;
+  static uint8_t have[192];
+  static bool filled = false;
+  if (bytes != sizeof have) return -1;
+  if (filled && memcmp(have, blob, sizeof have) == 0) return 0;
+  const uint8_t* b = (const uint8_t*)blob;
+  if (!g2_compressed_valid(b) || !g2_compressed_valid(b + 96)) return -3;
+  if (!pairing_tables_fill(g2_prepare(g2_decode_valid(b)), g2_prepare(g2_decode_valid(b + 96)), &T)) return -4;
+  memcpy(have, blob, sizeof have);
+  filled = true;
+  arith::h_pairing_tables = &T;
+  return 0;
+}
+
 static void fr_op(uint32_t op, const uint32_t* a, const uint32_t* b, uint32_t* o) {
   FrIn in{}; in.op = op;
   if (a) memcpy(in.a, a, 32);

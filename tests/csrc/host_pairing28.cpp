@@ -52,9 +52,27 @@ static Fp28 rand_p28(uint32_t top_bound) {   // normalised, top limb below top_b
   r.l[Fp28::N - 1] %= top_bound;
   return r;
 }
+// a coordinate of the operand classes of tests/arith_vectors.py (tower_coords): one in four is 0, 1, p (zero in its upper
+// representative), 1 + p, 2p - 1 or p - 1 with every low limb saturated below p's top limb; the others random below p
+static Fp28 rand_coord() {
+  Fp28 p, r;
+  for (int i = 0; i < Fp28::N; ++i) p.l[i] = Fp28::mod(i);
+  const uint32_t pick = rng28() & 31;
+  switch (pick) {
+    case 0: return Fp28::zero();
+    case 1: return Fp28::one();
+    case 2: return p;
+    case 3: return Fp28::add(Fp28::one(), p);
+    case 4: r = Fp28::add(p, p); r.l[0] -= 1; return r;                          // 2p's low limb is not zero
+    case 5: for (int i = 0; i < Fp28::N - 1; ++i) r.l[i] = Fp28::MASK; r.l[Fp28::N - 1] = Fp28::mod(Fp28::N - 1) - 1; return r;
+    case 6: r = p; r.l[0] -= 1; return r;
+    case 7: return Fp28::add(rand_p28(Fp28::mod(Fp28::N - 1)), p);               // a random residue in its upper representative
+    default: return rand_p28(Fp28::mod(Fp28::N - 1));
+  }
+}
 static void rand_f12r(F12r* x) {
   F2r* c = &x->c0.c0;
-  for (int i = 0; i < 6; ++i) c[i] = F2r{rand_p28(Fp28::mod(Fp28::N - 1)), rand_p28(Fp28::mod(Fp28::N - 1))};
+  for (int i = 0; i < 6; ++i) c[i] = F2r{rand_coord(), rand_coord()};
 }
 
 extern "C" {
