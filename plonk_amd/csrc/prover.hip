@@ -23,6 +23,7 @@
 #include "permutation.hpp"
 #include "diagnose.hpp"
 #include "composer.hpp"
+#include "prove_schedule_core.hpp"
 
 static_assert(plonk::DQ_M == plonk::QS_M && plonk::DQ_ARITH == plonk::QS_ARITH && plonk::DQ_VAR == plonk::QS_VAR &&
               plonk::DQ_COUNT == plonk::QS_COUNT, "diagnose_core.hpp selector ids");
@@ -183,6 +184,25 @@ struct SideJoin {   // never leave side work in flight when prove() returns (buf
   Ctx* c;
   ~SideJoin() { (void)hipStreamSynchronize(c->side_stream); }
 };
+// A commitment group and the side work that overlaps it: the side work is issued with the group (in front of it, on the
+// side stream) or, deferred, behind the event the group records at the end of its accumulation.
+template <class Side, class Commit>
+static int commit_with_side(Prover* p, bool defer, Side side_work, Commit commit) {
+  Ctx* c = p->c;
+  if (!defer) {
+    SideScope side(c, p->ev_ready);
+    PTRY(side_work());
+  }
+  {
+    AccMark mark(c, defer ? p->ev_acc : nullptr);
+    PTRY(commit());
+  }
+  if (defer) {
+    SideScopeAfter side(c, p->ev_acc);
+    PTRY(side_work());
+  }
+  return PLONK_OK;
+}
 
 // Host time of a proof (slots 8-10 of plonk_profile_read, only while profiling is on): what the HOST does while the device
 // waits for it.  prove() has five points where the transcript needs device results before the next kernels can be queued
@@ -883,6 +903,74 @@ struct Challenges {   // filled as the transcript produces them
   Fr beta, gamma;                                   // round 2
   Fr alpha, range_ch, logic_ch, fixed_ch, var_ch;   // round 3
 };
+static void draw_round2(Transcript& tr, Challenges* ch) {
+  ch->beta = tr.challenge_scalar("beta");
+  tr.append_scalar("beta", ch->beta);
+  ch->gamma = tr.challenge_scalar("gamma");
+}
+static void draw_round3(Transcript& tr, Challenges* ch) {
+  ch->alpha = tr.challenge_scalar("alpha");
+  ch->range_ch = tr.challenge_scalar("range separation challenge");
+  ch->logic_ch = tr.challenge_scalar("logic separation challenge");
+  ch->fixed_ch = tr.challenge_scalar("fixed base separation challenge");
+  ch->var_ch = tr.challenge_scalar("variable base separation challenge");
+}
+// round 3: t_low, t_mid, t_high and the t_fourth the path built, as one group into slots 5 .. 8
+static int commit_quotient_parts(Prover* p, const Fr* t4, uint64_t t4_len) {
+  const uint64_t n = p->n, np = p->np;
+  const Fr* sc[4] = {p->tparts, p->tparts + np, p->tparts + 2 * np, t4};
+  const uint64_t ms[4] = {n + 1, n + 1, n + 1, t4_len};
+  return msm_group(p, sc, ms, 4, 5);
+}
+// round 5: W_z and W_zw as one group into slots 9, 10
+static int commit_openings(Prover* p) {
+  const Fr* sc[2] = {p->wit, p->wit2};
+  const uint64_t ms[2] = {p->np - 2, p->np - 2};
+  return msm_group(p, sc, ms, 2, 9);
+}
+// the schedule of this prover's proofs under the context's configuration (prove_schedule_core.hpp): the one place that
+// reads the six switches
+static ProveSchedule schedule_of(const Prover* p) {
+  const Config& cfg = p->c->cfg;
+  ProveScheduleIn in;
+  in.logn = p->logn;
+  in.lag_on = p->lag_on;
+  in.lag_z = p->lag_z;
+  in.wires_pending = p->wires_pending;
+  in.world = (uint32_t)p->world;
+  in.sharded = p->sharded;
+  in.n = p->n;
+  in.rank_pts = p->hi - p->lo;
+  in.wire_by_column = cfg.wire_by_column;
+  in.wire_polys_side = cfg.wire_polys_side;
+  in.side_defer = cfg.side_defer;
+  in.z_commit_coeff = cfg.z_commit_coeff;
+  in.shard_side = cfg.shard_side;
+  in.shard_z = cfg.shard_z;
+  return prove_schedule(in);
+}
+// The scalars of a commitment group over the Lagrange-basis key, as msm_group takes them.  A commitment is an MSM of n
+// VALUES (read in place) and its blinders over [L_i(tau)] G and the key's blinding points; [lo, hi) are the key points
+// that take part: all n + 2 (wires) or n + 3 (z) of them, or a rank's slice.
+struct LagrangeGroup {
+  const Fr* sc[4];
+  const Fr* tl[4];
+  uint64_t ms[4], sp[4];
+  int count = 0;
+  void add(const Fr* values, const Fr* blinders, uint64_t n, uint64_t lo, uint64_t hi) {
+    sc[count] = values + (lo < n ? lo : 0);
+    sp[count] = lo < n ? (hi < n ? hi : n) - lo : 0;    // scalars of the range below index n
+    tl[count] = blinders + (lo > n ? lo - n : 0);       // blinder b_(index - n)
+    ms[count] = hi - lo;
+    ++count;
+  }
+};
+// wire columns k0 .. k1 - 1: bl[0..8) = a0 a1 b0 b1 c0 c1 d0 d1 wait in wscal
+static LagrangeGroup lagrange_wire_group(const Prover* p, const Fr* wires_dev, int k0, int k1, uint64_t lo, uint64_t hi) {
+  LagrangeGroup g;
+  for (int k = k0; k < k1; ++k) g.add(wires_dev + (uint64_t)k * p->n, p->wscal + 2 * k, p->n, lo, hi);
+  return g;
+}
 static uint64_t own_len(uint64_t len, uint64_t lo, uint64_t hi) {   // coefficients of a length-`len` polynomial inside [lo, hi)
   const uint64_t e = len < hi ? len : hi;
   return e > lo ? e - lo : 0;
@@ -1099,6 +1187,8 @@ static int prover_prove(Prover* p, const Fr* wires_dev, const uint64_t* pi_idx, 
   if (p->srs_gen != c->srs_gen) return (set_last_error("prover is bound to an SRS that was replaced on its context", __func__, __FILE__, __LINE__), PLONK_ERR_STATE);
   const uint64_t n = p->n, n8 = p->n8, np = p->np;
   const uint32_t L = p->logn;
+  const ProveSchedule sch = schedule_of(p);   // what this proof runs where, and why: prove_schedule_core.hpp
+  p->last_wire_launches = sch.wire_parts;
   NttTables* tbn;
   PTRY(ntt_tables(c, L, false, &tbn));
   const Fr omega = p->omega;
@@ -1112,112 +1202,64 @@ static int prover_prove(Prover* p, const Fr* wires_dev, const uint64_t* pi_idx, 
   GapScope gap_scope(&gap);
   // ---- round 1 (prover.rs:444-479)
   const bool lag = p->lag_on;
-  // Up to 2^19 gates the wire polynomials (needed from round 3 on) ride on the side stream under the commitment pipeline,
-  // started after the group's accumulation (side_defer below): they fill its latency-bound reduction tail.  At 2^20 the
-  // accumulation owns the VALU and its register file (two waves of 256 VGPRs per SIMD: no transform wave fits beside
-  // them), the tails of the four groups are too short for the 6 ms of side transforms, and the inverse transforms keep
-  // their place in front of the commitment (same-box A/B, profiles/r06b/polys_side_*.jsonl: 2^19 18.1-18.3 -> 17.4-17.7 ms
-  // with both moved, 2^20 32.17 -> 32.07-32.44).  PLONK_WIRE_POLYS_SIDE=0/1 forces it.
-  // plonk_gpu_config has no field for it; PLONK_WIRE_BY_COLUMN: 0 = never, 1 / 2 = at EVERY size (a, b, c + d / one launch per
-  // column: what the variant tests use to run the phased launches on small circuits), unset = from 2^19 gates on
-  const int bc_cfg = c->cfg.wire_by_column;
-  const bool by_column = lag && p->wires_pending && p->world == 1 && bc_cfg >= 0 && (L > 18 || bc_cfg > 0);
-  const bool polys_on_side = lag && !by_column && (c->cfg.wire_polys_side >= 0 ? c->cfg.wire_polys_side == 1 : L <= 19);
-  // Host wire columns (plonk_prover_prove, round 6): column k lands over PCIe 32 n bytes after column k - 1 (0.65 ms apart at
-  // 2^20 gates), and until round 5 the commitment group waited for all four before its grouped bucket sort — 2.1 ms of every
-  // such proof with nothing but the four inverse transforms to hide in.  Now each column's transform is followed at once by
-  // ITS bucket sort, accumulation and bucket sums (msm_batch_device phase 1 on column k: the throughput-bound 90 % of a
-  // commitment), under the next columns' copies; the latency-bound reduction tail still runs once for the group (phase 2).
-  // Same additions, same bucket sums, same bytes.  Resident columns (plonk_prover_prove_dev, what `value` times) keep the
-  // grouped launch: four launches have four ramp-downs.
-  if (!polys_on_side && !by_column) PTRY(wire_polynomials(p, wires_dev, bl, p->tmp8, 0, 4));
-  if (lag && by_column) {
-    HIP_TRY(hipMemcpyAsync(p->wscal, bl, 8 * sizeof(Fr), hipMemcpyHostToDevice, c->stream));
-  } else if (lag) {
+  if (!sch.polys_on_side && !sch.by_column) PTRY(wire_polynomials(p, wires_dev, bl, p->tmp8, 0, 4));
+  if (lag) {
     // Lagrange-basis key: a(X) = sum_i w_i L_i(X) + b0 (X^n - 1) + b1 (X^(n+1) - X)  (blind_poly, prover.rs:139-152), so the
     // commitment is an MSM of the wire VALUES and the two blinders over [L_i(tau)] G, [tau^n] G - G, [tau^(n+1)] G - [tau] G
     // (the values are read in place; only the eight blinders travel: bl[0..8) = a0 a1 b0 b1 c0 c1 d0 d1)
-    for (int k = 0; k < 4; ++k)
-      if (p->wires_pending) HIP_TRY(hipStreamWaitEvent(c->stream, p->ev_wire[k], 0));
+    if (!sch.by_column)   // (by column: wire_polynomials waits for each column where its launch begins)
+      for (int k = 0; k < 4; ++k)
+        if (p->wires_pending) HIP_TRY(hipStreamWaitEvent(c->stream, p->ev_wire[k], 0));
     HIP_TRY(hipMemcpyAsync(p->wscal, bl, 8 * sizeof(Fr), hipMemcpyHostToDevice, c->stream));
   }
   SideJoin side_join{c};
   uint64_t pi_len = 0;
-  // Side transforms either start with the group (they then compete with its bandwidth-bound sort) or wait for the end of
-  // its accumulation and fill the latency-bound tail.  Same-box A/B (r02e): waiting wins up to 2^18 gates (2^16: 5.19 vs
-  // 5.33 ms) and on the widget workload (38.1 vs 38.5 ms) but loses on the dense 2^20 headline (37.2-37.4 vs 36.6-36.8 ms:
-  // z's transform no longer fits between its commitment and the quotient), so it follows the size; round 6: 2^19 gates
-  // wait too, together with the wire inverse transforms (above).  PLONK_SIDE_DEFER=0/1 forces it.
-  const int side_defer_env = c->cfg.side_defer;
-  const bool defer_size = L <= 18 || (L == 19 && !by_column);   // (host wire columns at 2^19 gates keep the phased launches' order)
-  const bool side_defer = side_defer_env >= 0 ? side_defer_env >= 1 : defer_size;       // round 1: a, b, c, d (+ PI)
-  const bool side_defer_z = side_defer_env >= 0 ? side_defer_env == 1 : defer_size;      // round 2: z ("2" = round 1 only)
-  const bool z_from_evals = lag && p->lag_z && (L <= 17 || c->cfg.z_commit_coeff < 0);                                   // z committed from its evaluations (round 2)
   auto side_round1 = [&]() -> int {
     // quotient_poly.rs:139-157,177: coset FFTs of a, b, c, d and of the public-input polynomial
     // (prover.rs:520-521) need no challenge -> side stream, overlapped with the commitments; with the
     // Lagrange key the wire polynomials themselves are only needed from round 3 on and move there too
-    if (polys_on_side) PTRY(wire_polynomials(p, wires_dev, bl, p->tmp8b, 0, 4));
+    if (sch.polys_on_side) PTRY(wire_polynomials(p, wires_dev, bl, p->tmp8b, 0, 4));
     for (int k = 0; k < 4; ++k)
       PTRY(ntt_device(c, p->wpoly + k * np, p->cos + (1 + k) * n8, p->tmp8b, L + p->lq, false, true, n + 2));
     PTRY(public_input_polynomial(p, pi_idx, pi_val, pi_count, p->tmp8b, &pi_len));
     if (pi_len) PTRY(ntt_device(c, p->pipoly, p->cos + 5 * n8, p->tmp8b, L + p->lq, false, true, pi_len));   // no public inputs: PI(X) = 0, nothing to transform or read
     return PLONK_OK;
   };
-  if (!side_defer && !by_column) {
-    SideScope side(c, p->ev_ready);
-    PTRY(side_round1());
-  }
-  if (by_column) {
-    const uint64_t ms[4] = {n + 2, n + 2, n + 2, n + 2};
-    const Fr* sc[4] = {wires_dev, wires_dev + n, wires_dev + 2 * n, wires_dev + 3 * n};
-    const Fr* tl[4] = {p->wscal, p->wscal + 2, p->wscal + 4, p->wscal + 6};
-    const uint64_t sp[4] = {n, n, n, n};
-    // Columns a and b each get a launch of their own as they land; c and d — both have arrived by the time b's accumulation
-    // ends (0.65 ms per column over PCIe against ~1.5 ms of commitment work per column at 2^20 gates) — share one: a sort
-    // launch set and an accumulation ramp-down less.  Measured and NOT adopted (profiles/r06/host_wires_ab.jsonl): column k's
-    // work on a stream of its own (k & 1), gated only by its copy — no gain at 2^20 (gap 1.09-1.27 against 1.12 ms) and a
-    // loss at 2^19 (0.38-0.54 against 0.24): the accumulations are VALU-bound, so overlapping them only interleaves them.
-    // PLONK_WIRE_BY_COLUMN=2: one launch per column (A/B)
-    const int parts[3][2] = {{0, 1}, {1, 1}, {2, 2}};
-    const int nparts = c->cfg.wire_by_column == 2 ? 4 : 3;
-    p->last_wire_launches = (uint32_t)nparts;
-    for (int q = 0; q < nparts; ++q) {
-      const int k0 = nparts == 4 ? q : parts[q][0], kc = nparts == 4 ? 1 : parts[q][1];
+  if (sch.by_column) {
+    // host wire columns, committed as they arrive: a launch per part (phase 1), one reduction tail for the group (phase 2)
+    const LagrangeGroup g = lagrange_wire_group(p, wires_dev, 0, 4, 0, n + 2);
+    const int parts[3][2] = {{0, 1}, {1, 1}, {2, 2}};   // a, b, c + d
+    for (int q = 0; q < (int)sch.wire_parts; ++q) {
+      const int k0 = sch.wire_parts == 4 ? q : parts[q][0], kc = sch.wire_parts == 4 ? 1 : parts[q][1];
       PTRY(wire_polynomials(p, wires_dev, bl, p->tmp8, k0, k0 + kc));   // waits for the columns' copies, then their inverse transforms + blinding
-      if (k0 + kc == 4 && !side_defer) {              // all four polynomials exist: their coset transforms go to the side stream
+      if (k0 + kc == 4 && !sch.side_defer_r1) {              // all four polynomials exist: their coset transforms go to the side stream
         SideScope side(c, p->ev_ready);
         PTRY(side_round1());
       }
-      AccMark mark(c, (side_defer && k0 + kc == 4) ? p->ev_acc : nullptr);
-      PTRY(msm_group(p, sc, ms, 4, 0, p->lag_table, p->lag_n, tl, sp, 1, k0, kc));
+      AccMark mark(c, (sch.side_defer_r1 && k0 + kc == 4) ? p->ev_acc : nullptr);
+      PTRY(msm_group(p, g.sc, g.ms, 4, 0, p->lag_table, p->lag_n, g.tl, g.sp, 1, k0, kc));
     }
-    PTRY(msm_group(p, sc, ms, 4, 0, p->lag_table, p->lag_n, tl, sp, 2));
+    PTRY(msm_group(p, g.sc, g.ms, 4, 0, p->lag_table, p->lag_n, g.tl, g.sp, 2));
+    if (sch.side_defer_r1) {
+      SideScopeAfter side(c, p->ev_acc);
+      PTRY(side_round1());
+    }
   } else {
-    p->last_wire_launches = 1;
-    AccMark mark(c, side_defer ? p->ev_acc : nullptr);
-    const uint64_t ms[4] = {n + 2, n + 2, n + 2, n + 2};
-    if (lag) {
-      const Fr* sc[4] = {wires_dev, wires_dev + n, wires_dev + 2 * n, wires_dev + 3 * n};
-      const Fr* tl[4] = {p->wscal, p->wscal + 2, p->wscal + 4, p->wscal + 6};
-      const uint64_t sp[4] = {n, n, n, n};
-      PTRY(msm_group(p, sc, ms, 4, 0, p->lag_table, p->lag_n, tl, sp));
-    } else {
+    PTRY(commit_with_side(p, sch.side_defer_r1, side_round1, [&]() -> int {
+      if (lag) {
+        const LagrangeGroup g = lagrange_wire_group(p, wires_dev, 0, 4, 0, n + 2);
+        return msm_group(p, g.sc, g.ms, 4, 0, p->lag_table, p->lag_n, g.tl, g.sp);
+      }
       const Fr* sc[4] = {p->wpoly, p->wpoly + np, p->wpoly + 2 * np, p->wpoly + 3 * np};
-      PTRY(msm_group(p, sc, ms, 4, 0));   // commit_polynomials (prover.rs:187-210) as one group launch
-    }
-  }
-  if (side_defer) {
-    SideScopeAfter side(c, p->ev_acc);
-    PTRY(side_round1());
+      const uint64_t ms[4] = {n + 2, n + 2, n + 2, n + 2};
+      return msm_group(p, sc, ms, 4, 0);   // commit_polynomials (prover.rs:187-210) as one group launch
+    }));
   }
   PTRY(absorb_commitments(p, tr, 0, 4, comm));
 
   // ---- round 2 (prover.rs:481-505)
   Challenges ch;
-  ch.beta = tr.challenge_scalar("beta");
-  tr.append_scalar("beta", ch.beta);
-  ch.gamma = tr.challenge_scalar("gamma");
+  draw_round2(tr, &ch);
   {
     prof_begin(c, 4);
     const PermArgs pa = perm_args(p, wires_dev, ch, tbn);
@@ -1228,21 +1270,17 @@ static int prover_prove(Prover* p, const Fr* wires_dev, const uint64_t* pi_idx, 
     PTRY(poly_batch_inverse(c, pa.den, n, true));
     PTRY(poly_mul_arrays(c, pa.num, pa.den, n, p->flag_dev));
     PTRY(scan_prefix_product(c, pa.num, n, p->totals));
-    if (!z_from_evals) PTRY(blind_z(p, pa.num, bl, p->tmp8));
+    if (!sch.z_from_evals) PTRY(blind_z(p, pa.num, bl, p->tmp8));
     prof_end(c, 4);
   }
   // Round 6, second session: z(X) = sum_i z_i L_i(X) + (b0 + b1 X + b2 X^2)(X^n - 1), so — like the wires — its commitment is
   // an MSM of the n EVALUATIONS the scan just wrote and the three blinders over the Lagrange-basis key and its blinding
   // points: the inverse transform, the blinding and the copy of the low coefficients leave the critical path (the side
-  // stream runs them before z's coset transform; `scratch` keeps the evaluations until round 5 reuses it).  Up to 2^17 gates
-  // only: same-box A/B 2^12 2.04 -> 2.01 ms, 2^16 4.09 -> 4.03, 2^17 5.88 -> 5.86 (even in a later
-  // five-repetition pair); at 2^18 the coefficient form is 1 % ahead (9.88 against 10.00 ms, mid_sizes_ab.jsonl), at 2^19 too, and
-  // at 2^20 the transform that left the main stream competes with the commitment's sort on the side stream instead (32.2 against
-  // 32.3), so larger circuits keep the coefficient form (profiles/r06b/zcommit_ab.jsonl).
+  // stream runs them before z's coset transform; `scratch` keeps the evaluations until round 5 reuses it).
   // The side stream's share of either form: z's coset transform and, in front of it, what the evaluation form took off the
   // main stream — z(X) in coefficient form (needed from round 3 on) and its lowest coefficients.
   auto side_round2 = [&]() -> int {
-    if (z_from_evals) {
+    if (sch.z_from_evals) {
       PTRY(blind_z(p, p->scratch, bl, p->tmp8b));
       HIP_TRY(hipMemcpyAsync(p->low_host + 28, p->zpoly, 7 * sizeof(Fr), hipMemcpyDeviceToHost, c->stream));
       HIP_TRY(hipEventRecord(p->ev_zlow, c->stream));
@@ -1251,39 +1289,22 @@ static int prover_prove(Prover* p, const Fr* wires_dev, const uint64_t* pi_idx, 
     HIP_TRY(hipEventRecord(p->ev_side, c->side_stream));
     return PLONK_OK;
   };
-  if (z_from_evals) {
+  if (sch.z_from_evals) {
     HIP_TRY(hipMemcpyAsync(p->wscal + 8, bl + 8, 3 * sizeof(Fr), hipMemcpyHostToDevice, c->stream));
   } else {
     HIP_TRY(hipMemcpyAsync(p->low_host + 28, p->zpoly, 7 * sizeof(Fr), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipEventRecord(p->ev_zlow, c->stream));
   }
-  if (!side_defer_z) {
-    SideScope side(c, p->ev_ready);
-    PTRY(side_round2());
-  }
-  {
-    AccMark mark(c, side_defer_z ? p->ev_acc : nullptr);
-    if (z_from_evals) {
-      const Fr* sc[1] = {p->scratch};
-      const Fr* tl[1] = {p->wscal + 8};
-      const uint64_t ms[1] = {n + 3}, sp[1] = {n};
-      PTRY(msm_group(p, sc, ms, 1, 4, p->lag_table, p->lag_n, tl, sp));
-    } else {
-      PTRY(msm_to(p, p->zpoly, n + 3, 4));
-    }
-  }
-  if (side_defer_z) {
-    SideScopeAfter side(c, p->ev_acc);
-    PTRY(side_round2());
-  }
+  PTRY(commit_with_side(p, sch.side_defer_r2, side_round2, [&]() -> int {
+    if (!sch.z_from_evals) return msm_to(p, p->zpoly, n + 3, 4);
+    LagrangeGroup g;
+    g.add(p->scratch, p->wscal + 8, n, 0, n + 3);
+    return msm_group(p, g.sc, g.ms, 1, 4, p->lag_table, p->lag_n, g.tl, g.sp);
+  }));
   PTRY(absorb_commitments(p, tr, 4, 1, comm));
 
   // ---- round 3 (prover.rs:507-589)
-  ch.alpha = tr.challenge_scalar("alpha");
-  ch.range_ch = tr.challenge_scalar("range separation challenge");
-  ch.logic_ch = tr.challenge_scalar("logic separation challenge");
-  ch.fixed_ch = tr.challenge_scalar("fixed base separation challenge");
-  ch.var_ch = tr.challenge_scalar("variable base separation challenge");
+  draw_round3(tr, &ch);
   // quotient (quotient_poly.rs:20-137): the 6 coset FFTs on 8n were issued on the side stream in
   // rounds 1-2; point-wise pass, then coset iFFT
   HIP_TRY(hipStreamWaitEvent(c->main_stream, p->ev_side, 0));
@@ -1330,11 +1351,7 @@ static int prover_prove(Prover* p, const Fr* wires_dev, const uint64_t* pi_idx, 
   }
   Fr* t4 = p->tbuf + 3 * n;
   const uint64_t t4_len = len4 ? len4 : 1;                 // t_fourth[0] -= b14 even when the tail is empty
-  {
-    const Fr* sc[4] = {p->tparts, p->tparts + np, p->tparts + 2 * np, t4};
-    const uint64_t ms[4] = {n + 1, n + 1, n + 1, t4_len};
-    PTRY(msm_group(p, sc, ms, 4, 5));
-  }
+  PTRY(commit_quotient_parts(p, t4, t4_len));
   PTRY(absorb_commitments(p, tr, 5, 4, comm));
   if (*p->flag_host) return (plonk::set_last_error("invalid argument", __func__, __FILE__, __LINE__), PLONK_ERR_ARG);   // "permutation denominator must be nonzero" (permutation.rs:231-234)
 
@@ -1394,11 +1411,7 @@ static int prover_prove(Prover* p, const Fr* wires_dev, const uint64_t* pi_idx, 
   HIP_TRY(hipMemcpyAsync(p->evout + 15, p->scratch, sizeof(Fr), hipMemcpyDeviceToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(p->ev_host + 15, p->evout + 15, sizeof(Fr), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamWaitEvent(c->main_stream, p->ev_side, 0));   // W_zw (side stream, above)
-  {
-    const Fr* sc[2] = {p->wit, p->wit2};
-    const uint64_t ms[2] = {np - 2, np - 2};
-    PTRY(msm_group(p, sc, ms, 2, 9));
-  }
+  PTRY(commit_openings(p));
   PTRY(fetch_commitments(p, 9, 2, comm + 9));
   if (!quotient_identity_holds(p->ev_host[15], ev, ch.alpha, ch.beta, ch.gamma, op.l1_z, op.vp)) return PLONK_ERR_UNSAT;
 
@@ -1420,6 +1433,7 @@ static int prover_prove_sharded(Prover* p, const Fr* wires_dev, const uint64_t* 
   const uint64_t n = p->n, np = p->np, qn = p->qn;
   const uint32_t L = p->logn, W = (uint32_t)p->world, cpr = p->cpr, Q = p->Q;
   const uint64_t lo = p->lo, hi = p->hi;                       // owned coefficient indices, hi <= n + 7
+  const ProveSchedule sch = schedule_of(p);                    // a rank's schedule: prove_schedule_core.hpp
   NttTables* tbn;
   PTRY(ntt_tables(c, L, false, &tbn));
   const Fr omega = p->omega;
@@ -1432,23 +1446,13 @@ static int prover_prove_sharded(Prover* p, const Fr* wires_dev, const uint64_t* 
   uint8_t comm[11][48];
   // ---- round 1 (replicated polynomials, sharded commitments)
   const bool lag = p->lag_on;
-  // Round 4 (r04): the schedule of the single-GPU path for a RANK.  With the Lagrange-basis slice the wire commitments read
-  // the wire VALUES, so the replicated wire polynomials (needed from round 3 on) ride on the side stream under the
-  // commitment pipeline — a rank's MSM over 1/W of the points leaves most of the chip idle in its latency-bound sort and
-  // reduction tail (W = 8 at 2^20: 1.4 of the rank's 7.7 ms were these transforms in front of the commitment).  The side
-  // work starts after the group's accumulation (side_defer) while the rank's share is small; PLONK_SHARD_SIDE=0 restores
-  // the round-3 order.
-  const bool shard_side_env = c->cfg.shard_side >= 0;   // plonk_gpu_config.shard_side_stream = -1 / PLONK_SHARD_SIDE=0 restores the round-3 order
-  const uint64_t rank_pts = hi - lo;
-  const bool polys_on_side = lag && shard_side_env && rank_pts <= (1ull << 18) + 64;   // (2^19 points per rank: 19.2 -> 19.4 ms, the accumulation owns the VALU)
-  const bool side_defer = shard_side_env && rank_pts <= (1ull << 18) + 64;
-  if (!polys_on_side) PTRY(wire_polynomials(p, wires_dev, bl, p->tmp8, 0, 4));
+  if (!sch.polys_on_side) PTRY(wire_polynomials(p, wires_dev, bl, p->tmp8, 0, 4));
   SideJoin side_join{c};
   uint64_t pi_len = 0;
   Fr* fold_side = p->fold + n;
   auto side_round1 = [&]() -> int {
     // class evaluations of a, b, c, d, PI on the side stream: fold mod (X^n - x^n|class), size-n coset transform
-    if (polys_on_side) PTRY(wire_polynomials(p, wires_dev, bl, p->tmp8b, 0, 4));
+    if (sch.polys_on_side) PTRY(wire_polynomials(p, wires_dev, bl, p->tmp8b, 0, 4));
     for (uint32_t k = 0; k < cpr; ++k)
       for (int w = 0; w < 4; ++w) {
         PTRY(poly_fold(c, p->wpoly + w * np, fold_side, n, 2, p->sigma_j[p->cls[k]]));
@@ -1460,83 +1464,46 @@ static int prover_prove_sharded(Prover* p, const Fr* wires_dev, const uint64_t* 
         PTRY(ntt_device(c, p->pipoly, p->cos + 5 * qn + k * n, p->tmp8b, L, false, true, n, &p->cs_fwd[k]));
     return PLONK_OK;
   };
-  if (!side_defer) {
-    SideScope side(c, p->ev_ready);
-    PTRY(side_round1());
-  }
-  {
-    AccMark mark(c, side_defer ? p->ev_acc : nullptr);
-    if (lag && p->lag_whole) {
+  PTRY(commit_with_side(p, sch.side_defer_r1, side_round1, [&]() -> int {
+    if (!lag) {
+      const Fr* sc[4] = {p->wpoly, p->wpoly + np, p->wpoly + 2 * np, p->wpoly + 3 * np};
+      const uint64_t ms[4] = {n + 2, n + 2, n + 2, n + 2};
+      return msm_group(p, sc, ms, 4, 0);
+    }
+    for (int k = 0; k < 4; ++k)
+      if (p->wires_pending) HIP_TRY(hipStreamWaitEvent(c->stream, p->ev_wire[k], 0));
+    HIP_TRY(hipMemcpyAsync(p->wscal, bl, 8 * sizeof(Fr), hipMemcpyHostToDevice, c->stream));
+    if (p->lag_whole) {
       // by commitment (round 5): this rank's whole columns over the whole Lagrange-basis key, exactly the single-GPU launch
       // for those columns; the slots of the columns it does not own hold the identity (all-zero bit sums), so the all-gather
       // + add of fetch_commitments needs no change
       const int per_rank = 4 / (int)W, first = per_rank * p->rank;
-      for (int k = 0; k < 4; ++k)
-        if (p->wires_pending) HIP_TRY(hipStreamWaitEvent(c->stream, p->ev_wire[k], 0));
-      HIP_TRY(hipMemcpyAsync(p->wscal, bl, 8 * sizeof(Fr), hipMemcpyHostToDevice, c->stream));
       HIP_TRY(hipMemsetAsync(p->res, 0, (size_t)RES_STRIDE * 4, c->stream));
       for (int k = 0; k < 4; ++k) { p->res_bitpos[k] = false; p->res_rowbits[k] = 8; }
-      const Fr* sc[2];
-      const Fr* tl[2];
-      uint64_t ms[2], sp[2];
-      for (int j = 0; j < per_rank; ++j) {
-        sc[j] = wires_dev + (uint64_t)(first + j) * n;
-        tl[j] = p->wscal + 2 * (first + j);
-        ms[j] = n + 2;
-        sp[j] = n;
-      }
-      PTRY(msm_group(p, sc, ms, per_rank, first, p->lag_table, p->lag_n, tl, sp));
-    } else if (lag) {
-      // wire commitments from the wire VALUES over this rank's slice of the Lagrange-basis key (see prover_prove): values
-      // [lo_L, hi_L) of each column in place, the column's two blinders for the slice that reaches indices n, n + 1
-      const uint64_t lo_l = p->shard_lo, hi_l = p->shard_lo + p->lag_n;       // hi_l <= n + 2
-      for (int k = 0; k < 4; ++k)
-        if (p->wires_pending) HIP_TRY(hipStreamWaitEvent(c->stream, p->ev_wire[k], 0));
-      HIP_TRY(hipMemcpyAsync(p->wscal, bl, 8 * sizeof(Fr), hipMemcpyHostToDevice, c->stream));
-      const Fr* sc[4];
-      const Fr* tl[4];
-      uint64_t ms[4], sp[4];
-      for (int k = 0; k < 4; ++k) {
-        sc[k] = wires_dev + (uint64_t)k * n + (lo_l < n ? lo_l : 0);
-        sp[k] = lo_l < n ? n - lo_l : 0;                                      // scalars of the slice below index n
-        if (sp[k] > p->lag_n) sp[k] = p->lag_n;
-        tl[k] = p->wscal + 2 * k + (lo_l > n ? lo_l - n : 0);                 // blinder b_(index - n)
-        ms[k] = hi_l - lo_l;
-      }
-      PTRY(msm_group(p, sc, ms, 4, 0, p->lag_table, p->lag_n, tl, sp));
-    } else {
-      const Fr* sc[4] = {p->wpoly, p->wpoly + np, p->wpoly + 2 * np, p->wpoly + 3 * np};
-      const uint64_t ms[4] = {n + 2, n + 2, n + 2, n + 2};
-      PTRY(msm_group(p, sc, ms, 4, 0));
+      const LagrangeGroup g = lagrange_wire_group(p, wires_dev, first, first + per_rank, 0, n + 2);
+      return msm_group(p, g.sc, g.ms, per_rank, first, p->lag_table, p->lag_n, g.tl, g.sp);
     }
-  }
-  if (side_defer) {
-    SideScopeAfter side(c, p->ev_acc);
-    PTRY(side_round1());
-  }
+    // wire commitments from the wire VALUES over this rank's slice of the Lagrange-basis key (see prover_prove): values
+    // [lo_L, hi_L) of each column in place, the column's two blinders for the slice that reaches indices n, n + 1
+    const LagrangeGroup g = lagrange_wire_group(p, wires_dev, 0, 4, p->shard_lo, p->shard_lo + p->lag_n);   // hi_L <= n + 2
+    return msm_group(p, g.sc, g.ms, 4, 0, p->lag_table, p->lag_n, g.tl, g.sp);
+  }));
   PTRY(absorb_commitments(p, tr, 0, 4, comm));
 
   // ---- round 2 (replicated grand product)
   Challenges ch;
-  ch.beta = tr.challenge_scalar("beta");
-  tr.append_scalar("beta", ch.beta);
-  ch.gamma = tr.challenge_scalar("gamma");
+  draw_round2(tr, &ch);
   {
     prof_begin(c, 4);
     PermArgs pa = perm_args(p, wires_dev, ch, tbn);
     gap.launching();
     HIP_TRY(hipMemsetAsync(p->flag_dev, 0, sizeof(int), c->stream));
-    // Round 4: the grand product (permutation.rs:213-294) split over the ranks from 2^19 gates and four ranks on.  Rank r forms the n / W
+    // Round 4: the grand product (permutation.rs:213-294) split over the ranks.  Rank r forms the n / W
     // numerator / denominator terms of ITS evaluation indices, inverts, multiplies and scans them locally; the ranks exchange
     // their range products (36 bytes each: the product in twiddle form + the zero-denominator flag), every rank scales its
     // range by the product of the ranges before it, and the z evaluations are all-gathered in place (32 n / W bytes per
     // rank; 0.5 MB per peer link at 2^20 gates and W = 8) for the one replicated step left, z's inverse transform.
-    // PLONK_SHARD_Z=0 / 1 forces either (the multi-rank tests run small circuits through both).
-    const int shard_z_env = c->cfg.shard_z > 0 ? 1 : (c->cfg.shard_z < 0 ? 0 : -1);   // plonk_gpu_config.shard_grand_product / PLONK_SHARD_Z
-    // rank alone, loop-back collectives (profiles/r04): W = 8 at 2^20 gates 7.41 -> 7.01 ms, at 2^22 21.9 -> 20.1; W = 2 at 2^20
-    // 19.05 -> 19.27 (half of 0.5 ms of work against two more host round trips): from four ranks on
-    const bool shard_z = (shard_z_env >= 0 ? shard_z_env == 1 : (L >= 19 && W >= 4)) && n % W == 0 && n / W >= 2;
-    if (!shard_z) {
+    if (!sch.shard_z) {
       PTRY(poly_perm_terms(c, pa));
       PTRY(poly_batch_inverse(c, pa.den, n, true));
       PTRY(poly_mul_arrays(c, pa.num, pa.den, n, p->flag_dev));
@@ -1585,26 +1552,11 @@ static int prover_prove_sharded(Prover* p, const Fr* wires_dev, const uint64_t* 
     HIP_TRY(hipEventRecord(p->ev_side, c->side_stream));
     return PLONK_OK;
   };
-  if (!side_defer) {
-    SideScope side(c, p->ev_ready);
-    PTRY(side_round2());
-  }
-  {
-    AccMark mark(c, side_defer ? p->ev_acc : nullptr);
-    PTRY(msm_to(p, p->zpoly, n + 3, 4));
-  }
-  if (side_defer) {
-    SideScopeAfter side(c, p->ev_acc);
-    PTRY(side_round2());
-  }
+  PTRY(commit_with_side(p, sch.side_defer_r2, side_round2, [&]() -> int { return msm_to(p, p->zpoly, n + 3, 4); }));
   PTRY(absorb_commitments(p, tr, 4, 1, comm));
 
   // ---- round 3: quotient on the owned classes
-  ch.alpha = tr.challenge_scalar("alpha");
-  ch.range_ch = tr.challenge_scalar("range separation challenge");
-  ch.logic_ch = tr.challenge_scalar("logic separation challenge");
-  ch.fixed_ch = tr.challenge_scalar("fixed base separation challenge");
-  ch.var_ch = tr.challenge_scalar("variable base separation challenge");
+  draw_round3(tr, &ch);
   gap.launching();
   HIP_TRY(hipStreamWaitEvent(c->main_stream, p->ev_side, 0));
   for (uint32_t k = 0; k < cpr; ++k) {
@@ -1644,11 +1596,7 @@ static int prover_prove_sharded(Prover* p, const Fr* wires_dev, const uint64_t* 
   }
   HIP_TRY(hipMemcpyAsync(p->flag_host, p->flag_dev, sizeof(int), hipMemcpyDeviceToHost, c->stream));
   const uint64_t t4_len = n + 7;   // t has 4n + 7 coefficients by construction (prover.hip, 4n path); explicit zeros do not change a commitment
-  {
-    const Fr* sc[4] = {p->tparts, p->tparts + np, p->tparts + 2 * np, t4};
-    const uint64_t ms[4] = {n + 1, n + 1, n + 1, t4_len};
-    PTRY(msm_group(p, sc, ms, 4, 5));
-  }
+  PTRY(commit_quotient_parts(p, t4, t4_len));
   PTRY(absorb_commitments(p, tr, 5, 4, comm));
   if (*p->flag_host) return (plonk::set_last_error("invalid argument", __func__, __FILE__, __LINE__), PLONK_ERR_ARG);
 
@@ -1727,11 +1675,7 @@ static int prover_prove_sharded(Prover* p, const Fr* wires_dev, const uint64_t* 
   gap.launching();
   PTRY(poly_ruffini_finish(c, p->scratch, p->wit, lo, rlen, op.inv_z, carry_z, n + 6));
   PTRY(poly_ruffini_finish(c, p->scratch2, p->wit2, lo, rlen, op.inv_z * p->omega_inv, carry_zw, n + 6));
-  {
-    const Fr* sc[2] = {p->wit, p->wit2};
-    const uint64_t ms[2] = {np - 2, np - 2};
-    PTRY(msm_group(p, sc, ms, 2, 9));
-  }
+  PTRY(commit_openings(p));
   PTRY(fetch_commitments(p, 9, 2, comm + 9));
   if (!quotient_identity_holds(num_at_z, ev, ch.alpha, ch.beta, ch.gamma, op.l1_z, op.vp)) return PLONK_ERR_UNSAT;
   write_proof(proof, comm, ev);
