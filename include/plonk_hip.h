@@ -840,8 +840,8 @@ int plonk_kzg_evals_last(plonk_kzg_domain* domain, plonk_kzg_evals_info* out);
  *   H_m = c_(r-2-m) (m <= r-2), H_(r-1) = O                                                          
  *   A VERIFIER checks cell k with  e(proofs[k], [tau^l] h) == e(C - commit(r_k) + x_k proofs[k], h):  with an opening key whose
  *   third element is [tau^l] h instead of [tau] h that is plonk_kzg_pairing_check_each(key_l, A = proofs[k],
- *   B = C - commit(r_k) + x_k proofs[k]), C the commitment and r_k from the cell's values by the formula above.  The library
- *   has no device-side cell verifier.
+ *   B = C - commit(r_k) + x_k proofs[k]), C the commitment and r_k from the cell's values by the formula above.
+ *   plonk_kzg_verify_cells / plonk_kzg_verify_cells_each (below) do all of this on the device.
  * plonk_kzg_open_cells: `count` polynomials in coefficient form (host pointers; lengths may differ).  cells: count x n x 4
  *   limbs, Montgomery, cell-major; proofs48: count x r x 48 bytes, compressed G1, encoded on the device; commitments48:
  *   count x 48 through the ordinary commitment path, NULL skips them.  A polynomial of fewer than l + 1 coefficients has r
@@ -882,6 +882,75 @@ int plonk_kzg_open_cells_dev(plonk_kzg_domain* domain, uint32_t log_cell, const 
                              void* cells_dev, void* proofs48_dev, void* commitments48_dev /* or NULL */);
 int plonk_kzg_cell_points(plonk_kzg_domain* domain, uint32_t log_cell, uint64_t* x /* r x 4: w^(l k) */, uint64_t* shift /* r x 4: w^k, or NULL */);
 int plonk_kzg_cells_last(plonk_kzg_domain* domain, plonk_kzg_cells_info* out);
+
+/* ---- KZG10 cell verification: a folded batch check and per-cell verdicts --------------------------------
+ * The checking side of plonk_kzg_open_cells.  Items i < count each name a commitment c_i < ncommitments and a cell k_i < r and
+ * bring the cell's l values v_i and its proof pi_i.  With c_ij = w^(-k_i j) * (the size-l inverse NTT of v_i)_j, the
+ * coefficients of the remainder r_i, and weights rho^i (item 0 has weight 1):
+ *     L   = sum_i rho^i pi_i
+ *     Rhs = sum_c (sum_(i : c_i = c) rho^i) C_c + sum_i (rho^i x_(k_i)) pi_i - sum_(j < l) (sum_i rho^i c_ij) s_j
+ *     accept iff e(L, [tau^l] h) == e(Rhs, h)
+ *   and per item, weight 1:  e(pi_i, [tau^l] h) == e(C_(c_i) + x_(k_i) pi_i - sum_j c_ij s_j, h)   (DESIGN.md section 17).
+ * plonk_kzg_cell_verifier_create: key_l is a plonk_kzg_key whose third element is [tau^l] h (NOT the ordinary opening key's
+ *   [tau] h); log_n in [2, 20]; log_cell in [1, min(log_n - 1, 11)]: a cell is transformed by ONE workgroup in LDS, larger
+ *   cells are out of scope.  The handle COPIES the first l points of the context's commit key into device memory of its own
+ *   and builds x_k and w^(-k) (k < r) and the l / 2 inverse twiddles there: l points and 2r + l / 2 scalars, none of the
+ *   tables of a plonk_kzg_domain.  Reloading the context's commit key afterwards does not affect the verifier.  Errors, in
+ *   this order: PLONK_ERR_ARG (a NULL pointer, a size outside the ranges above); PLONK_ERR_STATE for a context with a
+ *   communicator; PLONK_ERR_NO_SRS; PLONK_ERR_DEGREE for a commit key of fewer than l points; PLONK_ERR_VERIFY when s_0 is not
+ *   the key's g; PLONK_ERR_VERIFY when e(s_l, h) != e(s_0, x_h) — one host pairing, made only when the commit key has more
+ *   than l points (it catches an ordinary opening key passed by mistake); with exactly l points the check cannot be made and
+ *   plonk_kzg_cell_verifier_last reports key_checked = 0.  Destroy the verifier before its key, the key before its context.
+ * plonk_kzg_verify_cells: the folded check: one call, two MSM launches (plonk_msm_points' kernels, per-term or buckets by its
+ *   own rule), ONE pairing on the host whatever count is; no bisection, as plonk_kzg_batch_check.  PLONK_OK when the batch
+ *   verifies; PLONK_ERR_VERIFY for a failing batch and for count == 0.  Checks, in this order: PLONK_ERR_ARG (a NULL
+ *   argument, an index >= ncommitments or >= r, count > 2^20, count * l > 2^25, ncommitments > 65536); PLONK_ERR_DATA (a
+ *   value or rho_override that is not a canonical residue); PLONK_ERR_POINT (a commitment or proof that does not decode or is
+ *   outside the subgroup; the compressed identity is legal); then the pairing.  An error leaves nothing queued.
+ *   rho: with rho_override == NULL it is drawn from a fresh Merlin transcript Transcript::new(label): "dom-sep" =
+ *   "kzg10-cell-batch-check-v1"; u64 "log-n", "log-cell", "commitments", "items"; "opening-key" = the key's 240 bytes;
+ *   "commitment" per commitment; per item u64 "commitment-index", u64 "cell-index", "cell" = its l x 32 canonical
+ *   little-endian bytes, "cell-proof"; challenge_scalar("cell-batch-challenge").  The transcript runs on the host over
+ *   count x l x 32 bytes (info->ms_scalars shows its cost).  rho_override replaces it — for a caller whose own transcript
+ *   already binds all of the above.  A rho the prover could predict VOIDS the check (errors of two items can be made to
+ *   cancel); with an unpredictable rho a batch with a false item passes with probability at most count / q.
+ * plonk_kzg_verify_cells_each: exact per-item verdicts, one device pairing per item (the kernels of
+ *   plonk_kzg_pairing_check_each): verdicts[i] = PLONK_OK, PLONK_ERR_VERIFY, PLONK_ERR_DATA (one of its values is not
+ *   canonical) or PLONK_ERR_POINT (its proof or the commitment it names); a malformed item never stops the others, and
+ *   verdicts[i] is what the folded call returns for that item alone.  Returns PLONK_OK when every verdict is, PLONK_ERR_VERIFY
+ *   when at least one is not (as plonk_kzg_check_each), PLONK_ERR_ARG as above (and for count == 0) with verdicts untouched.
+ * plonk_verify_info (may be NULL) is filled as plonk_kzg_batch_check / plonk_kzg_check_each fill it: proofs = count;
+ *   msm_terms = 2 count + ncommitments + l (folded) or l + 2 per checked item (each).
+ * plonk_kzg_cell_verifier_last: what the last call on the handle ran as; the tests assert it against the plan computed on the
+ *   host (plonk_amd/csrc/kzg_cell_verify_core.hpp).  The calls leave the context, its commit key, tables, provers and
+ *   plonk_ctx_last_msm_points as they found them; the workspaces belong to the handle, only grow, and go with it. */
+typedef struct plonk_kzg_cell_verifier plonk_kzg_cell_verifier;
+typedef struct plonk_kzg_cell_verify_info {
+  uint32_t log_n;
+  uint32_t log_cell;
+  uint32_t key_checked;            /* 1: e(s_l, h) == e(s_0, x_h) was checked at creation */
+  uint32_t path_each;              /* 1: the last call was plonk_kzg_verify_cells_each */
+  uint64_t items;                  /* of the last call (0 before the first) */
+  uint64_t commitments;
+  uint64_t transforms;             /* size-l inverse transforms: one per item */
+  uint64_t msm_terms_left;         /* folded: count */
+  uint64_t msm_terms_right;        /* folded: ncommitments + count + l */
+  uint32_t msm_path_left;          /* 0 per-term kernel, 1 buckets */
+  uint32_t msm_path_right;
+  uint64_t scalar_muls;            /* each: count x (l + 1) full-width scalar multiplications */
+  uint64_t device_bytes;           /* everything the handle holds on the device */
+} plonk_kzg_cell_verify_info;
+int plonk_kzg_cell_verifier_create(plonk_kzg_key* key_l, uint32_t log_n, uint32_t log_cell, plonk_kzg_cell_verifier** out);
+void plonk_kzg_cell_verifier_destroy(plonk_kzg_cell_verifier* v);
+int plonk_kzg_verify_cells(plonk_kzg_cell_verifier* v, const uint8_t* commitments48 /* M x 48 */, uint64_t ncommitments,
+                           const uint32_t* commitment_index /* count */, const uint32_t* cell_index /* count */,
+                           const uint64_t* values /* count x l x 4, Montgomery */, const uint8_t* proofs48 /* count x 48 */, uint64_t count,
+                           const uint8_t* label, uint64_t label_len, const uint64_t* rho_override /* 4 limbs or NULL */,
+                           plonk_verify_info* info /* may be NULL */);
+int plonk_kzg_verify_cells_each(plonk_kzg_cell_verifier* v, const uint8_t* commitments48, uint64_t ncommitments,
+                                const uint32_t* commitment_index, const uint32_t* cell_index, const uint64_t* values,
+                                const uint8_t* proofs48, uint64_t count, int32_t* verdicts /* count */, plonk_verify_info* info);
+int plonk_kzg_cell_verifier_last(plonk_kzg_cell_verifier* v, plonk_kzg_cell_verify_info* out);
 
 /* ---- variable-base MSM over caller-supplied points ------------------------------------------------
  * sum_i scalars[i] * P_i for points the CALLER brings — the reference's msm_variable_base (the primitive under Proof::verify

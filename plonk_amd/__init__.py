@@ -78,6 +78,8 @@ EXPORTS = [
     "plonk_kzg_commit_evals", "plonk_kzg_commit_evals_dev", "plonk_kzg_open_evals", "plonk_kzg_open_evals_dev",
     "plonk_kzg_evals_last",
     "plonk_kzg_open_cells", "plonk_kzg_open_cells_dev", "plonk_kzg_cell_points", "plonk_kzg_cells_last",
+    "plonk_kzg_cell_verifier_create", "plonk_kzg_cell_verifier_destroy", "plonk_kzg_verify_cells", "plonk_kzg_verify_cells_each",
+    "plonk_kzg_cell_verifier_last",
 ]
 
 # what bit f of plonk_unsat_row.families / slot f of plonk_unsat_info.family_rows stands for (include/plonk_hip.h); the
@@ -166,6 +168,15 @@ class _KzgCellsInfo(ctypes.Structure):
                 ("count", ctypes.c_uint64), ("slices", ctypes.c_uint64), ("chunk_polys", ctypes.c_uint64),
                 ("workspace_bytes", ctypes.c_uint64), ("table_bytes", ctypes.c_uint64), ("stage_launches", ctypes.c_uint64),
                 ("scalar_muls", ctypes.c_uint64)]
+
+
+class _KzgCellVerifyInfo(ctypes.Structure):
+    """plonk_kzg_cell_verify_info (include/plonk_hip.h)"""
+    _fields_ = [("log_n", ctypes.c_uint32), ("log_cell", ctypes.c_uint32), ("key_checked", ctypes.c_uint32), ("path_each", ctypes.c_uint32),
+                ("items", ctypes.c_uint64), ("commitments", ctypes.c_uint64), ("transforms", ctypes.c_uint64),
+                ("msm_terms_left", ctypes.c_uint64), ("msm_terms_right", ctypes.c_uint64),
+                ("msm_path_left", ctypes.c_uint32), ("msm_path_right", ctypes.c_uint32),
+                ("scalar_muls", ctypes.c_uint64), ("device_bytes", ctypes.c_uint64)]
 
 
 class _ProverInfo(ctypes.Structure):
@@ -445,6 +456,14 @@ def load_library() -> ctypes.CDLL:
     lib.plonk_kzg_open_cells_dev.argtypes = [vp, u32, ctypes.POINTER(vp), ctypes.POINTER(u64), u64, vp, vp, vp]
     lib.plonk_kzg_cell_points.argtypes = [vp, u32, vp, vp]
     lib.plonk_kzg_cells_last.argtypes = [vp, ctypes.POINTER(_KzgCellsInfo)]
+    lib.plonk_kzg_cell_verifier_create.argtypes = [vp, u32, u32, ctypes.POINTER(vp)]
+    lib.plonk_kzg_cell_verifier_destroy.argtypes = [vp]
+    lib.plonk_kzg_cell_verifier_destroy.restype = None
+    lib.plonk_kzg_verify_cells.argtypes = [vp, vp, u64, vp, vp, vp, vp, u64, vp, u64, vp, vp]
+    lib.plonk_kzg_verify_cells_each.argtypes = [vp, vp, u64, vp, vp, vp, vp, u64, vp, vp]
+    lib.plonk_kzg_cell_verifier_last.argtypes = [vp, ctypes.POINTER(_KzgCellVerifyInfo)]
+    lib.plonk_test_kzg_cell_verify_last_rho.argtypes = [vp, vp]   # test hooks of kzg_cell_verify.hip, not in the header
+    lib.plonk_test_kzg_cell_verify_force_paths.argtypes = [vp, u32, u32]
     _lib = lib
     return lib
 
@@ -1594,8 +1613,101 @@ class KzgKey:
 
     def close(self):
         if getattr(self, "handle", None):
+            for v in list(getattr(self, "_cell_verifiers", ())):   # they hold a pointer to the native key
+                v.close()
             if getattr(self.ctx, "handle", None):
                 self.ctx.lib.plonk_kzg_key_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class KzgCellVerifier:
+    """plonk_kzg_cell_verifier: checks the cells and proofs of KzgDomain.open_cells on the device (include/plonk_hip.h).
+    `key` is a KzgKey whose third element is [tau^l] h.  The handle copies the first l points of the context's commit key;
+    reloading that key afterwards does not affect it.  `items` is a list of (commitment_index, cell_index, values, proof48);
+    values: l ints, or 32 l Montgomery bytes (for the non-canonical cases).  Destroyed before its key."""
+
+    def __init__(self, key: KzgKey, log_n: int, log_cell: int):
+        self.key, self.ctx, self.log_n, self.log_cell = key, key.ctx, log_n, log_cell
+        h = ctypes.c_void_p()
+        self.ctx._check(self.ctx.lib.plonk_kzg_cell_verifier_create(key.handle, log_n, log_cell, ctypes.byref(h)))
+        self.handle = h
+        if not hasattr(key, "_cell_verifiers"):
+            key._cell_verifiers = weakref.WeakSet()
+        key._cell_verifiers.add(self)
+
+    def _args(self, commitments, items):
+        commitments, items = [bytes(c) for c in commitments], list(items)
+        l = 1 << self.log_cell
+        if any(len(c) != 48 for c in commitments) or any(len(bytes(it[3])) != 48 for it in items):
+            raise ValueError("commitments and proofs are 48-byte compressed G1 points")
+        vals = []
+        for it in items:
+            v = bytes(it[2]) if isinstance(it[2], (bytes, bytearray)) else fr_to_bytes_mont(it[2])
+            if len(v) != 32 * l:
+                raise ValueError("a cell has 2^log_cell values")
+            vals.append(v)
+        n = max(len(items), 1)
+        cidx = (ctypes.c_uint32 * n)(*[it[0] for it in items])
+        kidx = (ctypes.c_uint32 * n)(*[it[1] for it in items])
+        return (self.handle, b"".join(commitments) or None, len(commitments), cidx, kidx, b"".join(vals) or b"\0",
+                b"".join(bytes(it[3]) for it in items) or b"\0", len(items))
+
+    def verify_code(self, commitments, items, label: bytes = b"", rho: "int | None" = None):
+        """(return code of plonk_kzg_verify_cells, plonk_verify_info as a dict)"""
+        info = _VerifyInfo()
+        rc = self.ctx.lib.plonk_kzg_verify_cells(*self._args(commitments, items), label, len(label),
+                                                 fr_to_bytes_mont([rho]) if rho is not None else None, ctypes.byref(info))
+        return rc, {k: getattr(info, k) for k, _ in info._fields_}
+
+    def verify(self, commitments, items, label: bytes = b"", rho: "int | None" = None) -> bool:
+        """The folded check: True when the whole batch verifies, False when it does not (PLONK_ERR_VERIFY, an empty batch
+        included); malformed input raises.  `rho` replaces the challenge the library derives from a fresh transcript over
+        `label` and every input; a rho the prover could predict voids the check."""
+        rc, _ = self.verify_code(commitments, items, label, rho)
+        if rc not in (PLONK_OK, -12):
+            self.ctx._check(rc)
+        return rc == PLONK_OK
+
+    def verify_each_info(self, commitments, items):
+        """(verdict codes, plonk_verify_info as a dict) of plonk_kzg_verify_cells_each: 0 valid, -12 PLONK_ERR_VERIFY, -10
+        PLONK_ERR_POINT, -9 PLONK_ERR_DATA per item"""
+        args = self._args(commitments, items)
+        verdicts = (ctypes.c_int32 * max(args[-1], 1))()
+        info = _VerifyInfo()
+        rc = self.ctx.lib.plonk_kzg_verify_cells_each(*args, verdicts, ctypes.byref(info))
+        if rc not in (PLONK_OK, -12):
+            self.ctx._check(rc)
+        return [int(v) for v in verdicts][:args[-1]], {k: getattr(info, k) for k, _ in info._fields_}
+
+    def verify_each(self, commitments, items) -> list:
+        return self.verify_each_info(commitments, items)[0]
+
+    def last(self) -> dict:
+        info = _KzgCellVerifyInfo()
+        self.ctx._check(self.ctx.lib.plonk_kzg_cell_verifier_last(self.handle, ctypes.byref(info)))
+        return {k: getattr(info, k) for k, _ in info._fields_}
+
+    def _last_rho(self) -> int:
+        """TEST HOOK: the challenge of the last folded call.  Not part of the C API."""
+        out = ctypes.create_string_buffer(32)
+        self.ctx._check(self.ctx.lib.plonk_test_kzg_cell_verify_last_rho(self.handle, out))
+        return fr_from_bytes_mont(out.raw)[0]
+
+    def _force_paths(self, min_left: int = 0, min_right: int = 0):
+        """TEST HOOK: plonk_msm_points' min_bucket_terms for the left / right sum of the next folded calls (1 forces the
+        buckets, a value above the term count the per-term kernel, 0 restores the rule).  Not part of the C API."""
+        self.ctx._check(self.ctx.lib.plonk_test_kzg_cell_verify_force_paths(self.handle, min_left, min_right))
+
+    def close(self):
+        if getattr(self, "handle", None):
+            if getattr(self.key, "handle", None) and getattr(self.ctx, "handle", None):
+                self.ctx.lib.plonk_kzg_cell_verifier_destroy(self.handle)
             self.handle = None
 
     def __del__(self):

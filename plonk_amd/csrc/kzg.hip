@@ -30,12 +30,7 @@
 #include "hostpairing.hpp"
 #include "verify_core.hpp"
 #include "kzg_core.hpp"
-
-namespace plonk { struct KzgKey; }
-struct plonk_kzg_key {
-  plonk::KzgKey* k;
-  plonk_ctx* ctx;
-};
+#include "kzg_key.hpp"
 
 namespace plonk {
 
@@ -281,17 +276,7 @@ static int kzg_open_body(const char* api_fn, Ctx& c, const void* const* polys, c
   return PLONK_OK;
 }
 
-// ---- the opening key ---------------------------------------------------------------------------------------------------
-struct KzgKey {
-  Ctx* c = nullptr;
-  uint8_t opening_key[OPENING_KEY_LEN];
-  G2Prepared h, x_h;
-  G1Affine g_aff;        // g as decoded on the device
-  Fr last_u, last_r;     // the challenges of the last batch_check / srs_check (test hook)
-  void* pair_tables = nullptr;   // device: the lines of x_h and h for the pairing kernel, made by the first per-item call
-  ~KzgKey() { (void)hipFree(pair_tables); }
-};
-
+// ---- the opening key (kzg_key.hpp) ---------------------------------------------------------------------------------------
 static int check_reserve(KzgWork& w, uint64_t npts, uint64_t nterms) {
   PTRY(w.need(KzgWork::PTS, sizeof(G1Affine) * npts));
   PTRY(w.need(KzgWork::KIND, 4 * npts));
