@@ -952,6 +952,63 @@ int plonk_kzg_verify_cells_each(plonk_kzg_cell_verifier* v, const uint8_t* commi
                                 const uint8_t* proofs48, uint64_t count, int32_t* verdicts /* count */, plonk_verify_info* info);
 int plonk_kzg_cell_verifier_last(plonk_kzg_cell_verifier* v, plonk_kzg_cell_verify_info* out);
 
+/* ---- KZG10 cell recovery: a polynomial rebuilt from a subset of its cells --------------------------------
+ * The third part of data-availability sampling next to plonk_kzg_open_cells and plonk_kzg_verify_cells: from `available`
+ * distinct cells of a polynomial of at most max_len coefficients (max_len <= available x l) the call rebuilds the
+ * coefficients, all r cells, their proofs and the commitment.  Notation as above; M = the r - available missing cells:
+ *     Z(X) = Z_r(X^l),  Z_r(Y) = prod_(m in M) (Y - phi^m)     Z(w^(k + r j)) = Z_r(phi^k),  Z(7 w^i) = Z_r(7^l phi^(i mod r))
+ *     E = the values, 0 in missing cells;  P = f Z = NTT^-1(E Z) exactly (deg < max_len + l |M| <= n)
+ *     f = coset-NTT^-1( coset-NTT(P)_i / Z_r(7^l phi^(i mod r)) )       (7 the generator of plonk_ntt's coset; 7^n != 1)
+ *   The values are consistent with a polynomial of at most max_len coefficients iff the result is zero from index max_len on;
+ *   with max_len < available x l a single changed value is always detected, with max_len == available x l there is no
+ *   redundancy and every input is consistent (the call returns the interpolant).                       
+ * plonk_kzg_recover_cells: all `count` polynomials share ONE set of cells (rows of a blob matrix that lost the same columns):
+ *   cell_ids: `available` distinct indexes < r in any order; values[b]: available x l x 4 limbs, Montgomery, the cells in the
+ *   order of cell_ids, each cell as plonk_kzg_open_cells writes it.  Outputs, each may be NULL but not all four: coeffs (count
+ *   x n x 4, zero above the polynomial), cells (count x n x 4, cell-major), proofs48 (count x r x 48) and commitments48
+ *   (count x 48): byte for byte what plonk_kzg_open_cells returns for the recovered polynomial (proofs and commitments come
+ *   through its code).  status (count entries, may be NULL): PLONK_OK or PLONK_ERR_VERIFY per polynomial.
+ *   Checks, in this order, every one before anything is queued or written: PLONK_ERR_ARG (a NULL domain; log_cell outside
+ *   [1, log_n - 1]; log_n - log_cell > 11, that is r > 2048 — Z_r is evaluated by direct products, 2r |M| multiplications,
+ *   and a product tree for larger r is not built; count > 65536; available == 0 or > r; a cell index >= r or repeated; NULL
+ *   cell_ids or values, or values[b] NULL, with count > 0; max_len == 0 or > n; all four outputs NULL); PLONK_ERR_STATE
+ *   exactly where plonk_kzg_open_cells returns it; count == 0 is PLONK_OK and writes nothing; PLONK_ERR_DEGREE for max_len >
+ *   available x l; PLONK_ERR_DATA for a value that is not a canonical residue; PLONK_ERR_VERIFY when any polynomial is
+ *   inconsistent: the verdict is read back with one synchronisation before any output is written, status is filled, and the
+ *   four outputs stay untouched (all or nothing).  On success status is all PLONK_OK.
+ *   The workspace (3 arrays of n values per polynomial of a chunk) stays under the handle's workspace cap, chunked as
+ *   plonk_kzg_open_domain chunks; a call of several chunks computes the coefficients twice, before and after the verdict.
+ *   With proofs48 == NULL the call leaves plonk_kzg_cells_last as it was; with proofs48 set it runs plonk_kzg_open_cells'
+ *   body (and may build its A^(u) tables: built_table).  The context, its tables and the handle's other entry points are
+ *   left as found.
+ * plonk_kzg_recover_cells_dev: values_dev is a HOST array of `count` device pointers, the four outputs are device pointers
+ *   on the context's GPU; cell_ids and status stay host memory.
+ * plonk_kzg_recover_last: what the last plonk_kzg_recover_cells call on the handle ran as (count == 0 before the first): the
+ *   tests assert it against the plan computed on the host (plonk_amd/csrc/kzg_recover_core.hpp). */
+typedef struct plonk_kzg_recover_info {
+  uint32_t log_n;
+  uint32_t log_cell;               /* cell size of the last call */
+  uint32_t chunks;                 /* chunks the polynomials of the last call were processed in */
+  uint32_t built_table;            /* 1: this call made plonk_kzg_open_cells' body build the A^(u) of its cell size */
+  uint64_t count;                  /* polynomials of the last call */
+  uint64_t available;              /* cells given */
+  uint64_t missing;                /* r - available */
+  uint64_t max_len;
+  uint64_t chunk_polys;            /* polynomials per chunk (the last chunk may be shorter) */
+  uint64_t transforms;             /* size-n transforms issued: 3 per polynomial (6 in a call of several chunks), + 1 for cell values */
+  uint64_t vanish_muls;            /* 2r x missing */
+  uint64_t workspace_bytes;        /* 3 x n x 32 per polynomial of a chunk */
+  uint64_t inconsistent;           /* polynomials whose values fit no polynomial of max_len coefficients */
+} plonk_kzg_recover_info;
+int plonk_kzg_recover_cells(plonk_kzg_domain* domain, uint32_t log_cell, const uint32_t* cell_ids, uint64_t available,
+                            const uint64_t* const* values, uint64_t count, uint64_t max_len, uint64_t* coeffs /* count x n x 4, or NULL */,
+                            uint64_t* cells /* count x n x 4, cell-major, or NULL */, uint8_t* proofs48 /* count x r x 48, or NULL */,
+                            uint8_t* commitments48 /* count x 48, or NULL */, int32_t* status /* count, or NULL */);
+int plonk_kzg_recover_cells_dev(plonk_kzg_domain* domain, uint32_t log_cell, const uint32_t* cell_ids, uint64_t available,
+                                const void* const* values_dev, uint64_t count, uint64_t max_len, void* coeffs_dev, void* cells_dev,
+                                void* proofs48_dev, void* commitments48_dev, int32_t* status);
+int plonk_kzg_recover_last(plonk_kzg_domain* domain, plonk_kzg_recover_info* out);
+
 /* ---- variable-base MSM over caller-supplied points ------------------------------------------------
  * sum_i scalars[i] * P_i for points the CALLER brings — the reference's msm_variable_base (the primitive under Proof::verify
  * and OpeningKey::batch_check) — where plonk_msm / _batch / _dev run over the loaded commit key and its precomputed tables.

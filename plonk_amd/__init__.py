@@ -80,6 +80,7 @@ EXPORTS = [
     "plonk_kzg_open_cells", "plonk_kzg_open_cells_dev", "plonk_kzg_cell_points", "plonk_kzg_cells_last",
     "plonk_kzg_cell_verifier_create", "plonk_kzg_cell_verifier_destroy", "plonk_kzg_verify_cells", "plonk_kzg_verify_cells_each",
     "plonk_kzg_cell_verifier_last",
+    "plonk_kzg_recover_cells", "plonk_kzg_recover_cells_dev", "plonk_kzg_recover_last",
 ]
 
 # what bit f of plonk_unsat_row.families / slot f of plonk_unsat_info.family_rows stands for (include/plonk_hip.h); the
@@ -168,6 +169,14 @@ class _KzgCellsInfo(ctypes.Structure):
                 ("count", ctypes.c_uint64), ("slices", ctypes.c_uint64), ("chunk_polys", ctypes.c_uint64),
                 ("workspace_bytes", ctypes.c_uint64), ("table_bytes", ctypes.c_uint64), ("stage_launches", ctypes.c_uint64),
                 ("scalar_muls", ctypes.c_uint64)]
+
+
+class _KzgRecoverInfo(ctypes.Structure):
+    """plonk_kzg_recover_info (include/plonk_hip.h)"""
+    _fields_ = [("log_n", ctypes.c_uint32), ("log_cell", ctypes.c_uint32), ("chunks", ctypes.c_uint32), ("built_table", ctypes.c_uint32),
+                ("count", ctypes.c_uint64), ("available", ctypes.c_uint64), ("missing", ctypes.c_uint64), ("max_len", ctypes.c_uint64),
+                ("chunk_polys", ctypes.c_uint64), ("transforms", ctypes.c_uint64), ("vanish_muls", ctypes.c_uint64),
+                ("workspace_bytes", ctypes.c_uint64), ("inconsistent", ctypes.c_uint64)]
 
 
 class _KzgCellVerifyInfo(ctypes.Structure):
@@ -456,6 +465,9 @@ def load_library() -> ctypes.CDLL:
     lib.plonk_kzg_open_cells_dev.argtypes = [vp, u32, ctypes.POINTER(vp), ctypes.POINTER(u64), u64, vp, vp, vp]
     lib.plonk_kzg_cell_points.argtypes = [vp, u32, vp, vp]
     lib.plonk_kzg_cells_last.argtypes = [vp, ctypes.POINTER(_KzgCellsInfo)]
+    lib.plonk_kzg_recover_cells.argtypes = [vp, u32, vp, u64, ctypes.POINTER(vp), u64, u64, vp, vp, vp, vp, vp]
+    lib.plonk_kzg_recover_cells_dev.argtypes = [vp, u32, vp, u64, ctypes.POINTER(vp), u64, u64, vp, vp, vp, vp, vp]
+    lib.plonk_kzg_recover_last.argtypes = [vp, ctypes.POINTER(_KzgRecoverInfo)]
     lib.plonk_kzg_cell_verifier_create.argtypes = [vp, u32, u32, ctypes.POINTER(vp)]
     lib.plonk_kzg_cell_verifier_destroy.argtypes = [vp]
     lib.plonk_kzg_cell_verifier_destroy.restype = None
@@ -1872,6 +1884,77 @@ class KzgDomain:
     def cells_last(self) -> dict:
         info = _KzgCellsInfo()
         self.ctx._check(self.ctx.lib.plonk_kzg_cells_last(self.handle, ctypes.byref(info)))
+        return {k: getattr(info, k) for k, _ in info._fields_}
+
+    # ---- cell recovery: the polynomial, all of its cells and their proofs from a subset of the cells ----
+    def _recover_check(self, rc: int, status, count: int):
+        if rc == -12:
+            err = ProofVerificationError(rc, (self.ctx.lib.plonk_last_error() or b"").decode())
+            err.status = list(status[:count])
+            raise err
+        self.ctx._check(rc)
+
+    def recover_cells_bytes(self, cell_ids, values_bytes, log_cell: int, max_len: int, proofs: bool = True, commitments: bool = True,
+                            coeffs: bool = False, cells: bool = True):
+        """plonk_kzg_recover_cells on Montgomery bytes: values_bytes[j] = the cells cell_ids of polynomial j, l x 32 bytes each, in
+        the order of cell_ids -> (cell-value bytes, proof bytes, commitment bytes, coefficient bytes), each the concatenation
+        over the polynomials, or None where not asked for.  Raises ProofVerificationError (with .status, one code per
+        polynomial) when a polynomial's values fit no polynomial of max_len coefficients; nothing is returned then."""
+        ids = list(cell_ids)
+        bufs = [bytes(b) for b in values_bytes]
+        count, a = len(bufs), len(ids)
+        r = self.n >> log_cell if 0 <= log_cell < 64 else 0
+        for b in bufs:
+            if len(b) != 32 * (a << log_cell if 0 <= log_cell < 64 else 0):
+                raise ValueError("a polynomial's values must hold exactly len(cell_ids) cells of l field elements")
+        keep = [ctypes.create_string_buffer(b, len(b)) for b in bufs]
+        parr = (ctypes.c_void_p * max(count, 1))(*[ctypes.cast(k, ctypes.c_void_p).value for k in keep])
+        iarr = (ctypes.c_uint32 * max(a, 1))(*ids)
+        out_cells = ctypes.create_string_buffer(max(32 * self.n * count, 1)) if cells else None
+        out_proofs = ctypes.create_string_buffer(max(48 * r * count, 1)) if proofs else None
+        out_cm = ctypes.create_string_buffer(max(48 * count, 1)) if commitments else None
+        out_coeffs = ctypes.create_string_buffer(max(32 * self.n * count, 1)) if coeffs else None
+        status = (ctypes.c_int32 * max(count, 1))()
+        rc = self.ctx.lib.plonk_kzg_recover_cells(self.handle, log_cell, iarr, a, parr, count, max_len, out_coeffs, out_cells, out_proofs,
+                                                  out_cm, status)
+        self._recover_check(rc, status, count)
+        return (out_cells.raw[:32 * self.n * count] if cells else None, out_proofs.raw[:48 * r * count] if proofs else None,
+                out_cm.raw[:48 * count] if commitments else None, out_coeffs.raw[:32 * self.n * count] if coeffs else None)
+
+    def recover_cells(self, cell_ids, values, log_cell: int, max_len: int, proofs: bool = True, commitments: bool = True,
+                      coeffs: bool = False):
+        """values[j][i]: the l values (ints) of cell cell_ids[i] of polynomial j — what open_cells returned as cells[j][cell_ids[i]]
+        — or per polynomial the same as Montgomery bytes.  All polynomials share the cell set; each has at most max_len
+        coefficients, max_len <= len(cell_ids) * l.  -> (cells[j][k], proofs[j][k] or None, commitments[j] or None, coefficients[j]
+        (n ints) or None): the first three are what open_cells returns for the recovered polynomials."""
+        bufs = [v if isinstance(v, (bytes, bytearray)) else fr_to_bytes_mont([x for cell in v for x in cell]) for v in values]
+        cl, pr, cm, co = self.recover_cells_bytes(cell_ids, bufs, log_cell, max_len, proofs, commitments, coeffs)
+        n, count, l = self.n, len(bufs), 1 << log_cell
+        r = n >> log_cell
+        vals = fr_from_bytes_mont(cl)
+        cof = fr_from_bytes_mont(co) if coeffs else None
+        return ([[vals[j * n + k * l:j * n + (k + 1) * l] for k in range(r)] for j in range(count)],
+                [[pr[48 * (j * r + k):48 * (j * r + k + 1)] for k in range(r)] for j in range(count)] if proofs else None,
+                [cm[48 * j:48 * j + 48] for j in range(count)] if commitments else None,
+                [cof[j * n:(j + 1) * n] for j in range(count)] if coeffs else None)
+
+    def recover_cells_dev(self, cell_ids, ptrs, log_cell: int, max_len: int, coeffs: "int | None" = None, cells: "int | None" = None,
+                          proofs: "int | None" = None, commitments: "int | None" = None):
+        """plonk_kzg_recover_cells_dev: values resident in HBM (device pointers, len(cell_ids) x l values each); the outputs are
+        device pointers (count x n x 32, count x n x 32, count x r x 48, count x 48 bytes) or None.  Returns the status list."""
+        ids, ptrs = list(cell_ids), list(ptrs)
+        count = len(ptrs)
+        parr = (ctypes.c_void_p * max(count, 1))(*ptrs)
+        iarr = (ctypes.c_uint32 * max(len(ids), 1))(*ids)
+        status = (ctypes.c_int32 * max(count, 1))()
+        rc = self.ctx.lib.plonk_kzg_recover_cells_dev(self.handle, log_cell, iarr, len(ids), parr, count, max_len, coeffs, cells, proofs,
+                                                      commitments, status)
+        self._recover_check(rc, status, count)
+        return list(status[:count])
+
+    def recover_last(self) -> dict:
+        info = _KzgRecoverInfo()
+        self.ctx._check(self.ctx.lib.plonk_kzg_recover_last(self.handle, ctypes.byref(info)))
         return {k: getattr(info, k) for k, _ in info._fields_}
 
     def _set_workspace_cap(self, nbytes: int):

@@ -285,7 +285,7 @@ int cells_body(const KzdView& v, KzgCells* e, uint32_t log_cell, const void* con
     PTRY(kzd_extract(&c, ws, stride, log_r, cnt));
     PTRY(kzd_transform(&c, ws + r, stride, log_r, cnt, false, v.tw, L + 1, &info.stage_launches, &info.scalar_muls));
     PTRY(kzd_finish(&c, ws, stride, r, log_r, cnt, true, out48));
-    HIP_TRY(hipMemcpyAsync((uint8_t*)cells + sizeof(Fr) * n * first, cl, sizeof(Fr) * n * cnt, hipMemcpyDefault, c.stream));
+    if (cells) HIP_TRY(hipMemcpyAsync((uint8_t*)cells + sizeof(Fr) * n * first, cl, sizeof(Fr) * n * cnt, hipMemcpyDefault, c.stream));
     HIP_TRY(hipMemcpyAsync((uint8_t*)proofs48 + 48 * r * first, out48, 48 * r * cnt, hipMemcpyDefault, c.stream));
     if (commitments48) {
       comm.resize(48ull * cnt);
@@ -329,6 +329,14 @@ int cells_impl(const char* api_fn, plonk_kzg_domain* dom, uint32_t log_cell, con
 }
 
 }  // namespace
+
+int kzc_open_resident(const KzdView& v, uint32_t log_cell, const void* const* polys_dev, const uint64_t* trimmed, uint64_t count, void* cells,
+                      void* proofs48, void* commitments48, uint32_t* built_table) {
+  KzgCells* e = kzc_state(v.cells);
+  PTRY(cells_body(v, e, log_cell, polys_dev, trimmed, count, cells, proofs48, commitments48));
+  if (e->last.built_table) *built_table = 1;
+  return PLONK_OK;
+}
 
 void kzc_release(void* cells) { delete (KzgCells*)cells; }
 void kzc_set_slices(void** cells, uint64_t slices) { kzc_state(cells)->forced_slices = slices; }

@@ -255,7 +255,9 @@ struct KzgDomain : KzdBufs, DevBufs<KzdBufs::NBUF> {
   plonk_kzg_domain_info last = {};
   void* evals = nullptr;         // the Lagrange points and workspace of the evaluation-form calls (kzg_evals.hip); not in device_bytes()
   void* cells = nullptr;         // the A^(u) tables and workspace of the cell proofs (kzg_cells.hip); not in device_bytes()
-  ~KzgDomain() {   // in this order: the cell state, the evaluation-form state, the fixed buffers; the base frees the grow-only ones last
+  void* recover = nullptr;       // the workspace of the cell recovery (kzg_recover.hip); not in device_bytes()
+  ~KzgDomain() {   // in this order: the recovery state, the cell state, the evaluation-form state, the fixed buffers; the base frees the grow-only ones last
+    kzr_release(recover);
     kzc_release(cells);
     kze_release(evals);
     (void)hipFree(A);
@@ -266,7 +268,7 @@ struct KzgDomain : KzdBufs, DevBufs<KzdBufs::NBUF> {
 
 KzdView kzd_view(plonk_kzg_domain* dom) {
   KzgDomain* d = dom->d;
-  return KzdView{d->c, d->log_n, d->srs_gen == d->c->srs_gen, d->tw, &d->evals, &d->cells, d->ws_cap};
+  return KzdView{d->c, d->log_n, d->srs_gen == d->c->srs_gen, d->tw, &d->evals, &d->cells, d->ws_cap, &d->recover};
 }
 
 static int domain_create_body(Ctx& c, uint32_t log_n, KzgDomain* d) {

@@ -48,8 +48,10 @@ struct KzdView {
   void** evals;            // the handle's slot for the state of kzg_evals.hip, released through kze_release
   void** cells;            // the handle's slot for the state of kzg_cells.hip, released through kzc_release
   uint64_t ws_cap;         // the cap on the point workspace of a call
+  void** recover;          // the handle's slot for the state of kzg_recover.hip, released through kzr_release
 };
 KzdView kzd_view(plonk_kzg_domain* dom);
 void kze_release(void* evals);
+void kzr_release(void* recover);   // kzg_recover.hip
 
 }  // namespace plonk
