@@ -1009,6 +1009,79 @@ int plonk_kzg_recover_cells_dev(plonk_kzg_domain* domain, uint32_t log_cell, con
                                 void* proofs48_dev, void* commitments48_dev, int32_t* status);
 int plonk_kzg_recover_last(plonk_kzg_domain* domain, plonk_kzg_recover_info* out);
 
+/* ---- KZG10 multiproofs: many evaluation-form openings, one 96-byte proof -----------------------------------
+ * K claims "vector j_k has the value y_k at index m_k" over M committed vectors of n = 2^log_n values (e_j[i] = p_j(w^i), C_j
+ * their commitments as plonk_kzg_commit_evals makes them) behind one proof of 96 bytes, whatever K is — the multiproof by
+ * random evaluation.  Item k has the weight r^k:
+ *     g(X) = sum_k r^k (p_(j_k)(X) - y_k) / (X - w^(m_k))      D = commit(g)                          (degree <= n - 2)
+ *     s_j  = sum_(k : j_k = j) r^k / (t - w^(m_k))             h = sum_j s_j e_j                       (t outside the domain)
+ *     y    = sum_k r^k y_k / (t - w^(m_k))   = h(t) - g(t)     pi = commit(((h - g)[i] - y) / (w^i - t))
+ *     proof96 = D || pi;    accept iff e(pi, [tau] h) == e(sum_j s_j C_j - D - [y] g + t pi, h)        
+ *   Everything stays in evaluation form: the quotients are aggregated per distinct point index with the derivative entry of
+ *   plonk_kzg_open_evals, K n field products in all; D and pi are two MSMs of n terms over the handle's Lagrange points (built
+ *   by whichever evaluation-form call of the handle commits first, shared with plonk_kzg_commit_evals / plonk_kzg_open_evals).
+ * Challenges: a fresh Merlin transcript Transcript::new(label), the same on both sides: "dom-sep" = "kzg10-multiproof-v1";
+ *   u64 "log-n", "commitments" (M), "items" (K); "commitment" for each of the M commitments; per item, in the caller's order,
+ *   u64 "vector-index", u64 "point-index" and "value" (32 canonical little-endian bytes); r = challenge_scalar("multiproof-r");
+ *   then "multiproof-d" = D's 48 bytes; t = challenge_scalar("multiproof-t").  challenges_override: 8 limbs, r then t,
+ *   Montgomery, replaces BOTH — for a caller whose own transcript binds all of the above.  A predictable r lets false claims
+ *   cancel each other and a predictable t lets a prover fit g to it: either voids the check.
+ * plonk_kzg_multiproof_open: evals[j]: n x 4 limbs, Montgomery; items k < count name vector_index[k] < nvectors and
+ *   point_index[k] < n.  The prover reads y_k from the vectors itself (values: count x 4 limbs out), so a false claim cannot be
+ *   made.  commitments_in (nvectors x 48): hashed as given, not decoded — a wrong commitment gives a proof that fails; NULL:
+ *   computed as plonk_kzg_commit_evals computes them (nvectors more MSMs) and those are hashed.  commitments_out, if not NULL,
+ *   receives whichever set was used.  Duplicate items, and vectors that no item names, are legal.  The host form uploads ALL
+ *   nvectors vectors into a grow-only workspace of the handle (nvectors x n x 32 bytes, hence its cap); the _dev form reads
+ *   them where they are and has no such cap.
+ *   Checks, in this order, every one before anything is queued or written; an error leaves nothing queued and no output
+ *   touched: PLONK_ERR_ARG (a NULL required pointer — domain, evals, evals[j], both index arrays, values, proof96, label with
+ *   label_len > 0; count == 0 or > 2^20; nvectors == 0 or > 65536; an index >= nvectors or >= n; host form only: nvectors x n
+ *   > 2^28); PLONK_ERR_DATA (an override that is not canonical or whose t has t^n == 1; a value of a vector that is not a
+ *   canonical residue — the _dev form finds that by a scan on the device, after the state checks, still before any output is
+ *   written); PLONK_ERR_STATE (the domain's commit key was replaced on its context; the context has a communicator; a
+ *   transcript-drawn t that lies in the domain: probability n / q, below 2^-234 — open again under another label; t exists
+ *   only once D does, so this one check comes after the aggregation, still with no output written and nothing left queued).
+ *   The call leaves the context, its tables, its provers, plonk_ctx_last_msm_points, plonk_kzg_domain_last and
+ *   plonk_kzg_evals_last as it found them, except that plonk_kzg_evals_last.lagrange_bytes reports the shared Lagrange points
+ *   once this call has built them.
+ * plonk_kzg_multiproof_open_dev: evals_dev is a HOST array of nvectors device pointers; every other argument stays host memory.
+ * plonk_kzg_multiproof_last: what the last plonk_kzg_multiproof_open call on the handle ran as (items == 0 before the first);
+ *   the tests assert it against the plan computed on the host (plonk_amd/csrc/kzg_multiproof_core.hpp).
+ * plonk_kzg_multiproof_check: key is the ordinary opening key (third element [tau] h).  One weights kernel, ONE launch of
+ *   plonk_msm_points' kernels over [C_0 .. C_(M-1) | D | pi | g] with the scalars [s_j | -1 | t | -y] (per-term or buckets by
+ *   its own rule) and ONE host pairing: PLONK_OK or PLONK_ERR_VERIFY — a multiproof has one verdict.  Checks, in this order:
+ *   PLONK_ERR_ARG (as above, the pointers being key, commitments48, both index arrays, values, proof96; and log_n outside
+ *   [1, 20]); PLONK_ERR_DATA (a value or an override that is not canonical, an override t in the domain); PLONK_ERR_POINT (a
+ *   commitment, D or pi that does not decode or lies outside the subgroup; the compressed identity is legal); then the
+ *   pairing.  A transcript-drawn t inside the domain is PLONK_ERR_VERIFY: no prover returns such a proof.  info (may be NULL):
+ *   proofs = count, msm_terms = ncommitments + 3, pairing_checks = 1 and the phase times. */
+typedef struct plonk_kzg_multiproof_info {
+  uint32_t log_n;
+  uint32_t built_points;           /* 1: this call built the Lagrange points */
+  uint64_t items;                  /* K */
+  uint64_t vectors;                /* M */
+  uint64_t point_groups;           /* distinct point indexes among the items */
+  uint64_t commitments_computed;   /* M when commitments_in was NULL, else 0 */
+  uint64_t msm_launches;           /* commitments_computed + 2 */
+  uint64_t msm_terms;              /* terms of each: n */
+  uint64_t products;               /* field products of the aggregation pass: (K + 2 point_groups) x n */
+  uint64_t device_bytes;           /* what the multiproof state of the handle holds: invd, workspaces, staged vectors */
+} plonk_kzg_multiproof_info;
+int plonk_kzg_multiproof_open(plonk_kzg_domain* domain, const uint64_t* const* evals, uint64_t nvectors,
+                              const uint8_t* commitments_in /* nvectors x 48, or NULL: computed */, const uint32_t* vector_index,
+                              const uint32_t* point_index, uint64_t count, const uint8_t* label, uint64_t label_len,
+                              const uint64_t* challenges_override /* 8 limbs or NULL */, uint64_t* values /* count x 4 out: y_k */,
+                              uint8_t* commitments_out /* nvectors x 48 or NULL */, uint8_t proof96[96]);
+int plonk_kzg_multiproof_open_dev(plonk_kzg_domain* domain, const void* const* evals_dev, uint64_t nvectors, const uint8_t* commitments_in,
+                                  const uint32_t* vector_index, const uint32_t* point_index, uint64_t count, const uint8_t* label,
+                                  uint64_t label_len, const uint64_t* challenges_override, uint64_t* values, uint8_t* commitments_out,
+                                  uint8_t proof96[96]);
+int plonk_kzg_multiproof_last(plonk_kzg_domain* domain, plonk_kzg_multiproof_info* out);
+int plonk_kzg_multiproof_check(plonk_kzg_key* key, uint32_t log_n, const uint8_t* commitments48, uint64_t ncommitments,
+                               const uint32_t* vector_index, const uint32_t* point_index, const uint64_t* values, uint64_t count,
+                               const uint8_t proof96[96], const uint8_t* label, uint64_t label_len, const uint64_t* challenges_override,
+                               plonk_verify_info* info /* may be NULL */);
+
 /* ---- variable-base MSM over caller-supplied points ------------------------------------------------
  * sum_i scalars[i] * P_i for points the CALLER brings — the reference's msm_variable_base (the primitive under Proof::verify
  * and OpeningKey::batch_check) — where plonk_msm / _batch / _dev run over the loaded commit key and its precomputed tables.
@@ -1151,6 +1224,8 @@ int plonk_prover_diagnose_inputs(plonk_prover* p, const uint64_t* inputs, uint64
  *   polynomials with its copies, the powers of v and every fold + evaluate launch (in the host form NOT the uploads the
  *   launches wait for, nor the polynomial commitments between them); 13 Ruffini (or the shift at the point 0); 14 the witness
  *   commitment, bit sums copied back included (its MSM kernels also count in slots 1 and 2).
+ *   plonk_kzg_multiproof_open / _open_dev (device events): 12 the aggregation pass, every aggregate and fix-up launch of the
+ *   call as one interval.
  *   plonk_msm_points / _dev, bucket path (device events): 15 load + recode (points, scalars, histogram), 22 scan + scatter,
  *   23 slice accumulation, 30 slice sums to bucket sums, 31 window sums.
  *   Slots 0 .. 31 are valid.

@@ -81,6 +81,7 @@ EXPORTS = [
     "plonk_kzg_cell_verifier_create", "plonk_kzg_cell_verifier_destroy", "plonk_kzg_verify_cells", "plonk_kzg_verify_cells_each",
     "plonk_kzg_cell_verifier_last",
     "plonk_kzg_recover_cells", "plonk_kzg_recover_cells_dev", "plonk_kzg_recover_last",
+    "plonk_kzg_multiproof_open", "plonk_kzg_multiproof_open_dev", "plonk_kzg_multiproof_last", "plonk_kzg_multiproof_check",
 ]
 
 # what bit f of plonk_unsat_row.families / slot f of plonk_unsat_info.family_rows stands for (include/plonk_hip.h); the
@@ -177,6 +178,13 @@ class _KzgRecoverInfo(ctypes.Structure):
                 ("count", ctypes.c_uint64), ("available", ctypes.c_uint64), ("missing", ctypes.c_uint64), ("max_len", ctypes.c_uint64),
                 ("chunk_polys", ctypes.c_uint64), ("transforms", ctypes.c_uint64), ("vanish_muls", ctypes.c_uint64),
                 ("workspace_bytes", ctypes.c_uint64), ("inconsistent", ctypes.c_uint64)]
+
+
+class _KzgMultiproofInfo(ctypes.Structure):
+    """plonk_kzg_multiproof_info (include/plonk_hip.h)"""
+    _fields_ = [("log_n", ctypes.c_uint32), ("built_points", ctypes.c_uint32), ("items", ctypes.c_uint64), ("vectors", ctypes.c_uint64),
+                ("point_groups", ctypes.c_uint64), ("commitments_computed", ctypes.c_uint64), ("msm_launches", ctypes.c_uint64),
+                ("msm_terms", ctypes.c_uint64), ("products", ctypes.c_uint64), ("device_bytes", ctypes.c_uint64)]
 
 
 class _KzgCellVerifyInfo(ctypes.Structure):
@@ -476,6 +484,11 @@ def load_library() -> ctypes.CDLL:
     lib.plonk_kzg_cell_verifier_last.argtypes = [vp, ctypes.POINTER(_KzgCellVerifyInfo)]
     lib.plonk_test_kzg_cell_verify_last_rho.argtypes = [vp, vp]   # test hooks of kzg_cell_verify.hip, not in the header
     lib.plonk_test_kzg_cell_verify_force_paths.argtypes = [vp, u32, u32]
+    lib.plonk_kzg_multiproof_open.argtypes = [vp, ctypes.POINTER(vp), u64, vp, vp, vp, u64, vp, u64, vp, vp, vp, vp]
+    lib.plonk_kzg_multiproof_open_dev.argtypes = [vp, ctypes.POINTER(vp), u64, vp, vp, vp, u64, vp, u64, vp, vp, vp, vp]
+    lib.plonk_kzg_multiproof_last.argtypes = [vp, ctypes.POINTER(_KzgMultiproofInfo)]
+    lib.plonk_kzg_multiproof_check.argtypes = [vp, u32, vp, u64, vp, vp, vp, u64, vp, vp, u64, vp, vp]
+    lib.plonk_test_kzg_multiproof_last_challenges.argtypes = [vp, vp]   # test hook of kzg_multiproof.hip, not in the header
     _lib = lib
     return lib
 
@@ -1528,6 +1541,14 @@ def kzg_flatten(ctx: Context, commitments, evaluations, v: int, witness: bytes) 
     return ctx.kzg_flatten(commitments, evaluations, v, witness)
 
 
+def _multi_challenges(challenges):
+    """(r, t) ints -> the 8 Montgomery limbs of challenges_override; bytes pass through; None stays None"""
+    if challenges is None or isinstance(challenges, (bytes, bytearray)):
+        return bytes(challenges) if challenges is not None else None
+    r, t = challenges
+    return fr_to_bytes_mont([r, t])
+
+
 class KzgKey:
     """An OpeningKey (240 bytes g || h || x_h, OpeningKey::to_bytes) bound to a context: plonk_kzg_key_create validates it like
     OpeningKey::from_bytes (raises InvalidData).  `batch_check` is OpeningKey::batch_check (reference key.rs:661-707),
@@ -1609,6 +1630,34 @@ class KzgKey:
 
     def check_each(self, points, proofs) -> list:
         return self.check_each_info(points, proofs)[0]
+
+    def check_multi_code(self, log_n: int, commitments, items, values, proof: bytes, label: bytes = b"", challenges=None):
+        """(return code of plonk_kzg_multiproof_check, plonk_verify_info as a dict).  items: (vector index, point index) pairs;
+        values: one int per item, or 32 Montgomery bytes (for the non-canonical cases); challenges: (r, t) ints, or 64 Montgomery
+        bytes."""
+        commitments, items, values = [bytes(c) for c in commitments], list(items), list(values)
+        if any(len(c) != 48 for c in commitments) or len(bytes(proof)) != 96:
+            raise ValueError("commitments are 48-byte compressed G1 points, a multiproof is 96 bytes")
+        if len(values) != len(items):
+            raise ValueError("one value per item")
+        n = max(len(items), 1)
+        vidx = (ctypes.c_uint32 * n)(*[it[0] for it in items])
+        midx = (ctypes.c_uint32 * n)(*[it[1] for it in items])
+        vals = b"".join(bytes(v) if isinstance(v, (bytes, bytearray)) else fr_to_bytes_mont([v]) for v in values) or b"\0"
+        info = _VerifyInfo()
+        rc = self.ctx.lib.plonk_kzg_multiproof_check(self.handle, log_n, b"".join(commitments) or None, len(commitments), vidx, midx, vals,
+                                                     len(items), bytes(proof), label, len(label), _multi_challenges(challenges),
+                                                     ctypes.byref(info))
+        return rc, {k: getattr(info, k) for k, _ in info._fields_}
+
+    def check_multi(self, log_n: int, commitments, items, values, proof: bytes, label: bytes = b"", challenges=None) -> bool:
+        """plonk_kzg_multiproof_check: True when the multiproof of KzgDomain.open_multi verifies, False when it does not
+        (PLONK_ERR_VERIFY); malformed input raises.  `challenges` = (r, t) replaces both challenges the library derives from a
+        fresh transcript over `label` and every input; a predictable r or t voids the check."""
+        rc, _ = self.check_multi_code(log_n, commitments, items, values, proof, label, challenges)
+        if rc not in (PLONK_OK, -12):
+            self.ctx._check(rc)
+        return rc == PLONK_OK
 
     def _pairing_each_values(self, a, b):
         """TEST HOOK: per check the final-exponentiated Fp12 value of e(-a, x_h) e(b, h) as 12 integers (tower order), from
@@ -1835,6 +1884,47 @@ class KzgDomain:
         info = _KzgEvalsInfo()
         self.ctx._check(self.ctx.lib.plonk_kzg_evals_last(self.handle, ctypes.byref(info)))
         return {k: getattr(info, k) for k, _ in info._fields_}
+
+    # ---- multiproofs: many (vector, domain point) openings, one 96-byte proof ----
+    def _open_multi(self, fn, ptrs, items, label, commitments, challenges):
+        items = list(items)
+        M, K = len(ptrs), len(items)
+        parr = (ctypes.c_void_p * max(M, 1))(*ptrs)
+        vidx = (ctypes.c_uint32 * max(K, 1))(*[it[0] for it in items])
+        midx = (ctypes.c_uint32 * max(K, 1))(*[it[1] for it in items])
+        cin = None
+        if commitments is not None:
+            cin = b"".join(bytes(c) for c in commitments)
+            if len(cin) != 48 * M:
+                raise ValueError("one 48-byte commitment per vector")
+        vals = ctypes.create_string_buffer(32 * max(K, 1))
+        cout = ctypes.create_string_buffer(48 * max(M, 1))
+        proof = ctypes.create_string_buffer(96)
+        self.ctx._check(fn(self.handle, parr, M, cin, vidx, midx, K, label, len(label), _multi_challenges(challenges), vals, cout, proof))
+        return fr_from_bytes_mont(vals.raw[:32 * K]), [cout.raw[48 * j:48 * j + 48] for j in range(M)], proof.raw
+
+    def open_multi(self, vectors, items, label: bytes = b"", commitments=None, challenges=None):
+        """plonk_kzg_multiproof_open: vectors of n values (lists of ints, or Montgomery bytes); items: (vector index, point index)
+        pairs -> (values, commitments, proof): the value of every item, the commitments the proof is bound to (those given, or
+        computed when `commitments` is None) and the 96-byte proof D || pi.  `challenges` = (r, t) replaces both transcript
+        challenges; a predictable r or t voids the check."""
+        keep, ptrs = self._host_vectors(vectors)
+        return self._open_multi(self.ctx.lib.plonk_kzg_multiproof_open, ptrs, items, label, commitments, challenges)
+
+    def open_multi_dev(self, ptrs, items, label: bytes = b"", commitments=None, challenges=None):
+        """plonk_kzg_multiproof_open_dev: the same for vectors resident in HBM (device pointers, n values each)"""
+        return self._open_multi(self.ctx.lib.plonk_kzg_multiproof_open_dev, list(ptrs), items, label, commitments, challenges)
+
+    def multi_last(self) -> dict:
+        info = _KzgMultiproofInfo()
+        self.ctx._check(self.ctx.lib.plonk_kzg_multiproof_last(self.handle, ctypes.byref(info)))
+        return {k: getattr(info, k) for k, _ in info._fields_}
+
+    def _multi_last_challenges(self):
+        """TEST HOOK: (r, t) of the last open_multi / open_multi_dev.  Not part of the C API."""
+        out = ctypes.create_string_buffer(64)
+        self.ctx._check(self.ctx.lib.plonk_test_kzg_multiproof_last_challenges(self.handle, out))
+        return tuple(fr_from_bytes_mont(out.raw))
 
     # ---- cell proofs: one proof per coset of l = 2^log_cell values ----
     def open_cells_bytes(self, polys_bytes, log_cell: int, commitments: bool = True):

@@ -256,7 +256,9 @@ struct KzgDomain : KzdBufs, DevBufs<KzdBufs::NBUF> {
   void* evals = nullptr;         // the Lagrange points and workspace of the evaluation-form calls (kzg_evals.hip); not in device_bytes()
   void* cells = nullptr;         // the A^(u) tables and workspace of the cell proofs (kzg_cells.hip); not in device_bytes()
   void* recover = nullptr;       // the workspace of the cell recovery (kzg_recover.hip); not in device_bytes()
-  ~KzgDomain() {   // in this order: the recovery state, the cell state, the evaluation-form state, the fixed buffers; the base frees the grow-only ones last
+  void* multi = nullptr;         // the invd table and workspace of the multiproofs (kzg_multiproof.hip); not in device_bytes()
+  ~KzgDomain() {   // in this order: the multiproof state, the recovery state, the cell state, the evaluation-form state, the fixed buffers; the base frees the grow-only ones last
+    kmp_release(multi);
     kzr_release(recover);
     kzc_release(cells);
     kze_release(evals);
@@ -268,7 +270,7 @@ struct KzgDomain : KzdBufs, DevBufs<KzdBufs::NBUF> {
 
 KzdView kzd_view(plonk_kzg_domain* dom) {
   KzgDomain* d = dom->d;
-  return KzdView{d->c, d->log_n, d->srs_gen == d->c->srs_gen, d->tw, &d->evals, &d->cells, d->ws_cap, &d->recover};
+  return KzdView{d->c, d->log_n, d->srs_gen == d->c->srs_gen, d->tw, &d->evals, &d->cells, d->ws_cap, &d->recover, &d->multi};
 }
 
 static int domain_create_body(Ctx& c, uint32_t log_n, KzgDomain* d) {

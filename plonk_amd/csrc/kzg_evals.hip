@@ -499,6 +499,11 @@ int evals_impl(const char* api_fn, plonk_kzg_domain* dom, const void* const* vec
 
 void kze_release(void* evals) { delete (KzgEvals*)evals; }
 
+int kze_points_ready(const KzdView& v, uint32_t* built) { return lagrange_ready(v, kze_state(v), built); }
+int kze_commit_values(const KzdView& v, const Fr* s, uint8_t out48[48]) {
+  return commit_values(v.c, kze_state(v), s, 1ull << v.log_n, out48);
+}
+
 }  // namespace plonk
 
 using namespace plonk;

@@ -49,9 +49,17 @@ struct KzdView {
   void** cells;            // the handle's slot for the state of kzg_cells.hip, released through kzc_release
   uint64_t ws_cap;         // the cap on the point workspace of a call
   void** recover;          // the handle's slot for the state of kzg_recover.hip, released through kzr_release
+  void** multi;            // the handle's slot for the state of kzg_multiproof.hip, released through kmp_release
 };
 KzdView kzd_view(plonk_kzg_domain* dom);
 void kze_release(void* evals);
 void kzr_release(void* recover);   // kzg_recover.hip
+void kmp_release(void* multi);     // kzg_multiproof.hip
+
+// What kzg_multiproof.hip shares with the evaluation-form calls of the handle: the resident Lagrange points (built by whichever
+// call commits first; *built = 1 when this one did) and the commitment over them, sum_i s[i] [L_i(tau)] G as 48 compressed
+// bytes (returns with the stream synchronised; plonk_ctx_last_msm_points keeps reporting the caller's own last call).
+int kze_points_ready(const KzdView& v, uint32_t* built);
+int kze_commit_values(const KzdView& v, const Fr* s, uint8_t out48[48]);
 
 }  // namespace plonk

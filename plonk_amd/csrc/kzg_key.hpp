@@ -21,7 +21,8 @@ struct KzgKey {
   G1Affine g_aff;        // g as decoded on the device
   Fr last_u, last_r;     // the challenges of the last batch_check / srs_check (test hook)
   void* pair_tables = nullptr;   // device: the lines of x_h and h for the pairing kernel, made by the first per-item call
-  ~KzgKey() { (void)hipFree(pair_tables); }
+  void* multiproof = nullptr;    // the workspace of plonk_kzg_multiproof_check (kzg_multiproof.hip), made by its first call
+  ~KzgKey();                     // kzg_multiproof.hip: frees both
 };
 
 }  // namespace plonk
