@@ -826,6 +826,38 @@ int plonk_kzg_open_evals_dev(plonk_kzg_domain* domain, const void* const* evals_
                              const uint64_t* v_challenge, uint64_t* evaluations, uint8_t* commitments48, uint8_t* witness48);
 int plonk_kzg_evals_last(plonk_kzg_domain* domain, plonk_kzg_evals_info* out);
 
+/* ---- Lagrange-basis tables on a domain handle (opt-in) -----------------------------------------------------
+ * By default the commitments and witnesses of the evaluation-form calls and of plonk_kzg_multiproof_open are table-free
+ * bucket MSMs over the handle's Lagrange points.  plonk_kzg_evals_tables_build gives the handle the table rows a prover's
+ * Lagrange-basis key has (the layout the context's rule gives a key that is built last; a forced table_mode forces it here
+ * too): from then on those calls run the prover's grouped table MSM, four commitments per launch, and return the same bytes.
+ * A call whose MSMs fit one group is finished on the host; a call with more queues all its groups and finishes and
+ * compresses their commitments on the device, up to 4096 per kernel launch.
+ * plonk_kzg_evals_tables_build: builds the Lagrange points if no call has yet, then the tables.  rows x n x 128 bytes count
+ *   against the context's table budget and show in plonk_ctx_table_bytes while the handle holds them: the documented
+ *   exception to "leaves the context as found".  A second call is PLONK_OK with built == 0.  PLONK_ERR_ARG for NULL or when
+ *   rows x n exceeds 2^31; PLONK_ERR_STATE once the context's key was reloaded, and on a context with a communicator.  A
+ *   failed build leaves the handle without tables and the budget as it was.
+ * plonk_kzg_evals_tables_drop: frees them (PLONK_OK when the handle holds none; works after a key reload);
+ *   plonk_kzg_domain_destroy drops them too.
+ * plonk_kzg_evals_tables_last: the tables the handle holds and how the last call that used them ran: the tests assert it
+ *   against the plan computed on the host (kze_tables_plan, plonk_amd/csrc/kzg_evals_core.hpp).  plonk_kzg_evals_last and
+ *   plonk_kzg_multiproof_last keep every field and meaning with tables present. */
+typedef struct plonk_kzg_evals_tables_info {
+  uint32_t log_n;
+  uint32_t table_rows;        /* 0: the handle holds no tables; else 16 / 64 / 128 / 256 */
+  uint64_t table_bytes;       /* rows x n x 128, counted in plonk_ctx_table_bytes while held */
+  uint32_t built;             /* 1: the last plonk_kzg_evals_tables_build call built them (0: they were there) */
+  uint32_t bucket_bits;       /* of the last table MSM on the handle (0 before the first) */
+  uint64_t msms;              /* last call that used the tables: commitments + witness / D / pi computed */
+  uint64_t group_launches;    /* grouped table MSM launches it made */
+  uint32_t device_finished;   /* 1: its commitments were finished and compressed on the device */
+  uint32_t reserved;
+} plonk_kzg_evals_tables_info;
+int plonk_kzg_evals_tables_build(plonk_kzg_domain* domain);
+int plonk_kzg_evals_tables_drop(plonk_kzg_domain* domain);
+int plonk_kzg_evals_tables_last(plonk_kzg_domain* domain, plonk_kzg_evals_tables_info* out);
+
 /* ---- KZG10 cell proofs: a polynomial opened on every coset of its domain --------------------------------
  * The n = 2^log_n evaluations of a polynomial cut into r = n / l cells of l = 2^log_cell values, each cell with ONE 48-byte
  * proof that opens all l of its values at once (Feist-Khovratovich section 3; data-availability sampling).  w is the generator

@@ -77,6 +77,7 @@ EXPORTS = [
     "plonk_kzg_open_domain_dev", "plonk_kzg_domain_last",
     "plonk_kzg_commit_evals", "plonk_kzg_commit_evals_dev", "plonk_kzg_open_evals", "plonk_kzg_open_evals_dev",
     "plonk_kzg_evals_last",
+    "plonk_kzg_evals_tables_build", "plonk_kzg_evals_tables_drop", "plonk_kzg_evals_tables_last",
     "plonk_kzg_open_cells", "plonk_kzg_open_cells_dev", "plonk_kzg_cell_points", "plonk_kzg_cells_last",
     "plonk_kzg_cell_verifier_create", "plonk_kzg_cell_verifier_destroy", "plonk_kzg_verify_cells", "plonk_kzg_verify_cells_each",
     "plonk_kzg_cell_verifier_last",
@@ -162,6 +163,13 @@ class _KzgEvalsInfo(ctypes.Structure):
     _fields_ = [("log_n", ctypes.c_uint32), ("built_points", ctypes.c_uint32), ("count", ctypes.c_uint64),
                 ("in_domain_index", ctypes.c_uint64), ("msm_launches", ctypes.c_uint64), ("msm_terms", ctypes.c_uint64),
                 ("lagrange_bytes", ctypes.c_uint64)]
+
+
+class _KzgEvalsTablesInfo(ctypes.Structure):
+    """plonk_kzg_evals_tables_info (include/plonk_hip.h)"""
+    _fields_ = [("log_n", ctypes.c_uint32), ("table_rows", ctypes.c_uint32), ("table_bytes", ctypes.c_uint64),
+                ("built", ctypes.c_uint32), ("bucket_bits", ctypes.c_uint32), ("msms", ctypes.c_uint64),
+                ("group_launches", ctypes.c_uint64), ("device_finished", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
 class _KzgCellsInfo(ctypes.Structure):
@@ -469,6 +477,9 @@ def load_library() -> ctypes.CDLL:
     lib.plonk_kzg_open_evals.argtypes = [vp, ctypes.POINTER(vp), u64, vp, vp, vp, vp, vp]
     lib.plonk_kzg_open_evals_dev.argtypes = [vp, ctypes.POINTER(vp), u64, vp, vp, vp, vp, vp]
     lib.plonk_kzg_evals_last.argtypes = [vp, ctypes.POINTER(_KzgEvalsInfo)]
+    lib.plonk_kzg_evals_tables_build.argtypes = [vp]
+    lib.plonk_kzg_evals_tables_drop.argtypes = [vp]
+    lib.plonk_kzg_evals_tables_last.argtypes = [vp, ctypes.POINTER(_KzgEvalsTablesInfo)]
     lib.plonk_kzg_open_cells.argtypes = [vp, u32, ctypes.POINTER(vp), ctypes.POINTER(u64), u64, vp, vp, vp]
     lib.plonk_kzg_open_cells_dev.argtypes = [vp, u32, ctypes.POINTER(vp), ctypes.POINTER(u64), u64, vp, vp, vp]
     lib.plonk_kzg_cell_points.argtypes = [vp, u32, vp, vp]
@@ -1885,6 +1896,20 @@ class KzgDomain:
         self.ctx._check(self.ctx.lib.plonk_kzg_evals_last(self.handle, ctypes.byref(info)))
         return {k: getattr(info, k) for k, _ in info._fields_}
 
+    # ---- opt-in Lagrange-basis tables: the MSMs of the evaluation-form calls and multiproofs as grouped table launches ----
+    def tables_last(self) -> dict:
+        info = _KzgEvalsTablesInfo()
+        self.ctx._check(self.ctx.lib.plonk_kzg_evals_tables_last(self.handle, ctypes.byref(info)))
+        return {k: getattr(info, k) for k, _ in info._fields_ if k != "reserved"}
+
+    def build_tables(self) -> dict:
+        """plonk_kzg_evals_tables_build: rows x n x 128 bytes of the context's table budget until drop_tables / close"""
+        self.ctx._check(self.ctx.lib.plonk_kzg_evals_tables_build(self.handle))
+        return self.tables_last()
+
+    def drop_tables(self):
+        self.ctx._check(self.ctx.lib.plonk_kzg_evals_tables_drop(self.handle))
+
     # ---- multiproofs: many (vector, domain point) openings, one 96-byte proof ----
     def _open_multi(self, fn, ptrs, items, label, commitments, challenges):
         items = list(items)
@@ -2054,6 +2079,7 @@ class KzgDomain:
     def close(self):
         if getattr(self, "handle", None):
             if getattr(self.ctx, "handle", None):
+                self.ctx.lib.plonk_kzg_evals_tables_drop(self.handle)   # the table budget first, then the handle
                 self.ctx.lib.plonk_kzg_domain_destroy(self.handle)
             self.handle = None
 

@@ -143,16 +143,18 @@ static int ensure_ntt_staging(Ctx* c, uint64_t n) {
   return PLONK_OK;
 }
 
-int msm_group_sums(Ctx* c, const Fr* const* scalars_dev, const uint64_t* m, int cnt, G1* sums) {
+int msm_group_sums(Ctx* c, const Fr* const* scalars_dev, const uint64_t* m, int cnt, G1* sums, const void* table, uint64_t table_n,
+                   uint32_t table_rows) {
   G1* res[MSM_MAX_BATCH];
   for (int k = 0; k < cnt; ++k) res[k] = (G1*)c->msm.result + (size_t)k * MSM_BIT_SUMS;
-  const int rc = msm_batch_device(c, scalars_dev, m, cnt, res, true);
+  const int rc = msm_batch_device(c, scalars_dev, m, cnt, res, true, table, table_n, nullptr, nullptr, table_rows);
   if (rc) return rc;
+  const uint32_t rows = table ? table_rows : c->srs_rows;
   HIP_TRY(hipMemcpyAsync(c->msm.result_host, c->msm.result, sizeof(G1) * MSM_BIT_SUMS * cnt, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   for (int k = 0; k < cnt; ++k)
     sums[k] = finish_bit_sums(reinterpret_cast<const G1*>(c->msm.result_host) + (size_t)k * MSM_BIT_SUMS, c->msm.last_rowbits,
-                              c->srs_rows == MSM_ROWS_BITPOS);
+                              rows == MSM_ROWS_BITPOS);
   return PLONK_OK;
 }
 

@@ -8,6 +8,7 @@
 // the prime-order-subgroup half of from_bytes is srs_validate_kernel's job (msm.hip) on the decoded points.
 #pragma once
 #include "curve.cuh"
+#include "curve28.cuh"
 
 namespace plonk {
 
@@ -54,6 +55,29 @@ HD int g1_decompress48(const uint8_t* in, G1Affine* out) {
   out->x = xm;
   out->y = y;
   return G1DEC_OK;
+}
+
+// G1Affine::to_bytes of an XYZZ point over Fp28: the 48 bytes as 12 words in memory order (w[0]'s low byte is byte 0: the
+// flags and the top bits of x).  One safegcd inverse; the identity is 0xC0 then zeros.  The lane function of kzd_finish_kernel
+// (kzg_domain.hip) and kze_finish_kernel (kzg_evals.hip).
+HD void g1r_compress48_words(const G1R& p, uint32_t w[12]) {
+#pragma unroll
+  for (int k = 0; k < 12; ++k) w[k] = 0;
+  if (p.is_identity()) {
+    w[0] = 0xC0u;
+    return;
+  }
+  Fp28 x, y;
+  g1r_to_affine(p, &x, &y);
+  const Fp xc = x.to_fp().from_mont(), yc = y.to_fp().from_mont();
+#pragma unroll
+  for (int k = 0; k < 12; ++k) w[k] = __builtin_bswap32(xc.l[11 - k]);
+  bool larger = false;   // y > (p - 1) / 2 = p >> 1
+  for (int k = 11; k >= 0; --k) {
+    const uint32_t half = (FpP::MOD[k] >> 1) | (k < 11 ? FpP::MOD[k + 1] << 31 : 0u);
+    if (yc.l[k] != half) { larger = yc.l[k] > half; break; }
+  }
+  w[0] |= 0x80u | (larger ? 0x20u : 0u);
 }
 
 }  // namespace plonk

@@ -28,6 +28,7 @@
 #include "plonk_internal.hpp"
 #include "api_guard.hpp"
 #include "hostg1.hpp"
+#include "g1codec.cuh"
 #include "kzg_core.hpp"
 #include "kzg_domain.hpp"
 #include "kzg_evals.hpp"
@@ -132,23 +133,7 @@ __global__ void __launch_bounds__(KZD_LANES) kzd_finish_kernel(const G1RSlot* __
   if (i >= n) return;
   const G1R p = ld_g1r(v + (uint64_t)blockIdx.y * stride + offset + (bitrev ? kzd_rev(i, log_n) : i));
   uint32_t w[12];
-#pragma unroll
-  for (int k = 0; k < 12; ++k) w[k] = 0;
-  if (p.is_identity()) {
-    w[0] = 0xC0u;
-  } else {
-    Fp28 x, y;
-    g1r_to_affine(p, &x, &y);
-    const Fp xc = x.to_fp().from_mont(), yc = y.to_fp().from_mont();
-#pragma unroll
-    for (int k = 0; k < 12; ++k) w[k] = __builtin_bswap32(xc.l[11 - k]);
-    bool larger = false;   // y > (p - 1) / 2 = p >> 1
-    for (int k = 11; k >= 0; --k) {
-      const uint32_t half = (FpP::MOD[k] >> 1) | (k < 11 ? FpP::MOD[k + 1] << 31 : 0u);
-      if (yc.l[k] != half) { larger = yc.l[k] > half; break; }
-    }
-    w[0] |= 0x80u | (larger ? 0x20u : 0u);
-  }
+  g1r_compress48_words(p, w);
   uint4* q = reinterpret_cast<uint4*>(out48 + 48ull * ((uint64_t)blockIdx.y * n + i));
   q[0] = make_uint4(w[0], w[1], w[2], w[3]);
   q[1] = make_uint4(w[4], w[5], w[6], w[7]);

@@ -13,8 +13,11 @@
 //                         are summed by shuffles, kze_final_kernel adds them per vector and applies -(z^n - 1) / n
 //   kze_quotient_kernel   q[i] = (F[i] - Y) / (w^i - z); inside the domain also the block partials of sum q[i] w^i, from
 //   kze_qfix_kernel       which one lane writes q[m] = -w^(-m) sum
+//   kze_finish_kernel     a handle with tables, a call of more than one MSM group: the bit sums of up to KZE_FINISH_CHUNK
+//                         commitments -> their 48 compressed bytes, one lane per commitment (kzg_evals_finish.cuh, g1codec.cuh)
 // Commitments and the witness go through msm_points_run over the resident Lagrange points: no tables, nothing of the
-// context's table budget.
+// context's table budget.  A handle that was given tables (plonk_kzg_evals_tables_build) runs them as
+// grouped launches of msm_batch_device over those tables instead: same bytes out.
 #include <hip/hip_runtime.h>
 
 #include <mutex>
@@ -27,15 +30,18 @@
 #include "poly.hpp"
 #include "devmem.cuh"
 #include "hostg1.hpp"
+#include "g1codec.cuh"
 #include "kzg_core.hpp"
 #include "kzg_domain.hpp"
 #include "kzg_evals.hpp"
+#include "kzg_evals_finish.cuh"
 
 namespace plonk {
 
 namespace {
 
 static_assert(sizeof(G1Affine) == KZE_POINT_BYTES, "point size");
+static_assert(KZE_TABLE_GROUP == (uint32_t)MSM_MAX_BATCH, "vectors per table launch");
 
 constexpr uint32_t KZE_POINT_LANES = 64;   // one wave per workgroup in the point kernels, as kzg_domain.hip
 
@@ -197,6 +203,30 @@ __global__ void __launch_bounds__(256) kze_qfix_kernel(const Fr* __restrict__ qp
   if (!t) st_fr(q + m, sh[0] * neg_w_inv_m);
 }
 
+// ---- the commitments of a call on a handle with tables --------------------------------------------------------------------
+// A lane owns a commitment: the Horner chain over its MSM_BIT_SUMS slots (one accumulator, the addend loaded where it is
+// used), one safegcd inverse, the encoding.  A slot is read once, 192 bytes by 16-byte words; a launch moves at most
+// 4096 x 21 x 192 B = 16.5 MB and runs ~36 point operations per lane: it is bound by the chain's latency, not by memory.
+namespace {
+struct KzeBitsLoad {
+  const G1* b;
+  __device__ G1R operator()(int slot) const { return g1r_of_g1(ld_g1(b + slot)); }
+};
+}  // namespace
+__global__ void __launch_bounds__(KZE_FINISH_LANES) kze_finish_kernel(const G1* __restrict__ bits, uint32_t count, int rb, int bitpos,
+                                                                      uint8_t* __restrict__ out48) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= count) return;
+  const KzeBitsLoad ld = {bits + (uint64_t)i * MSM_BIT_SUMS};
+  const G1R acc = kze_finish_chain(ld, rb, bitpos != 0);
+  uint32_t w[12];
+  g1r_compress48_words(acc, w);
+  uint4* q = reinterpret_cast<uint4*>(out48 + 48ull * i);
+  q[0] = make_uint4(w[0], w[1], w[2], w[3]);
+  q[1] = make_uint4(w[4], w[5], w[6], w[7]);
+  q[2] = make_uint4(w[8], w[9], w[10], w[11]);
+}
+
 // ---- launchers (kzg_evals.hpp) -----------------------------------------------------------------------------------------------
 int kze_lagrange_points(Ctx* c, uint32_t log_n, const GlvScalar* tw, uint32_t tw_log, G1Affine* out) {
   const uint64_t n = 1ull << log_n;
@@ -256,17 +286,44 @@ int kze_quotient(Ctx* c, uint32_t log_n, const Fr* fold, const Fr* inv, const Fr
   return PLONK_OK;
 }
 
+int kze_finish(Ctx* c, const G1* bits, uint32_t count, int rb, bool bitpos, uint8_t* out48) {
+  // rb + 9 slots are read of the MSM_BIT_SUMS a commitment has
+  if (!bits || !out48 || !count || rb < 8 || rb + 9 > MSM_BIT_SUMS) return (set_last_error("invalid argument", __func__, __FILE__, __LINE__), PLONK_ERR_ARG);
+  hipLaunchKernelGGL(kze_finish_kernel, dim3((count + KZE_FINISH_LANES - 1) / KZE_FINISH_LANES), dim3(KZE_FINISH_LANES), 0, c->stream, bits,
+                     count, rb, bitpos ? 1 : 0, out48);
+  HIP_TRY(hipGetLastError());
+  return PLONK_OK;
+}
+
 // ---- the state a handle holds for these calls ------------------------------------------------------------------------------
 namespace {
 
 struct KzeBufs {
-  enum { DEN, FOLD, Q, PARTIAL, EVALS, VPOW, VECS, META, QPART, NBUF };   // grow-only
+  enum { DEN, FOLD, Q, PARTIAL, EVALS, VPOW, VECS, META, QPART, BITS, FIN48, NBUF };   // grow-only
 };
 struct KzgEvals : KzeBufs, DevBufs<KzeBufs::NBUF> {
   G1Affine* lag = nullptr;      // [L_i(tau)] G, i < n
   uint64_t lag_bytes = 0;
   plonk_kzg_evals_info last = {};
-  ~KzgEvals() { (void)hipFree(lag); }
+  // opt-in (plonk_kzg_evals_tables_build): table rows over `lag`, held against the context's table budget
+  Ctx* tab_ctx = nullptr;
+  void* table = nullptr;
+  uint32_t tab_rows = 0;
+  uint64_t tab_n = 0;
+  plonk_kzg_evals_tables_info tl = {};   // built, bucket_bits and the counters of the last call that used the tables
+  std::vector<uint8_t> fin_host;         // the compressed commitments of a chunk on their way to the caller
+  void drop_tables() {
+    if (!table) return;
+    (void)hipStreamSynchronize(tab_ctx->stream);
+    srs_table_release(tab_ctx, table, tab_rows, tab_n);
+    table = nullptr;
+    tab_rows = 0;
+    tl = {};
+  }
+  ~KzgEvals() {
+    drop_tables();
+    (void)hipFree(lag);
+  }
 };
 
 KzgEvals* kze_state(const KzdView& v) {
@@ -293,7 +350,7 @@ int lagrange_ready(const KzdView& v, KzgEvals* e, uint32_t* built) {
 
 // sum_i s[i] [L_i(tau)] G as 48 compressed bytes (returns with the stream synchronised); plonk_ctx_last_msm_points keeps
 // reporting the caller's own last call
-int commit_values(Ctx* c, const KzgEvals* e, const Fr* s, uint64_t n, uint8_t out48[48]) {
+int commit_values_points(Ctx* c, const KzgEvals* e, const Fr* s, uint64_t n, uint8_t out48[48]) {
   const plonk_msm_points_info keep = c->last_points;
   const bool keep_valid = c->last_points_valid;
   MpInput in;
@@ -309,6 +366,121 @@ int commit_values(Ctx* c, const KzgEvals* e, const Fr* s, uint64_t n, uint8_t ou
   g1_compress97(aff[0], out48);
   return PLONK_OK;
 }
+
+// One run of table MSMs of a call on a handle that holds tables (kzg_evals_core.hpp kze_tables_plan): add() queues the
+// grouped launches of the vectors it is given, finish() ends the run.  A run planned as ONE launch is finished on the host,
+// as msm_group_sums does for the commit key.  A longer run writes the bit sums of its launches side by side into the handle's
+// array and turns a full chunk (and what is left at the end) into compressed bytes by kze_finish_kernel, one copy and one
+// synchronisation.  While the run lives the context's last_plan and acc_done are put aside: plonk_ctx_last_msm keeps
+// describing the caller's own last MSM, and no event of a prover is recorded by these launches.
+struct TableRun {
+  Ctx* c = nullptr;
+  KzgEvals* e = nullptr;
+  uint64_t n = 0;
+  bool device = false;
+  uint32_t cap = 0, pending = 0;   // commitments the bit-sum array holds / that wait in it
+  int rb = 0;
+  std::vector<uint8_t*> dest;      // where the 48 bytes of each waiting commitment go
+  plonk_msm_plan_internal keep_plan;
+  hipEvent_t keep_acc = nullptr;
+  TableRun() = default;
+  TableRun(const TableRun&) = delete;
+  TableRun& operator=(const TableRun&) = delete;
+  ~TableRun() {
+    if (!c) return;
+    c->last_plan = keep_plan;
+    c->acc_done = keep_acc;
+  }
+  // launches / entries: of the whole run, as planned
+  int begin(Ctx* ctx, KzgEvals* ev, uint64_t points, uint64_t launches, uint64_t entries) {
+    e = ev;
+    n = points;
+    device = launches > 1;
+    PTRY(msm_reserve(ctx, n));   // msm_group_sums reads the scratch's result slots before its launch reserves anything
+    if (device) {
+      cap = (uint32_t)(entries < KZE_FINISH_CHUNK ? entries : KZE_FINISH_CHUNK);
+      PTRY(e->need(KzgEvals::BITS, sizeof(G1) * MSM_BIT_SUMS * cap));
+      PTRY(e->need(KzgEvals::FIN48, 48ull * cap));
+      e->fin_host.resize(48ull * cap);
+      dest.reserve(cap);
+    }
+    c = ctx;
+    keep_plan = c->last_plan;
+    keep_acc = c->acc_done;
+    c->acc_done = nullptr;
+    return PLONK_OK;
+  }
+  // out48[k]: where the commitment of s[k] goes, k < cnt
+  int add(const Fr* const* s, uint32_t cnt, uint8_t* const* out48) {
+    uint64_t m[MSM_MAX_BATCH];
+    for (int k = 0; k < MSM_MAX_BATCH; ++k) m[k] = n;
+    for (uint32_t k0 = 0; k0 < cnt;) {
+      uint32_t g = cnt - k0 < (uint32_t)MSM_MAX_BATCH ? cnt - k0 : (uint32_t)MSM_MAX_BATCH;
+      if (!device) {
+        G1 sums[MSM_MAX_BATCH];
+        uint8_t aff[MSM_MAX_BATCH][97];
+        PTRY(msm_group_sums(c, s + k0, m, (int)g, sums, e->table, e->tab_n, e->tab_rows));
+        batch_xyzz_to_affine97(sums, (int)g, aff);
+        for (uint32_t k = 0; k < g; ++k) g1_compress97(aff[k], out48[k0 + k]);
+      } else {
+        if (g > cap - pending) g = cap - pending;   // (chunks end on a launch boundary for every plan; the array's bound)
+        G1* out[MSM_MAX_BATCH];
+        for (uint32_t k = 0; k < g; ++k) {
+          out[k] = e->at<G1>(KzgEvals::BITS) + (uint64_t)(pending + k) * MSM_BIT_SUMS;
+          dest.push_back(out48[k0 + k]);
+        }
+        PTRY(msm_batch_device(c, s + k0, m, (int)g, out, true, e->table, e->tab_n, nullptr, nullptr, e->tab_rows));
+        if (rb && rb != c->msm.last_rowbits) return (set_last_error("kzg_evals", "the launches of a run disagree on the layout of their bit sums", __FILE__, __LINE__), PLONK_ERR_STATE);
+        rb = c->msm.last_rowbits;
+        pending += g;
+      }
+      e->tl.bucket_bits = c->last_plan.bucket_bits;
+      e->tl.msms += g;
+      ++e->tl.group_launches;
+      k0 += g;
+      if (device && pending == cap) PTRY(flush());
+    }
+    return PLONK_OK;
+  }
+  int flush() {
+    if (!pending) return PLONK_OK;
+    PTRY(kze_finish(c, e->at<G1>(KzgEvals::BITS), pending, rb, e->tab_rows == MSM_ROWS_BITPOS, e->at<uint8_t>(KzgEvals::FIN48)));
+    HIP_TRY(hipMemcpyAsync(e->fin_host.data(), e->p[KzgEvals::FIN48], 48ull * pending, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (uint32_t k = 0; k < pending; ++k) memcpy(dest[k], e->fin_host.data() + 48ull * k, 48);
+    dest.clear();
+    pending = 0;
+    e->tl.device_finished = 1;
+    return PLONK_OK;
+  }
+  int finish() { return device ? flush() : PLONK_OK; }
+};
+
+// the counters plonk_kzg_evals_tables_last reports of "the last call that used the tables" start here
+void tables_call_begin(KzgEvals* e) {
+  e->tl.msms = 0;
+  e->tl.group_launches = 0;
+  e->tl.device_finished = 0;
+}
+
+// commitments of `count` resident vectors, out48 + 48 j for s[j]: one after the other over the points, or one run over the tables
+int commit_list(Ctx* c, KzgEvals* e, const Fr* const* s, uint64_t count, uint64_t n, uint8_t* out48) {
+  if (!e->table) {
+    for (uint64_t j = 0; j < count; ++j) PTRY(commit_values_points(c, e, s[j], n, out48 + 48 * j));
+    return PLONK_OK;
+  }
+  const KzeTablesPlan tp = kze_tables_plan(count, count, 0, 0);
+  TableRun run;
+  PTRY(run.begin(c, e, n, tp.group_launches, count));
+  std::vector<uint8_t*> out(count);
+  for (uint64_t j = 0; j < count; ++j) out[j] = out48 + 48 * j;
+  for (uint64_t j = 0; j < count; j += KZE_GROUP) {   // (add() takes a 32-bit count)
+    const uint32_t cnt = (uint32_t)(count - j < KZE_GROUP ? count - j : KZE_GROUP);
+    PTRY(run.add(s + j, cnt, out.data() + j));
+  }
+  return run.finish();
+}
+int commit_values(Ctx* c, KzgEvals* e, const Fr* s, uint64_t n, uint8_t out48[48]) { return commit_list(c, e, &s, 1, n, out48); }
 
 // The call's vectors made resident group after group, `per` at most at a time: fn(first, cnt, ptrs) runs with ptrs[k] the
 // device address of vector first + k.  The resident form passes the caller's pointers through; the host form packs a group
@@ -394,11 +566,27 @@ int evals_body(const char* api_fn, const KzdView& dv, KzgEvals* e, const EvalsCa
   info.in_domain_index = mh.m;
   // ---- from here on the call writes ----
   if (plan.msm_launches) PTRY(lagrange_ready(dv, e, &info.built_points));
-  if (!a.open) {
-    PTRY(for_groups(&c, a.vecs, count, n, a.resident, plan, [&](uint32_t first, uint32_t cnt, const Fr* const* ptrs) -> int {
-      for (uint32_t k = 0; k < cnt; ++k) PTRY(commit_values(&c, e, ptrs[k], n, a.commitments48 + 48ull * (first + k)));
+  // the MSMs of the call: per vector over the points, or ONE run over the handle's tables — the commitments group after
+  // group as their vectors become resident, the witness last
+  const bool tabled = e->table && plan.msm_launches;
+  TableRun run;
+  if (tabled) {
+    const KzeTablesPlan tp = kze_tables_plan(a.commitments48 ? count : 0, plan.group_vectors, a.witness48 ? 1 : 0, 0);
+    tables_call_begin(e);
+    PTRY(run.begin(&c, e, n, tp.group_launches, tp.msms));
+  }
+  auto commit_group = [&](uint32_t first, uint32_t cnt, const Fr* const* ptrs) -> int {
+    if (!tabled) {
+      for (uint32_t k = 0; k < cnt; ++k) PTRY(commit_values_points(&c, e, ptrs[k], n, a.commitments48 + 48ull * (first + k)));
       return PLONK_OK;
-    }));
+    }
+    uint8_t* out[KZE_GROUP];
+    for (uint32_t k = 0; k < cnt; ++k) out[k] = a.commitments48 + 48ull * (first + k);
+    return run.add(ptrs, cnt, out);
+  };
+  if (!a.open) {
+    PTRY(for_groups(&c, a.vecs, count, n, a.resident, plan, commit_group));
+    if (tabled) PTRY(run.finish());
     info.lagrange_bytes = e->lag_bytes;
     e->last = info;
     return PLONK_OK;
@@ -430,8 +618,7 @@ int evals_body(const char* api_fn, const KzdView& dv, KzgEvals* e, const EvalsCa
     fa.count = cnt;
     fa.accumulate = first ? 1 : 0;
     PTRY(kze_fold_eval(&c, fa, e->at<Fr>(KzgEvals::EVALS) + first));
-    if (a.commitments48)
-      for (uint32_t k = 0; k < cnt; ++k) PTRY(commit_values(&c, e, ptrs[k], n, a.commitments48 + 48ull * (first + k)));
+    if (a.commitments48) PTRY(commit_group(first, cnt, ptrs));
     return PLONK_OK;
   }));
   std::vector<Fr> y(count);
@@ -446,8 +633,15 @@ int evals_body(const char* api_fn, const KzdView& dv, KzgEvals* e, const EvalsCa
     PTRY(e->need(KzgEvals::Q, sizeof(Fr) * n));
     PTRY(e->need(KzgEvals::QPART, sizeof(Fr) * kze_quotient_blocks(n)));
     PTRY(kze_quotient(&c, L, e->at<Fr>(KzgEvals::FOLD), e->at<Fr>(KzgEvals::DEN), Y, mh.m, e->at<Fr>(KzgEvals::Q), e->at<Fr>(KzgEvals::QPART)));
-    PTRY(commit_values(&c, e, e->at<Fr>(KzgEvals::Q), n, a.witness48));
+    if (tabled) {
+      const Fr* q = e->at<Fr>(KzgEvals::Q);
+      uint8_t* out = a.witness48;
+      PTRY(run.add(&q, 1, &out));
+    } else {
+      PTRY(commit_values_points(&c, e, e->at<Fr>(KzgEvals::Q), n, a.witness48));
+    }
   }
+  if (tabled) PTRY(run.finish());
   memcpy(a.evaluations, y.data(), sizeof(Fr) * count);
   info.lagrange_bytes = e->lag_bytes;
   e->last = info;
@@ -502,6 +696,13 @@ void kze_release(void* evals) { delete (KzgEvals*)evals; }
 int kze_points_ready(const KzdView& v, uint32_t* built) { return lagrange_ready(v, kze_state(v), built); }
 int kze_commit_values(const KzdView& v, const Fr* s, uint8_t out48[48]) {
   return commit_values(v.c, kze_state(v), s, 1ull << v.log_n, out48);
+}
+int kze_commit_list(const KzdView& v, const Fr* const* s, uint64_t count, uint8_t* out48) {
+  return commit_list(v.c, kze_state(v), s, count, 1ull << v.log_n, out48);
+}
+void kze_tables_call_begin(const KzdView& v) {
+  KzgEvals* e = kze_state(v);
+  if (e->table) tables_call_begin(e);
 }
 
 }  // namespace plonk
@@ -558,6 +759,72 @@ int plonk_kzg_evals_last(plonk_kzg_domain* dom, plonk_kzg_evals_info* out) {
     info = e->last.log_n ? e->last : info;
     info.lagrange_bytes = e->lag_bytes;
   }
+  *out = info;
+  return PLONK_OK;
+  });
+}
+
+int plonk_kzg_evals_tables_build(plonk_kzg_domain* dom) {
+  const char* const api_fn = __func__;
+  return plonk::api_guard(api_fn, [&]() -> int {
+  if (!dom) API_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
+  const KzdView dv = kzd_view(dom);
+  Ctx& c = *dv.c;
+  CTX_ENTER(c, api_fn);
+  HIP_TRY(hipSetDevice(c.device));
+  if (!dv.key_current) API_FAIL(PLONK_ERR_STATE, "the domain is bound to a commit key that was replaced on its context");
+  if (c.nccl_comm) API_FAIL(PLONK_ERR_STATE, "a context with a communicator holds only a range of the commit key");
+  KzgEvals* e = kze_state(dv);
+  if (e->table) {
+    e->tl.built = 0;
+    return PLONK_OK;
+  }
+  const uint64_t n = 1ull << dv.log_n;
+  // srs_table_build's refusal, before the points are allocated
+  if ((uint64_t)msm_table_rows(&c, n, true) * n > (1ull << 31)) API_FAIL(PLONK_ERR_ARG, "invalid argument: table rows * points must be <= 2^31");
+  uint32_t built_points = 0;
+  PTRY(lagrange_ready(dv, e, &built_points));
+  void* t = nullptr;
+  uint32_t rows = 0;
+  PTRY(srs_table_build(&c, e->lag, n, &t, &rows));
+  e->tab_ctx = &c;
+  e->table = t;
+  e->tab_rows = rows;
+  e->tab_n = n;
+  e->tl = {};
+  e->tl.built = 1;
+  return PLONK_OK;
+  });
+}
+
+int plonk_kzg_evals_tables_drop(plonk_kzg_domain* dom) {
+  const char* const api_fn = __func__;
+  return plonk::api_guard(api_fn, [&]() -> int {
+  if (!dom) API_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
+  const KzdView dv = kzd_view(dom);
+  Ctx& c = *dv.c;
+  CTX_ENTER(c, api_fn);
+  HIP_TRY(hipSetDevice(c.device));
+  if (*dv.evals) ((KzgEvals*)*dv.evals)->drop_tables();
+  return PLONK_OK;
+  });
+}
+
+int plonk_kzg_evals_tables_last(plonk_kzg_domain* dom, plonk_kzg_evals_tables_info* out) {
+  const char* const api_fn = __func__;
+  return plonk::api_guard(api_fn, [&]() -> int {
+  if (!dom || !out) API_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
+  const KzdView dv = kzd_view(dom);
+  Ctx& c = *dv.c;
+  CTX_ENTER(c, api_fn);
+  const KzgEvals* e = (const KzgEvals*)*dv.evals;
+  plonk_kzg_evals_tables_info info = {};
+  if (e && e->table) {
+    info = e->tl;
+    info.table_rows = e->tab_rows;
+    info.table_bytes = sizeof(G1AffineR) * (uint64_t)e->tab_rows * e->tab_n;
+  }
+  info.log_n = dv.log_n;
   *out = info;
   return PLONK_OK;
   });

@@ -61,5 +61,15 @@ void kmp_release(void* multi);     // kzg_multiproof.hip
 // bytes (returns with the stream synchronised; plonk_ctx_last_msm_points keeps reporting the caller's own last call).
 int kze_points_ready(const KzdView& v, uint32_t* built);
 int kze_commit_values(const KzdView& v, const Fr* s, uint8_t out48[48]);
+// the same for `count` resident vectors, out48[48 j] for s[j]: one after the other on a handle without tables, as ONE run of
+// grouped table launches on a handle that holds them (kzg_evals_core.hpp kze_tables_plan)
+int kze_commit_list(const KzdView& v, const Fr* const* s, uint64_t count, uint8_t* out48);
+// a call that may use the handle's tables starts here: what plonk_kzg_evals_tables_last reports of "the last call" is
+// counted from this point on (kze_commit_values / kze_commit_list add to it)
+void kze_tables_call_begin(const KzdView& v);
+
+// kze_finish_kernel: out48[48 i] = the compressed commitment of bits[MSM_BIT_SUMS i ...], i < count — the chain of
+// finish_bit_sums (rb row bits, bitpos: 2 W - S), the affine normalisation and G1Affine::to_bytes, one lane per commitment
+int kze_finish(Ctx* c, const G1* bits, uint32_t count, int rb, bool bitpos, uint8_t* out48);
 
 }  // namespace plonk

@@ -73,6 +73,41 @@ HD KzePlan kze_plan(uint32_t log_n, uint64_t count, bool commitments, bool witne
   return p;
 }
 
+// ---- a handle that holds Lagrange-basis tables (plonk_kzg_evals_tables_build) ------------------------------------------------
+// The MSMs of a call run as grouped table launches (msm_batch_device over the handle's tables), KZE_TABLE_GROUP vectors per
+// launch.  The commitments are grouped inside the groups the call makes its vectors resident by (`group_vectors` at a time:
+// KzePlan::group_vectors for the evaluation-form calls, all M at once for a multiproof), so a staging buffer is never read
+// after it was handed back.  `joined` MSMs follow the commitments in the same run, one launch each (the witness of an
+// opening); `separate` MSMs are needed by the host before the next can start (D and pi of a multiproof feed the transcript)
+// and are a run of their own each.  A run of ONE launch is finished on the host; a longer run queues all its launches, their
+// bit sums side by side, and finishes and compresses them on the device, KZE_FINISH_CHUNK commitments per kernel launch.
+static constexpr uint32_t KZE_TABLE_GROUP = 4;        // MSM_MAX_BATCH (kzg_evals.hip asserts it)
+static constexpr uint32_t KZE_FINISH_CHUNK = 4096;    // commitments whose bit sums the handle holds at a time
+static constexpr uint32_t KZE_FINISH_LANES = 64;      // lanes (= commitments) per workgroup of the finish kernel
+
+struct KzeTablesPlan {
+  uint64_t msms;              // commitments + joined + separate
+  uint64_t group_launches;    // msm_batch_device calls
+  uint32_t device_finished;   // the run of the commitments (and the joined MSMs) is finished on the device
+  uint64_t finish_launches;   // finish kernel launches (= copies = synchronisations of the device finish): one per chunk
+  uint64_t last_chunk;        // commitments of the last of them
+};
+HD KzeTablesPlan kze_tables_plan(uint64_t commitments, uint64_t group_vectors, uint64_t joined, uint64_t separate) {
+  KzeTablesPlan p;
+  p.msms = commitments + joined + separate;
+  uint64_t run = joined;
+  if (commitments) {
+    const uint64_t g = group_vectors ? group_vectors : 1, full = commitments / g, rem = commitments % g;
+    run += full * ((g + KZE_TABLE_GROUP - 1) / KZE_TABLE_GROUP) + (rem + KZE_TABLE_GROUP - 1) / KZE_TABLE_GROUP;
+  }
+  p.group_launches = run + separate;
+  p.device_finished = run > 1 ? 1u : 0u;
+  const uint64_t entries = commitments + joined;
+  p.finish_launches = p.device_finished ? (entries + KZE_FINISH_CHUNK - 1) / KZE_FINISH_CHUNK : 0;
+  p.last_chunk = p.device_finished ? entries - (p.finish_launches - 1) * KZE_FINISH_CHUNK : 0;
+  return p;
+}
+
 // plonk_kzg_commit_evals' pointer checks: PLONK_ERR_ARG or PLONK_OK
 HD int kze_check_commit(bool has_domain, bool has_evals, bool has_out, uint64_t count) {
   if (!has_domain) return PLONK_ERR_ARG;

@@ -393,10 +393,11 @@ int open_body(const char* api_fn, const KzdView& dv, KzgMulti* s, const OpenCall
   HIP_TRY(hipStreamSynchronize(c.stream));
   // ---- the commitments and r ----
   PTRY(kze_points_ready(dv, &info.built_points));
+  kze_tables_call_begin(dv);   // (a handle with tables: the M commitments are one run of grouped launches, D and pi one launch each)
   if (a.commitments_in) {
     memcpy(cm.data(), a.commitments_in, 48 * M);
   } else {
-    for (uint64_t j = 0; j < M; ++j) PTRY(kze_commit_values(dv, table[j], cm.data() + 48 * j));
+    PTRY(kze_commit_list(dv, table.data(), M, cm.data()));
   }
   Transcript tr(a.label, a.label_len);
   Fr r = a.r, t = a.t;

@@ -387,7 +387,10 @@ G1Aff64 xyzz_to_aff(const H1& p);
 // capi.hip: up to MSM_MAX_BATCH resident scalar sets over the commit key as ONE grouped launch, the bit sums copied back and
 // finished on the host (plonk_msm / plonk_msm_batch / the KZG opening calls): sums[k] = the commitment as an XYZZ point.
 // The caller has reserved the MSM scratch (msm_reserve) for the largest m; returns with the stream synchronised.
-int msm_group_sums(Ctx* c, const Fr* const* scalars_dev, const uint64_t* m, int cnt, G1* sums);
+// table != nullptr: over tables built by srs_table_build (table_n points, table_rows rows) instead of the commit key; the
+// finishing chain follows THAT key's rows.
+int msm_group_sums(Ctx* c, const Fr* const* scalars_dev, const uint64_t* m, int cnt, G1* sums, const void* table = nullptr,
+                   uint64_t table_n = 0, uint32_t table_rows = 0);
 // pairing.hip: per-item verdicts (plonk_kzg_pairing_check_each, plonk_kzg_check_each, plonk_verify_each).  Everything is
 // device memory and queued on the context's stream; only each_finish and pairing_tables_create synchronise it.
 static constexpr int EACH_LANES = 64;             // verify_each_sums_kernel: one wave per item, L terms in lanes [0, 32), R in [32, 64)

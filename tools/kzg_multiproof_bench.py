@@ -10,7 +10,10 @@ All end in a device synchronisation and are timed with the host clock, the bindi
 alternate in one process, `--runs` times each after a warm-up call.  One JSON line per (log_n, K): median, min and max of each
 and, from one extra profiled open_multi_dev, the device time of the aggregation pass (profile slot 12) as ns per product K n.
 
-    python tools/kzg_multiproof_bench.py [--logs 8,12,16,20] [--items 1,64,1024,16384] [--vectors 16] [--runs 5] [--old-cap 64]
+    python tools/kzg_multiproof_bench.py [--logs 8,12,16,20] [--items 1,64,1024,16384] [--vectors 16] [--runs 5] [--old-cap 64] [--tables]
+
+--tables adds the two opening routes on a second handle of the context that holds Lagrange-basis tables
+(KzgDomain.build_tables) to the same alternation, and the one-time cost of building them.
 """
 import argparse
 import json
@@ -51,6 +54,7 @@ def main():
     ap.add_argument("--vectors", type=int, default=16)
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--old-cap", type=int, default=64)
+    ap.add_argument("--tables", action="store_true", help="time both opening routes on a handle with Lagrange-basis tables as well")
     args = ap.parse_args()
     import plonk_amd as P
     Q = P.Q
@@ -65,6 +69,10 @@ def main():
         ctx.sync()
         buf.free()
         dom = P.KzgDomain(ctx, log_n)
+        tab, build_ms = None, 0.0
+        if args.tables:   # a second handle on the same context that holds Lagrange-basis tables
+            tab = P.KzgDomain(ctx, log_n)
+            build_ms = timed(tab.build_tables)
         key = P.KzgKey(ctx, key_bytes)
         rnd = random.Random(log_n)
         vecs = []
@@ -99,12 +107,24 @@ def main():
                 reps = (K + cap - 1) // cap
                 assert key.check_each((points * reps)[:K], (proofs * reps)[:K]) == [0] * K
 
+            def tab_new_open():
+                out["tab_new"] = tab.open_multi_dev(ptrs, items, label, commitments=cm)
+
+            def tab_old_open():
+                out["tab_old"] = [tab.open_evals_dev([ptrs[j]], w[m], None, commitments=False) for j, m in items[:cap]]
+
             new_open(), new_check(), old_open(), old_check()                       # the warm-up; every proof verifies
             assert [ev[0] for ev, _, _ in out["old"]] == out["new"][0][:cap], "the two routes disagree on the values"
-            t = {name: [] for name in ("new_open", "new_check", "old_open", "old_check")}
+            if tab is not None:
+                tab_new_open(), tab_old_open()
+                assert out["tab_new"] == out["new"] and out["tab_old"] == out["old"], "a handle with tables gives other bytes"
+            t = {name: [] for name in ("new_open", "new_check", "old_open", "old_check", "tab_new_open", "tab_old_open")}
             for _ in range(args.runs):
                 t["new_open"].append(timed(new_open))
                 t["old_open"].append(timed(old_open))
+                if tab is not None:
+                    t["tab_new_open"].append(timed(tab_new_open))
+                    t["tab_old_open"].append(timed(tab_old_open))
                 t["new_check"].append(timed(new_check))
                 t["old_check"].append(timed(old_check))
             ctx.profile(True)
@@ -113,15 +133,21 @@ def main():
             agg_ms = ctx.profile_read(AGGREGATION_SLOT)[0]
             ctx.profile(False)
             scale = K / cap
-            print(json.dumps({"log_n": log_n, "vectors": M, "items": K, "runs": args.runs,
-                              "open_multi_dev": stats(t["new_open"]), "check_multi": stats(t["new_check"]),
-                              "open_evals_dev_x_items": stats(t["old_open"], scale), "check_each": stats(t["old_check"]),
-                              "extrapolated_from": cap if cap < K else None, "proof_bytes": {"new": 96, "old": 48 * K},
-                              "profiled_open_multi_dev_ms": round(wall, 3), "aggregation_ms": round(agg_ms, 3),
-                              "aggregation_ns_per_product": round(agg_ms * 1e6 / (K * n), 4),
-                              "multi_last": dom.multi_last()}), flush=True)
+            line = {"log_n": log_n, "vectors": M, "items": K, "runs": args.runs,
+                    "open_multi_dev": stats(t["new_open"]), "check_multi": stats(t["new_check"]),
+                    "open_evals_dev_x_items": stats(t["old_open"], scale), "check_each": stats(t["old_check"]),
+                    "extrapolated_from": cap if cap < K else None, "proof_bytes": {"new": 96, "old": 48 * K},
+                    "profiled_open_multi_dev_ms": round(wall, 3), "aggregation_ms": round(agg_ms, 3),
+                    "aggregation_ns_per_product": round(agg_ms * 1e6 / (K * n), 4),
+                    "multi_last": dom.multi_last()}
+            if tab is not None:
+                line["tables"] = {"open_multi_dev": stats(t["tab_new_open"]), "open_evals_dev_x_items": stats(t["tab_old_open"], scale),
+                                  "build_ms": round(build_ms, 3), "tables_last": tab.tables_last()}
+            print(json.dumps(line), flush=True)
         for b in vecs:
             b.free()
+        if tab is not None:
+            tab.close()
         key.close()
         dom.close()
         ctx.close()
