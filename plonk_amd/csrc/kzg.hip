@@ -287,10 +287,6 @@ static int check_reserve(KzgWork& w, uint64_t npts, uint64_t nterms) {
   return PLONK_OK;
 }
 
-static double ms_between(std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
-  return std::chrono::duration<double, std::milli>(b - a).count();
-}
-
 static void compress_h1(const H1& s, uint8_t out48[48]) {
   const G1Aff64 a = xyzz_to_aff(s);
   uint8_t raw[97];

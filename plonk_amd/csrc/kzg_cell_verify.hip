@@ -248,13 +248,8 @@ __global__ void __launch_bounds__(KZV_SUMS_LANES) kzv_cell_sums_kernel(const Fr*
 }
 
 // ---- launchers (kzg_cell_verify.hpp) ------------------------------------------------------------------------------------------
-static int kzv_bad_args(const char* what) {
-  set_last_error(what, "invalid argument", __FILE__, __LINE__);
-  return PLONK_ERR_ARG;
-}
-
 int kzv_key_copy(Ctx* c, uint64_t count, G1Affine* out) {
-  if (!c->srs_table || !count || count > c->srs_n) return kzv_bad_args("kzv_key_copy");
+  if (!c->srs_table || !count || count > c->srs_n) return kzg_bad_args("kzv_key_copy");
   hipLaunchKernelGGL(kzv_key_kernel, dim3((uint32_t)((count + 63) / 64)), dim3(64), 0, c->stream, (const G1AffineR*)c->srs_table,
                      (uint32_t)count, out);
   HIP_TRY(hipGetLastError());
@@ -264,7 +259,7 @@ int kzv_key_copy(Ctx* c, uint64_t count, G1Affine* out) {
 int kzv_twist(Ctx* c, const Fr* values, const uint32_t* cell_index, const Fr* weights, uint64_t count, uint32_t log_cell,
               const Fr* winv, const Fr* itw, Fr* out, uint32_t* flags) {
   if (log_cell < 1 || log_cell > KZC_NTT_MAX_LOG || !count || count > KZV_MAX_ITEMS || (count << log_cell) > KZV_MAX_VALUES)
-    return kzv_bad_args("kzv_twist");
+    return kzg_bad_args("kzv_twist");
   hipLaunchKernelGGL(kzv_twist_kernel, dim3((uint32_t)kzv_twist_groups(log_cell, count)), dim3(KZV_LANES), kzv_twist_lds_bytes(log_cell),
                      c->stream, values, cell_index, weights, (uint32_t)count, log_cell, winv, itw, Fr::from_u64(1ull << log_cell).inv(),
                      out, flags);
@@ -273,7 +268,7 @@ int kzv_twist(Ctx* c, const Fr* values, const uint32_t* cell_index, const Fr* we
 }
 
 int kzv_colsum(Ctx* c, const Fr* rows, uint64_t count, uint32_t log_cell, Fr* part0, Fr* part1, uint32_t* sc, uint32_t* ids) {
-  if (log_cell < 1 || log_cell > KZC_NTT_MAX_LOG || !count || count > KZV_MAX_ITEMS) return kzv_bad_args("kzv_colsum");
+  if (log_cell < 1 || log_cell > KZC_NTT_MAX_LOG || !count || count > KZV_MAX_ITEMS) return kzg_bad_args("kzv_colsum");
   const uint32_t gx = ((1u << log_cell) + KZV_COLSUM_LANES - 1) / KZV_COLSUM_LANES;
   Fr* part[2] = {part0, part1};
   int b = 0;
@@ -293,7 +288,7 @@ int kzv_colsum(Ctx* c, const Fr* rows, uint64_t count, uint32_t log_cell, Fr* pa
 
 int kzv_weights(Ctx* c, const Fr* pw, const uint32_t* cell_index, const Fr* xk, const uint32_t* perm, const uint32_t* off, uint64_t K,
                 uint64_t M, uint32_t log_cell, uint32_t* sc, uint32_t* ids) {
-  if (!K || K > KZV_MAX_ITEMS || M > KZV_MAX_COMMITMENTS) return kzv_bad_args("kzv_weights");
+  if (!K || K > KZV_MAX_ITEMS || M > KZV_MAX_COMMITMENTS) return kzg_bad_args("kzv_weights");
   hipLaunchKernelGGL(kzv_weights_kernel, dim3((uint32_t)(M + (K + 63) / 64)), dim3(64), 0, c->stream, pw, cell_index, xk, perm, off,
                      (uint32_t)K, (uint32_t)M, log_cell, sc, ids);
   HIP_TRY(hipGetLastError());
@@ -303,7 +298,7 @@ int kzv_weights(Ctx* c, const Fr* pw, const uint32_t* cell_index, const Fr* xk, 
 int kzv_cell_sums(Ctx* c, const Fr* coeffs, const uint32_t* commitment_index, const uint32_t* cell_index, const Fr* xk,
                   const uint32_t* flags, const G1Affine* pts, const int32_t* kind, uint64_t K, uint64_t M, uint32_t log_cell, G1* pairs,
                   int32_t* pre) {
-  if (log_cell < 1 || log_cell > KZC_NTT_MAX_LOG || !K || K > KZV_MAX_ITEMS || M > KZV_MAX_COMMITMENTS) return kzv_bad_args("kzv_cell_sums");
+  if (log_cell < 1 || log_cell > KZC_NTT_MAX_LOG || !K || K > KZV_MAX_ITEMS || M > KZV_MAX_COMMITMENTS) return kzg_bad_args("kzv_cell_sums");
   hipLaunchKernelGGL(kzv_cell_sums_kernel, dim3((uint32_t)K), dim3(KZV_SUMS_LANES), 0, c->stream, coeffs, commitment_index, cell_index, xk,
                      flags, pts, kind, (uint32_t)M, log_cell, pairs, pre);
   HIP_TRY(hipGetLastError());
@@ -334,10 +329,6 @@ struct KzgCellVerifier : KzvBufs, DevBufs<KzvBufs::NBUF> {
     (void)hipFree(itw);
   }
 };
-
-double ms_between(std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
-  return std::chrono::duration<double, std::milli>(b - a).count();
-}
 
 int create_body(const char* api_fn, KzgCellVerifier* v, KzgKey* kk) {
   Ctx& c = *kk->c;

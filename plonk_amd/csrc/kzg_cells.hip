@@ -24,8 +24,7 @@
 #include "plonk_internal.hpp"
 #include "api_guard.hpp"
 #include "kzg_core.hpp"
-#include "kzg_domain.hpp"
-#include "kzg_evals.hpp"
+#include "kzg_handle.hpp"
 #include "kzg_cells.hpp"
 #include "devmem.cuh"
 
@@ -172,8 +171,6 @@ int kzc_reduce(Ctx* c, void* ws, uint64_t stride, uint32_t log_r, uint64_t slice
 }
 
 // ---- the state a handle holds for these calls ------------------------------------------------------------------------------
-namespace {
-
 struct KzcBufs {
   enum { WS, F, G, EVALS, CELLS, TMP, OUT48, DESC, META, NBUF };   // grow-only
 };
@@ -189,15 +186,14 @@ struct KzgCells : KzcBufs, DevBufs<KzcBufs::NBUF> {
   }
 };
 
-KzgCells* kzc_state(void** slot) {
-  if (!*slot) *slot = new KzgCells();
-  return (KzgCells*)*slot;
-}
+void kzc_release(KzgCells* cells) { delete cells; }
 
-int table_ready(const KzdView& v, KzgCells* e, uint32_t log_cell, uint32_t* built) {
+namespace {
+
+int table_ready(const KzgDomain* d, KzgCells* e, uint32_t log_cell, uint32_t* built) {
   if (e->table[log_cell]) return PLONK_OK;
-  const uint64_t bytes = (2ull << v.log_n) * KZD_SLOT_BYTES;
-  const uint32_t log_size = v.log_n - log_cell + 1;
+  const uint64_t bytes = (2ull << d->log_n) * KZD_SLOT_BYTES;
+  const uint32_t log_size = d->log_n - log_cell + 1;
   if (log_size <= KZC_NTT_MAX_LOG && !e->ntt_tw[log_cell]) {   // the powers the scalar transform reads: at most 32 KiB
     std::vector<Fr> pw(1ull << (log_size - 1));
     const Fr w = fr_domain_root(log_size);
@@ -206,18 +202,18 @@ int table_ready(const KzdView& v, KzgCells* e, uint32_t log_cell, uint32_t* buil
       y = x;
       x = x * w;
     }
-    Fr* d = nullptr;
-    HIP_TRY(hipMalloc((void**)&d, sizeof(Fr) * pw.size()));
-    if (hipMemcpy(d, pw.data(), sizeof(Fr) * pw.size(), hipMemcpyHostToDevice) != hipSuccess) {
-      (void)hipFree(d);
+    Fr* tw_dev = nullptr;
+    HIP_TRY(hipMalloc((void**)&tw_dev, sizeof(Fr) * pw.size()));
+    if (hipMemcpy(tw_dev, pw.data(), sizeof(Fr) * pw.size(), hipMemcpyHostToDevice) != hipSuccess) {
+      (void)hipFree(tw_dev);
       return PLONK_ERR_HIP;
     }
-    e->ntt_tw[log_cell] = d;
+    e->ntt_tw[log_cell] = tw_dev;
   }
   G1RSlot* t = nullptr;
   HIP_TRY(hipMalloc((void**)&t, bytes));
-  int rc = kzc_table_build(v.c, v.log_n, log_cell, v.tw, v.log_n + 1, t);
-  if (hipStreamSynchronize(v.c->stream) != hipSuccess && rc == PLONK_OK) rc = PLONK_ERR_HIP;
+  int rc = kzc_table_build(d->c, d->log_n, log_cell, d->tw, d->log_n + 1, t);
+  if (hipStreamSynchronize(d->c->stream) != hipSuccess && rc == PLONK_OK) rc = PLONK_ERR_HIP;
   if (rc != PLONK_OK) {
     (void)hipFree(t);
     return rc;
@@ -228,12 +224,12 @@ int table_ready(const KzdView& v, KzgCells* e, uint32_t log_cell, uint32_t* buil
   return PLONK_OK;
 }
 
-int cells_body(const KzdView& v, KzgCells* e, uint32_t log_cell, const void* const* polys, const uint64_t* trimmed, uint64_t count,
+int cells_body(const KzgDomain* d, KzgCells* e, uint32_t log_cell, const void* const* polys, const uint64_t* trimmed, uint64_t count,
                void* cells, void* proofs48, void* commitments48) {
-  Ctx& c = *v.c;
-  const uint32_t L = v.log_n, log_r = L - log_cell;
+  Ctx& c = *d->c;
+  const uint32_t L = d->log_n, log_r = L - log_cell;
   const uint64_t n = 1ull << L, l = 1ull << log_cell, r = 1ull << log_r, size = 2 * r;
-  const KzcPlan plan = kzc_plan(L, log_cell, count, v.ws_cap, e->forced_slices);
+  const KzcPlan plan = kzc_plan(L, log_cell, count, d->ws_cap, e->forced_slices);
   const uint64_t chunk = plan.chunk_polys, stride = plan.slices * size;
   plonk_kzg_cells_info info = {};
   info.log_n = L;
@@ -242,7 +238,7 @@ int cells_body(const KzdView& v, KzgCells* e, uint32_t log_cell, const void* con
   info.slices = plan.slices;
   info.chunk_polys = chunk;
   info.workspace_bytes = plan.ws_bytes;
-  PTRY(table_ready(v, e, log_cell, &info.built_table));
+  PTRY(table_ready(d, e, log_cell, &info.built_table));
   PTRY(e->need(KzgCells::WS, plan.ws_bytes));
   PTRY(e->need(KzgCells::F, sizeof(Fr) * n * chunk));
   PTRY(e->need(KzgCells::G, sizeof(Fr) * 2 * n * chunk));
@@ -262,11 +258,7 @@ int cells_body(const KzdView& v, KzgCells* e, uint32_t log_cell, const void* con
   std::vector<uint8_t> comm;
   for (uint64_t first = 0; first < count; first += chunk) {
     const uint32_t cnt = (uint32_t)(count - first < chunk ? count - first : chunk);
-    // the chunk's coefficients, zero-padded to n each
-    HIP_TRY(hipMemsetAsync(f, 0, sizeof(Fr) * n * cnt, c.stream));
-    for (uint32_t b = 0; b < cnt; ++b)
-      if (trimmed[first + b])
-        HIP_TRY(hipMemcpyAsync(f + (uint64_t)b * n, polys[first + b], sizeof(Fr) * trimmed[first + b], hipMemcpyDefault, c.stream));
+    PTRY(kzd_stage(&c, f, n, polys + first, trimmed + first, cnt));
     // cell values: the ordinary forward transform in cell-major order; G^(u) = NTT_2r of the gathered coefficients
     PTRY(kzc_gather(&c, f, L, log_cell, cnt, g));
     for (uint32_t b = 0; b < cnt; ++b) {
@@ -281,17 +273,10 @@ int cells_body(const KzdView& v, KzgCells* e, uint32_t log_cell, const void* con
     PTRY(kzc_mulacc(&c, e->table[log_cell], g, 2 * n, ws, stride, L, log_cell, plan.slices, cnt, size_inv));
     info.scalar_muls += 2 * n * cnt;
     PTRY(kzc_reduce(&c, ws, stride, log_r, plan.slices, cnt));
-    PTRY(kzd_transform(&c, ws, stride, log_r + 1, cnt, true, v.tw, L + 1, &info.stage_launches, &info.scalar_muls));
-    PTRY(kzd_extract(&c, ws, stride, log_r, cnt));
-    PTRY(kzd_transform(&c, ws + r, stride, log_r, cnt, false, v.tw, L + 1, &info.stage_launches, &info.scalar_muls));
-    PTRY(kzd_finish(&c, ws, stride, r, log_r, cnt, true, out48));
+    PTRY(kzd_witnesses(&c, ws, stride, log_r, cnt, d->tw, L + 1, &info.stage_launches, &info.scalar_muls, out48));
     if (cells) HIP_TRY(hipMemcpyAsync((uint8_t*)cells + sizeof(Fr) * n * first, cl, sizeof(Fr) * n * cnt, hipMemcpyDefault, c.stream));
     HIP_TRY(hipMemcpyAsync((uint8_t*)proofs48 + 48 * r * first, out48, 48 * r * cnt, hipMemcpyDefault, c.stream));
-    if (commitments48) {
-      comm.resize(48ull * cnt);
-      PTRY(kzd_commit(&c, f, n, trimmed + first, cnt, comm.data()));
-      HIP_TRY(hipMemcpyAsync((uint8_t*)commitments48 + 48 * first, comm.data(), 48ull * cnt, hipMemcpyDefault, c.stream));
-    }
+    if (commitments48) PTRY(kzd_commit(&c, f, n, trimmed + first, cnt, comm, (uint8_t*)commitments48 + 48 * first));
     HIP_TRY(hipStreamSynchronize(c.stream));   // the chunk's buffers are reused by the next one
     ++info.chunks;
   }
@@ -303,43 +288,34 @@ int cells_body(const KzdView& v, KzgCells* e, uint32_t log_cell, const void* con
 int cells_impl(const char* api_fn, plonk_kzg_domain* dom, uint32_t log_cell, const void* const* polys, const uint64_t* lens, uint64_t count,
                void* cells, void* proofs48, void* commitments48, bool resident) {
   if (!dom) API_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
-  const KzdView v = kzd_view(dom);
-  if (kzc_check_cell(v.log_n, log_cell)) API_FAIL(PLONK_ERR_ARG, "invalid argument: log_cell must be in [1, log_n - 1]");
+  KzgDomain* d = dom->d;
+  if (kzc_check_cell(d->log_n, log_cell)) API_FAIL(PLONK_ERR_ARG, "invalid argument: log_cell must be in [1, log_n - 1]");
   if (count > KZD_MAX_COUNT) API_FAIL(PLONK_ERR_ARG, "invalid argument: at most 65536 polynomials per call");
   if (count && (!polys || !lens || !cells || !proofs48)) API_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
   for (uint64_t i = 0; i < count; ++i)
     if (lens[i] && !polys[i]) API_FAIL(PLONK_ERR_ARG, "invalid argument: polys[i] is NULL with lens[i] > 0");
-  Ctx& c = *v.c;
-  CTX_ENTER(c, api_fn);
-  HIP_TRY(hipSetDevice(c.device));
-  if (!kzd_view(dom).key_current) API_FAIL(PLONK_ERR_STATE, "the domain is bound to a commit key that was replaced on its context");
-  if (c.nccl_comm) API_FAIL(PLONK_ERR_STATE, "a context with a communicator holds only a range of the commit key");
+  KZD_ENTER(d, api_fn, KZD_WORK);
   if (!count) return PLONK_OK;
-  KzgCells* e = kzc_state(v.cells);
+  KzgCells* e = kzd_state(d->cells);
   std::vector<uint64_t> trimmed(count);
-  if (resident) {
-    PTRY(e->need(KzgCells::DESC, sizeof(KzdDesc) * count));
-    PTRY(e->need(KzgCells::META, 16 * count));
-  }
-  PTRY(kzd_lengths(api_fn, &c, v.log_n, polys, lens, count, resident, e->at<KzdDesc>(KzgCells::DESC),
-                     e->at<unsigned long long>(KzgCells::META), trimmed.data()));
-  const int rc = cells_body(kzd_view(dom), e, log_cell, polys, trimmed.data(), count, cells, proofs48, commitments48);
-  if (rc != PLONK_OK) (void)hipStreamSynchronize(c.stream);   // an error leaves nothing of the call queued
-  return rc;
+  PTRY(kzd_lengths_on(api_fn, d->c, e, d->log_n, polys, lens, count, resident, trimmed.data()));
+  return kzd_drained(d->c, cells_body(d, e, log_cell, polys, trimmed.data(), count, cells, proofs48, commitments48));
 }
 
 }  // namespace
 
-int kzc_open_resident(const KzdView& v, uint32_t log_cell, const void* const* polys_dev, const uint64_t* trimmed, uint64_t count, void* cells,
+int kzc_open_resident(KzgDomain* d, uint32_t log_cell, const void* const* polys_dev, const uint64_t* trimmed, uint64_t count, void* cells,
                       void* proofs48, void* commitments48, uint32_t* built_table) {
-  KzgCells* e = kzc_state(v.cells);
-  PTRY(cells_body(v, e, log_cell, polys_dev, trimmed, count, cells, proofs48, commitments48));
+  KzgCells* e = kzd_state(d->cells);
+  PTRY(cells_body(d, e, log_cell, polys_dev, trimmed, count, cells, proofs48, commitments48));
   if (e->last.built_table) *built_table = 1;
   return PLONK_OK;
 }
 
-void kzc_release(void* cells) { delete (KzgCells*)cells; }
-void kzc_set_slices(void** cells, uint64_t slices) { kzc_state(cells)->forced_slices = slices; }
+void kzc_set_slices(plonk_kzg_domain* dom, uint64_t slices) {
+  std::lock_guard<std::mutex> lk(dom->d->c->mu);
+  kzd_state(dom->d->cells)->forced_slices = slices;
+}
 
 }  // namespace plonk
 
@@ -367,14 +343,12 @@ int plonk_kzg_cell_points(plonk_kzg_domain* dom, uint32_t log_cell, uint64_t* x,
   const char* const api_fn = __func__;
   return plonk::api_guard(api_fn, [&]() -> int {
   if (!dom || !x) API_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
-  const KzdView v = kzd_view(dom);
-  if (kzc_check_cell(v.log_n, log_cell)) API_FAIL(PLONK_ERR_ARG, "invalid argument: log_cell must be in [1, log_n - 1]");
-  Ctx& c = *v.c;
-  CTX_ENTER(c, api_fn);
-  if (!kzd_view(dom).key_current) API_FAIL(PLONK_ERR_STATE, "the domain is bound to a commit key that was replaced on its context");
-  const Fr w = fr_domain_root(v.log_n), phi = fr_domain_root(v.log_n - log_cell);
+  const KzgDomain* d = dom->d;
+  if (kzc_check_cell(d->log_n, log_cell)) API_FAIL(PLONK_ERR_ARG, "invalid argument: log_cell must be in [1, log_n - 1]");
+  KZD_ENTER(d, api_fn, KZD_KEY);
+  const Fr w = fr_domain_root(d->log_n), phi = fr_domain_root(d->log_n - log_cell);
   Fr a = Fr::one(), b = Fr::one();
-  for (uint64_t k = 0; k < (1ull << (v.log_n - log_cell)); ++k) {
+  for (uint64_t k = 0; k < (1ull << (d->log_n - log_cell)); ++k) {
     memcpy(x + 4 * k, a.l, 32);
     if (shift) memcpy(shift + 4 * k, b.l, 32);
     a = a * phi;
@@ -388,17 +362,15 @@ int plonk_kzg_cells_last(plonk_kzg_domain* dom, plonk_kzg_cells_info* out) {
   const char* const api_fn = __func__;
   return plonk::api_guard(api_fn, [&]() -> int {
   if (!dom || !out) API_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
-  const KzdView v = kzd_view(dom);
-  Ctx& c = *v.c;
-  CTX_ENTER(c, api_fn);
-  if (!kzd_view(dom).key_current) API_FAIL(PLONK_ERR_STATE, "the domain is bound to a commit key that was replaced on its context");
-  const KzgCells* e = (const KzgCells*)*v.cells;
+  const KzgDomain* d = dom->d;
+  KZD_ENTER(d, api_fn, KZD_KEY);
+  const KzgCells* e = d->cells;
   plonk_kzg_cells_info info = {};
   if (e) {
     info = e->last;
     info.table_bytes = e->table_bytes;
   }
-  info.log_n = v.log_n;
+  info.log_n = d->log_n;
   *out = info;
   return PLONK_OK;
   });

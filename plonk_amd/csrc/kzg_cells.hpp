@@ -29,13 +29,12 @@ int kzc_reduce(Ctx* c, void* ws, uint64_t stride, uint32_t log_r, uint64_t slice
 // trimmed lengths the caller knows (at most n, canonical coefficients).  cells may be NULL (the values are not copied out);
 // the outputs go through hipMemcpyDefault, so either side of the call may own them.  *built_table is set to 1 when the call
 // built the A^(u) of its cell size; plonk_kzg_cells_last reports the call.  Synchronises the stream per chunk.
-struct KzdView;
-int kzc_open_resident(const KzdView& v, uint32_t log_cell, const void* const* polys_dev, const uint64_t* trimmed, uint64_t count, void* cells,
+struct KzgDomain;   // kzg_handle.hpp
+int kzc_open_resident(KzgDomain* d, uint32_t log_cell, const void* const* polys_dev, const uint64_t* trimmed, uint64_t count, void* cells,
                       void* proofs48, void* commitments48, uint32_t* built_table);
 
-// kzg_domain.hip: the handle's slot for the state of these calls
-void kzc_release(void* cells);
-// test hook (tests/csrc/dev_kzg_cells.hip): the slice count of the handle's next calls, 0 restores the plan's own
-void kzc_set_slices(void** cells, uint64_t slices);
+// test hook (tests/csrc/dev_kzg_cells.hip): the slice count of the handle's next calls, 0 restores the plan's own; takes the
+// context's mutex
+void kzc_set_slices(plonk_kzg_domain* dom, uint64_t slices);
 
 }  // namespace plonk

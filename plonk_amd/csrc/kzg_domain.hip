@@ -30,16 +30,8 @@
 #include "hostg1.hpp"
 #include "g1codec.cuh"
 #include "kzg_core.hpp"
-#include "kzg_domain.hpp"
-#include "kzg_evals.hpp"
-#include "kzg_cells.hpp"
+#include "kzg_handle.hpp"
 #include "devmem.cuh"
-
-namespace plonk { struct KzgDomain; }
-struct plonk_kzg_domain {
-  plonk::KzgDomain* d;
-  plonk_ctx* ctx;
-};
 
 namespace plonk {
 
@@ -226,36 +218,14 @@ int kzd_load_raw(Ctx* c, const G1Affine* xy96, uint64_t count, void* slots) {
 }
 
 // ---- the handle ------------------------------------------------------------------------------------------------------------
-struct KzdBufs {
-  enum { WS, F, G, EVALS, TMP, OUT48, DESC, META, NBUF };   // grow-only buffers of the open calls
-};
-struct KzgDomain : KzdBufs, DevBufs<KzdBufs::NBUF> {
-  Ctx* c = nullptr;
-  uint32_t log_n = 0;
-  uint64_t srs_gen = 0;
-  G1RSlot* A = nullptr;          // DFT_N(a), bit-reversed: N slots
-  GlvScalar* tw = nullptr;       // w_N^e, e < n
-  uint64_t fixed_bytes = 0;      // A + tw
-  uint64_t ws_cap = KZD_WS_CAP_DEFAULT;
-  plonk_kzg_domain_info last = {};
-  void* evals = nullptr;         // the Lagrange points and workspace of the evaluation-form calls (kzg_evals.hip); not in device_bytes()
-  void* cells = nullptr;         // the A^(u) tables and workspace of the cell proofs (kzg_cells.hip); not in device_bytes()
-  void* recover = nullptr;       // the workspace of the cell recovery (kzg_recover.hip); not in device_bytes()
-  void* multi = nullptr;         // the invd table and workspace of the multiproofs (kzg_multiproof.hip); not in device_bytes()
-  ~KzgDomain() {   // in this order: the multiproof state, the recovery state, the cell state, the evaluation-form state, the fixed buffers; the base frees the grow-only ones last
-    kmp_release(multi);
-    kzr_release(recover);
-    kzc_release(cells);
-    kze_release(evals);
-    (void)hipFree(A);
-    (void)hipFree(tw);
-  }
-  uint64_t device_bytes() const { return fixed_bytes + bytes(); }
-};
+static const char KZD_NEEDS_WHOLE_KEY[] = "a context with a communicator holds only a range of the commit key";
 
-KzdView kzd_view(plonk_kzg_domain* dom) {
-  KzgDomain* d = dom->d;
-  return KzdView{d->c, d->log_n, d->srs_gen == d->c->srs_gen, d->tw, &d->evals, &d->cells, d->ws_cap, &d->recover, &d->multi};
+int kzd_enter_checks(const char* api_fn, const KzgDomain* d, uint32_t checks) {
+  const Ctx& c = *d->c;
+  if (checks & KZD_SET_DEVICE) HIP_TRY(hipSetDevice(c.device));
+  if ((checks & KZD_KEY) && d->srs_gen != c.srs_gen) API_FAIL(PLONK_ERR_STATE, "the domain is bound to a commit key that was replaced on its context");
+  if ((checks & KZD_WHOLE_KEY) && c.nccl_comm) API_FAIL(PLONK_ERR_STATE, KZD_NEEDS_WHOLE_KEY);
+  return PLONK_OK;
 }
 
 static int domain_create_body(Ctx& c, uint32_t log_n, KzgDomain* d) {
@@ -276,8 +246,34 @@ static int domain_create_body(Ctx& c, uint32_t log_n, KzgDomain* d) {
   return PLONK_OK;
 }
 
-// commitments of the chunk's polynomials (zero-padded rows of f, trimmed lengths m) through the ordinary commitment path
-int kzd_commit(Ctx* c, const Fr* f, uint64_t n, const uint64_t* m, uint32_t cnt, uint8_t* out48) {
+// ---- the chunk steps (kzg_domain.hpp) ----------------------------------------------------------------------------------------
+int kzd_stage(Ctx* c, Fr* f, uint64_t n, const void* const* polys, const uint64_t* trimmed, uint32_t cnt) {
+  HIP_TRY(hipMemsetAsync(f, 0, sizeof(Fr) * n * cnt, c->stream));
+  for (uint32_t b = 0; b < cnt; ++b)
+    if (trimmed[b]) HIP_TRY(hipMemcpyAsync(f + (uint64_t)b * n, polys[b], sizeof(Fr) * trimmed[b], hipMemcpyDefault, c->stream));
+  return PLONK_OK;
+}
+
+int kzd_witnesses(Ctx* c, void* slots, uint64_t stride, uint32_t log_w, uint32_t cnt, const GlvScalar* tw, uint32_t tw_log,
+                  uint64_t* stage_launches, uint64_t* scalar_muls, uint8_t* out48) {
+  const uint64_t w = 1ull << log_w;
+  PTRY(kzd_transform(c, slots, stride, log_w + 1, cnt, true, tw, tw_log, stage_launches, scalar_muls));
+  PTRY(kzd_extract(c, slots, stride, log_w, cnt));
+  PTRY(kzd_transform(c, (G1RSlot*)slots + w, stride, log_w, cnt, false, tw, tw_log, stage_launches, scalar_muls));
+  return kzd_finish(c, slots, stride, w, log_w, cnt, true, out48);
+}
+
+int kzd_drained(Ctx* c, int rc) {
+  if (rc != PLONK_OK) {
+    if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
+    (void)hipStreamSynchronize(c->stream);
+  }
+  return rc;
+}
+
+int kzd_commit(Ctx* c, const Fr* f, uint64_t n, const uint64_t* m, uint32_t cnt, std::vector<uint8_t>& comm, void* dst48) {
+  comm.resize(48ull * cnt);
+  uint8_t* out48 = comm.data();
   const Fr* sc[MSM_MAX_BATCH];
   uint64_t mm[MSM_MAX_BATCH];
   uint32_t which[MSM_MAX_BATCH];
@@ -296,6 +292,7 @@ int kzd_commit(Ctx* c, const Fr* f, uint64_t n, const uint64_t* m, uint32_t cnt,
       g = 0;
     }
   }
+  HIP_TRY(hipMemcpyAsync(dst48, out48, 48ull * cnt, hipMemcpyDefault, c->stream));
   return PLONK_OK;
 }
 
@@ -328,11 +325,7 @@ static int domain_open_body(KzgDomain* d, const void* const* polys, const uint64
   std::vector<uint8_t> comm;
   for (uint64_t first = 0; first < count; first += chunk) {
     const uint32_t cnt = (uint32_t)(count - first < chunk ? count - first : chunk);
-    // the chunk's coefficients, zero-padded to n each
-    HIP_TRY(hipMemsetAsync(f, 0, sizeof(Fr) * n * cnt, c.stream));
-    for (uint32_t b = 0; b < cnt; ++b)
-      if (trimmed[first + b])
-        HIP_TRY(hipMemcpyAsync(f + (uint64_t)b * n, polys[first + b], sizeof(Fr) * trimmed[first + b], hipMemcpyDefault, c.stream));
+    PTRY(kzd_stage(&c, f, n, polys + first, trimmed + first, cnt));
     // evaluations: the ordinary forward transform; G = NTT_N of the reversed coefficients
     hipLaunchKernelGGL(kzd_reverse_kernel, dim3((uint32_t)((N + 255) / 256), cnt), dim3(256), 0, c.stream, (const Fr*)f, n, g);
     HIP_TRY(hipGetLastError());
@@ -342,17 +335,10 @@ static int domain_open_body(KzgDomain* d, const void* const* polys, const uint64
     }
     PTRY(kzd_pointwise(&c, d->A, g, N, ws, N, L + 1, cnt, n_inv));
     info.scalar_muls += N * cnt;
-    PTRY(kzd_transform(&c, ws, N, L + 1, cnt, true, d->tw, L + 1, &info.stage_launches, &info.scalar_muls));
-    PTRY(kzd_extract(&c, ws, N, L, cnt));
-    PTRY(kzd_transform(&c, ws + n, N, L, cnt, false, d->tw, L + 1, &info.stage_launches, &info.scalar_muls));
-    PTRY(kzd_finish(&c, ws, N, n, L, cnt, true, out48));
+    PTRY(kzd_witnesses(&c, ws, N, L, cnt, d->tw, L + 1, &info.stage_launches, &info.scalar_muls, out48));
     HIP_TRY(hipMemcpyAsync((uint8_t*)evaluations + sizeof(Fr) * n * first, ev, sizeof(Fr) * n * cnt, hipMemcpyDefault, c.stream));
     HIP_TRY(hipMemcpyAsync((uint8_t*)witnesses48 + 48 * n * first, out48, 48 * n * cnt, hipMemcpyDefault, c.stream));
-    if (commitments48) {
-      comm.resize(48ull * cnt);
-      PTRY(kzd_commit(&c, f, n, trimmed + first, cnt, comm.data()));
-      HIP_TRY(hipMemcpyAsync((uint8_t*)commitments48 + 48 * first, comm.data(), 48ull * cnt, hipMemcpyDefault, c.stream));
-    }
+    if (commitments48) PTRY(kzd_commit(&c, f, n, trimmed + first, cnt, comm, (uint8_t*)commitments48 + 48 * first));
     HIP_TRY(hipStreamSynchronize(c.stream));   // the chunk's buffers are reused by the next one
     ++info.chunks;
   }
@@ -413,23 +399,12 @@ static int domain_open_impl(const char* api_fn, plonk_kzg_domain* dom, const voi
   for (uint64_t i = 0; i < count; ++i)
     if (lens[i] && !polys[i]) API_FAIL(PLONK_ERR_ARG, "invalid argument: polys[i] is NULL with lens[i] > 0");
   KzgDomain* d = dom->d;
-  Ctx& c = *d->c;
-  CTX_ENTER(c, api_fn);
-  HIP_TRY(hipSetDevice(c.device));
-  if (d->srs_gen != c.srs_gen) API_FAIL(PLONK_ERR_STATE, "the domain is bound to a commit key that was replaced on its context");
-  if (c.nccl_comm) API_FAIL(PLONK_ERR_STATE, "a context with a communicator holds only a range of the commit key");
+  KZD_ENTER(d, api_fn, KZD_WORK);
   if (!count) return PLONK_OK;
   // lengths without trailing zeros and the canonical-form check, before anything is queued or written
   std::vector<uint64_t> trimmed(count);
-  if (resident) {
-    PTRY(d->need(KzgDomain::DESC, sizeof(KzdDesc) * count));
-    PTRY(d->need(KzgDomain::META, 16 * count));
-  }
-  PTRY(kzd_lengths(api_fn, &c, d->log_n, polys, lens, count, resident, d->at<KzdDesc>(KzgDomain::DESC),
-                     d->at<unsigned long long>(KzgDomain::META), trimmed.data()));
-  const int rc = domain_open_body(d, polys, trimmed.data(), count, evaluations, witnesses48, commitments48);
-  if (rc != PLONK_OK) (void)hipStreamSynchronize(c.stream);   // an error leaves nothing of the call queued
-  return rc;
+  PTRY(kzd_lengths_on(api_fn, d->c, d, d->log_n, polys, lens, count, resident, trimmed.data()));
+  return kzd_drained(d->c, domain_open_body(d, polys, trimmed.data(), count, evaluations, witnesses48, commitments48));
 }
 
 }  // namespace plonk
@@ -448,7 +423,7 @@ int plonk_kzg_domain_create(plonk_ctx* ctx, uint32_t log_n, plonk_kzg_domain** o
   HIP_TRY(hipSetDevice(c.device));
   switch (kzd_check_create(log_n, c.nccl_comm != nullptr, c.srs_table != nullptr && c.srs_n != 0, c.srs_n)) {
     case PLONK_ERR_ARG: API_FAIL(PLONK_ERR_ARG, "invalid argument: log_n must be in [1, 20]");
-    case PLONK_ERR_STATE: API_FAIL(PLONK_ERR_STATE, "a context with a communicator holds only a range of the commit key");
+    case PLONK_ERR_STATE: API_FAIL(PLONK_ERR_STATE, KZD_NEEDS_WHOLE_KEY);
     case PLONK_ERR_NO_SRS: return PLONK_ERR_NO_SRS;
     case PLONK_ERR_DEGREE: return PLONK_ERR_DEGREE;
     default: break;
@@ -479,9 +454,7 @@ int plonk_kzg_domain_points(plonk_kzg_domain* dom, uint64_t* out) {
   return plonk::api_guard(api_fn, [&]() -> int {
   if (!dom || !out) API_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
   KzgDomain* d = dom->d;
-  Ctx& c = *d->c;
-  CTX_ENTER(c, api_fn);
-  if (d->srs_gen != c.srs_gen) API_FAIL(PLONK_ERR_STATE, "the domain is bound to a commit key that was replaced on its context");
+  KZD_ENTER(d, api_fn, KZD_KEY);
   const Fr w = fr_domain_root(d->log_n);
   Fr x = Fr::one();
   for (uint64_t i = 0; i < (1ull << d->log_n); ++i) {
@@ -513,9 +486,7 @@ int plonk_kzg_domain_last(plonk_kzg_domain* dom, plonk_kzg_domain_info* out) {
   return plonk::api_guard(api_fn, [&]() -> int {
   if (!dom || !out) API_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
   KzgDomain* d = dom->d;
-  Ctx& c = *d->c;
-  CTX_ENTER(c, api_fn);
-  if (d->srs_gen != c.srs_gen) API_FAIL(PLONK_ERR_STATE, "the domain is bound to a commit key that was replaced on its context");
+  KZD_ENTER(d, api_fn, KZD_KEY);
   *out = d->last;
   out->device_bytes = d->device_bytes();
   out->workspace_cap_bytes = d->ws_cap;

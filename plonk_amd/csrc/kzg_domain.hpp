@@ -27,7 +27,18 @@ int kzd_finish(Ctx* c, const void* slots, uint64_t stride, uint64_t offset, uint
 // slots[i] = the affine point xy96[i] (Montgomery x || y, 96 zero bytes = the identity), i < count
 int kzd_load_raw(Ctx* c, const G1Affine* xy96, uint64_t count, void* slots);
 
-// What the other openings on a handle (kzg_cells.hip) share with plonk_kzg_open_domain.
+// ---- the chunk steps the openings on a handle (kzg_domain.hip, kzg_cells.hip, kzg_recover.hip) share ----
+// f[b] = the trimmed[b] coefficients of polys[b] (either side's memory), zero-padded to n, b < cnt
+int kzd_stage(Ctx* c, Fr* f, uint64_t n, const void* const* polys, const uint64_t* trimmed, uint32_t cnt);
+// from the transformed products of a chunk (2^(log_w + 1) slots per polynomial at slots + b * stride) to its 2^log_w witnesses
+// per polynomial as 48 bytes each: inverse transform, kzd_extract, forward transform of the upper half, kzd_finish in
+// bit-reversed order.  The two counters are added to.
+int kzd_witnesses(Ctx* c, void* slots, uint64_t stride, uint32_t log_w, uint32_t cnt, const GlvScalar* tw, uint32_t tw_log,
+                  uint64_t* stage_launches, uint64_t* scalar_muls, uint8_t* out48);
+// an error of a call's body leaves nothing of the call queued: the copy stream, if the context has one, and the main stream
+// are drained; passes rc on
+int kzd_drained(Ctx* c, int rc);
+
 struct KzdDesc {   // a resident polynomial as the scan kernel takes it
   const Fr* p;
   uint64_t len;
@@ -38,8 +49,9 @@ struct KzdDesc {   // a resident polynomial as the scan kernel takes it
 // with the stream drained.
 int kzd_lengths(const char* api_fn, Ctx* c, uint32_t log_n, const void* const* polys, const uint64_t* lens, uint64_t count, bool resident,
                 KzdDesc* desc_dev, unsigned long long* meta_dev, uint64_t* trimmed);
-// out48[i] (HOST memory) = the commitment of row i of f (n coefficients per row, trimmed length m[i]) through the ordinary
-// commitment path; the caller has reserved the MSM scratch (msm_reserve); returns with the stream synchronised
-int kzd_commit(Ctx* c, const Fr* f, uint64_t n, const uint64_t* m, uint32_t cnt, uint8_t* out48);
+// dst48[i] (either side's memory) = the commitment of row i of f (n coefficients per row, trimmed length m[i]) through the
+// ordinary commitment path; the caller has reserved the MSM scratch (msm_reserve).  The copy to dst48 is queued from `comm`,
+// which the caller keeps alive until it has synchronised the stream.
+int kzd_commit(Ctx* c, const Fr* f, uint64_t n, const uint64_t* m, uint32_t cnt, std::vector<uint8_t>& comm, void* dst48);
 
 }  // namespace plonk

@@ -32,7 +32,7 @@
 #include "hostg1.hpp"
 #include "g1codec.cuh"
 #include "kzg_core.hpp"
-#include "kzg_domain.hpp"
+#include "kzg_handle.hpp"
 #include "kzg_evals.hpp"
 #include "kzg_evals_finish.cuh"
 
@@ -249,11 +249,20 @@ int kze_lagrange_points(Ctx* c, uint32_t log_n, const GlvScalar* tw, uint32_t tw
 }
 
 int kze_scan(Ctx* c, const Fr* const* vecs, uint32_t first, uint32_t cnt, uint64_t n, KzeMeta* meta) {
-  if (!cnt) return PLONK_OK;
   const uint32_t blocks = (uint32_t)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024);
-  hipLaunchKernelGGL(kze_scan_kernel, dim3(blocks, cnt), dim3(256), 0, c->stream, vecs + first, n, meta);
-  HIP_TRY(hipGetLastError());
+  for (uint32_t done = 0; done < cnt; done += 32768) {   // grid.y
+    hipLaunchKernelGGL(kze_scan_kernel, dim3(blocks, cnt - done < 32768 ? cnt - done : 32768), dim3(256), 0, c->stream, vecs + first + done, n, meta);
+    HIP_TRY(hipGetLastError());
+  }
   return PLONK_OK;
+}
+
+bool kze_host_canonical(const void* const* vecs, uint64_t count, uint64_t n) {
+  Fr t;
+  for (uint64_t i = 0; i < count; ++i)
+    for (uint64_t k = 0; k < n; ++k)
+      if (!kzg_fr_load((const uint64_t*)vecs[i] + 4 * k, &t)) return false;
+  return true;
 }
 
 int kze_denominators(Ctx* c, uint32_t log_n, const Fr& z, Fr* den, KzeMeta* meta) {
@@ -296,8 +305,6 @@ int kze_finish(Ctx* c, const G1* bits, uint32_t count, int rb, bool bitpos, uint
 }
 
 // ---- the state a handle holds for these calls ------------------------------------------------------------------------------
-namespace {
-
 struct KzeBufs {
   enum { DEN, FOLD, Q, PARTIAL, EVALS, VPOW, VECS, META, QPART, BITS, FIN48, NBUF };   // grow-only
 };
@@ -326,18 +333,17 @@ struct KzgEvals : KzeBufs, DevBufs<KzeBufs::NBUF> {
   }
 };
 
-KzgEvals* kze_state(const KzdView& v) {
-  if (!*v.evals) *v.evals = new KzgEvals();
-  return (KzgEvals*)*v.evals;
-}
+void kze_release(KzgEvals* evals) { delete evals; }
+
+namespace {
 
 // the points, built by the first call that commits
-int lagrange_ready(const KzdView& v, KzgEvals* e, uint32_t* built) {
+int lagrange_ready(KzgDomain* d, KzgEvals* e, uint32_t* built) {
   if (e->lag) return PLONK_OK;
-  const uint64_t bytes = KZE_POINT_BYTES << v.log_n;
+  const uint64_t bytes = KZE_POINT_BYTES << d->log_n;
   G1Affine* pts = nullptr;
   HIP_TRY(hipMalloc((void**)&pts, bytes));
-  const int rc = kze_lagrange_points(v.c, v.log_n, v.tw, v.log_n + 1, pts);
+  const int rc = kze_lagrange_points(d->c, d->log_n, d->tw, d->log_n + 1, pts);
   if (rc != PLONK_OK) {
     (void)hipFree(pts);
     return rc;
@@ -530,9 +536,9 @@ struct EvalsCall {
   uint8_t* witness48;
 };
 
-int evals_body(const char* api_fn, const KzdView& dv, KzgEvals* e, const EvalsCall& a) {
-  Ctx& c = *dv.c;
-  const uint32_t L = dv.log_n;
+int evals_body(const char* api_fn, KzgDomain* d, KzgEvals* e, const EvalsCall& a) {
+  Ctx& c = *d->c;
+  const uint32_t L = d->log_n;
   const uint64_t n = 1ull << L, count = a.count;
   const bool in_domain = a.open && kze_in_domain(a.z, L);
   const KzePlan plan = kze_plan(L, count, a.commitments48 != nullptr, a.witness48 != nullptr, !a.resident);
@@ -551,9 +557,7 @@ int evals_body(const char* api_fn, const KzdView& dv, KzgEvals* e, const EvalsCa
     HIP_TRY(hipMemcpyAsync(e->p[KzgEvals::META], &mh, sizeof mh, hipMemcpyHostToDevice, c.stream));
     if (a.resident) {
       HIP_TRY(hipMemcpyAsync(e->p[KzgEvals::VECS], a.vecs, sizeof(Fr*) * count, hipMemcpyHostToDevice, c.stream));
-      for (uint64_t first = 0; first < count; first += 32768)   // grid.y
-        PTRY(kze_scan(&c, e->at<const Fr*>(KzgEvals::VECS), (uint32_t)first, (uint32_t)(count - first < 32768 ? count - first : 32768), n,
-                        e->at<KzeMeta>(KzgEvals::META)));
+      PTRY(kze_scan(&c, e->at<const Fr*>(KzgEvals::VECS), 0, (uint32_t)count, n, e->at<KzeMeta>(KzgEvals::META)));
     }
     if (a.open) PTRY(kze_denominators(&c, L, a.z, e->at<Fr>(KzgEvals::DEN), e->at<KzeMeta>(KzgEvals::META)));
     HIP_TRY(hipMemcpyAsync(&mh, e->p[KzgEvals::META], sizeof mh, hipMemcpyDeviceToHost, c.stream));
@@ -565,7 +569,7 @@ int evals_body(const char* api_fn, const KzdView& dv, KzgEvals* e, const EvalsCa
   }
   info.in_domain_index = mh.m;
   // ---- from here on the call writes ----
-  if (plan.msm_launches) PTRY(lagrange_ready(dv, e, &info.built_points));
+  if (plan.msm_launches) PTRY(lagrange_ready(d, e, &info.built_points));
   // the MSMs of the call: per vector over the points, or ONE run over the handle's tables — the commitments group after
   // group as their vectors become resident, the witness last
   const bool tabled = e->table && plan.msm_launches;
@@ -658,50 +662,35 @@ int evals_impl(const char* api_fn, plonk_kzg_domain* dom, const void* const* vec
     if (!vecs[i]) API_FAIL(PLONK_ERR_ARG, "invalid argument: evals[i] is NULL");
   EvalsCall a = {vecs, count, resident, open, Fr::zero(), Fr::one(), evaluations, commitments48, witness48};
   if (open && (!kzg_fr_load(point, &a.z) || (v_challenge && !kzg_fr_load(v_challenge, &a.v)))) API_FAIL(PLONK_ERR_DATA, "non-canonical scalar");
-  const KzdView dv = kzd_view(dom);
-  Ctx& c = *dv.c;
-  CTX_ENTER(c, api_fn);
-  HIP_TRY(hipSetDevice(c.device));
-  if (!dv.key_current) API_FAIL(PLONK_ERR_STATE, "the domain is bound to a commit key that was replaced on its context");
-  if (c.nccl_comm) API_FAIL(PLONK_ERR_STATE, "a context with a communicator holds only a range of the commit key");
-  if (!resident) {   // before anything is queued or written
-    Fr t;
-    for (uint64_t i = 0; i < count; ++i)
-      for (uint64_t k = 0; k < (1ull << dv.log_n); ++k)
-        if (!kzg_fr_load((const uint64_t*)vecs[i] + 4 * k, &t)) API_FAIL(PLONK_ERR_DATA, "a value is not a canonical residue");
-  }
-  KzgEvals* e = kze_state(dv);
+  KzgDomain* d = dom->d;
+  KZD_ENTER(d, api_fn, KZD_WORK);
+  // before anything is queued or written
+  if (!resident && !kze_host_canonical(vecs, count, 1ull << d->log_n)) API_FAIL(PLONK_ERR_DATA, "a value is not a canonical residue");
+  KzgEvals* e = kzd_state(d->evals);
   if (!count) {
     if (witness48) identity48(witness48);
     plonk_kzg_evals_info info = {};
-    info.log_n = dv.log_n;
+    info.log_n = d->log_n;
     info.in_domain_index = KZE_NONE;
-    info.msm_terms = 1ull << dv.log_n;
+    info.msm_terms = 1ull << d->log_n;
     info.lagrange_bytes = e->lag_bytes;
     e->last = info;
     return PLONK_OK;
   }
-  const int rc = evals_body(api_fn, dv, e, a);
-  if (rc != PLONK_OK) {   // an error leaves nothing of the call queued
-    if (c.copy_stream) (void)hipStreamSynchronize(c.copy_stream);
-    (void)hipStreamSynchronize(c.stream);
-  }
-  return rc;
+  return kzd_drained(d->c, evals_body(api_fn, d, e, a));
 }
 
 }  // namespace
 
-void kze_release(void* evals) { delete (KzgEvals*)evals; }
-
-int kze_points_ready(const KzdView& v, uint32_t* built) { return lagrange_ready(v, kze_state(v), built); }
-int kze_commit_values(const KzdView& v, const Fr* s, uint8_t out48[48]) {
-  return commit_values(v.c, kze_state(v), s, 1ull << v.log_n, out48);
+int kze_points_ready(KzgDomain* d, uint32_t* built) { return lagrange_ready(d, kzd_state(d->evals), built); }
+int kze_commit_values(KzgDomain* d, const Fr* s, uint8_t out48[48]) {
+  return commit_values(d->c, kzd_state(d->evals), s, 1ull << d->log_n, out48);
 }
-int kze_commit_list(const KzdView& v, const Fr* const* s, uint64_t count, uint8_t* out48) {
-  return commit_list(v.c, kze_state(v), s, count, 1ull << v.log_n, out48);
+int kze_commit_list(KzgDomain* d, const Fr* const* s, uint64_t count, uint8_t* out48) {
+  return commit_list(d->c, kzd_state(d->evals), s, count, 1ull << d->log_n, out48);
 }
-void kze_tables_call_begin(const KzdView& v) {
-  KzgEvals* e = kze_state(v);
+void kze_tables_call_begin(KzgDomain* d) {
+  KzgEvals* e = kzd_state(d->evals);
   if (e->table) tables_call_begin(e);
 }
 
@@ -746,15 +735,13 @@ int plonk_kzg_evals_last(plonk_kzg_domain* dom, plonk_kzg_evals_info* out) {
   const char* const api_fn = __func__;
   return plonk::api_guard(api_fn, [&]() -> int {
   if (!dom || !out) API_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
-  const KzdView dv = kzd_view(dom);
-  Ctx& c = *dv.c;
-  CTX_ENTER(c, api_fn);
-  if (!dv.key_current) API_FAIL(PLONK_ERR_STATE, "the domain is bound to a commit key that was replaced on its context");
-  const KzgEvals* e = (const KzgEvals*)*dv.evals;
+  const KzgDomain* d = dom->d;
+  KZD_ENTER(d, api_fn, KZD_KEY);
+  const KzgEvals* e = d->evals;
   plonk_kzg_evals_info info = {};
-  info.log_n = dv.log_n;
+  info.log_n = d->log_n;
   info.in_domain_index = KZE_NONE;
-  info.msm_terms = 1ull << dv.log_n;
+  info.msm_terms = 1ull << d->log_n;
   if (e) {
     info = e->last.log_n ? e->last : info;
     info.lagrange_bytes = e->lag_bytes;
@@ -768,22 +755,19 @@ int plonk_kzg_evals_tables_build(plonk_kzg_domain* dom) {
   const char* const api_fn = __func__;
   return plonk::api_guard(api_fn, [&]() -> int {
   if (!dom) API_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
-  const KzdView dv = kzd_view(dom);
-  Ctx& c = *dv.c;
-  CTX_ENTER(c, api_fn);
-  HIP_TRY(hipSetDevice(c.device));
-  if (!dv.key_current) API_FAIL(PLONK_ERR_STATE, "the domain is bound to a commit key that was replaced on its context");
-  if (c.nccl_comm) API_FAIL(PLONK_ERR_STATE, "a context with a communicator holds only a range of the commit key");
-  KzgEvals* e = kze_state(dv);
+  KzgDomain* d = dom->d;
+  Ctx& c = *d->c;
+  KZD_ENTER(d, api_fn, KZD_WORK);
+  KzgEvals* e = kzd_state(d->evals);
   if (e->table) {
     e->tl.built = 0;
     return PLONK_OK;
   }
-  const uint64_t n = 1ull << dv.log_n;
+  const uint64_t n = 1ull << d->log_n;
   // srs_table_build's refusal, before the points are allocated
   if ((uint64_t)msm_table_rows(&c, n, true) * n > (1ull << 31)) API_FAIL(PLONK_ERR_ARG, "invalid argument: table rows * points must be <= 2^31");
   uint32_t built_points = 0;
-  PTRY(lagrange_ready(dv, e, &built_points));
+  PTRY(lagrange_ready(d, e, &built_points));
   void* t = nullptr;
   uint32_t rows = 0;
   PTRY(srs_table_build(&c, e->lag, n, &t, &rows));
@@ -801,11 +785,9 @@ int plonk_kzg_evals_tables_drop(plonk_kzg_domain* dom) {
   const char* const api_fn = __func__;
   return plonk::api_guard(api_fn, [&]() -> int {
   if (!dom) API_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
-  const KzdView dv = kzd_view(dom);
-  Ctx& c = *dv.c;
-  CTX_ENTER(c, api_fn);
-  HIP_TRY(hipSetDevice(c.device));
-  if (*dv.evals) ((KzgEvals*)*dv.evals)->drop_tables();
+  KzgDomain* d = dom->d;
+  KZD_ENTER(d, api_fn, KZD_SET_DEVICE);
+  if (d->evals) d->evals->drop_tables();
   return PLONK_OK;
   });
 }
@@ -814,17 +796,16 @@ int plonk_kzg_evals_tables_last(plonk_kzg_domain* dom, plonk_kzg_evals_tables_in
   const char* const api_fn = __func__;
   return plonk::api_guard(api_fn, [&]() -> int {
   if (!dom || !out) API_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
-  const KzdView dv = kzd_view(dom);
-  Ctx& c = *dv.c;
-  CTX_ENTER(c, api_fn);
-  const KzgEvals* e = (const KzgEvals*)*dv.evals;
+  const KzgDomain* d = dom->d;
+  KZD_ENTER(d, api_fn, 0);
+  const KzgEvals* e = d->evals;
   plonk_kzg_evals_tables_info info = {};
   if (e && e->table) {
     info = e->tl;
     info.table_rows = e->tab_rows;
     info.table_bytes = sizeof(G1AffineR) * (uint64_t)e->tab_rows * e->tab_n;
   }
-  info.log_n = dv.log_n;
+  info.log_n = d->log_n;
   *out = info;
   return PLONK_OK;
   });

@@ -16,7 +16,7 @@ struct KzeMeta {              // what the host reads back before anything else o
 
 // den[i] = w^i - z, i < n = 2^log_n; meta->m = the lane where that is zero (the caller presets KZE_NONE)
 int kze_denominators(Ctx* c, uint32_t log_n, const Fr& z, Fr* den, KzeMeta* meta);
-// meta->bad |= 1 when one of the n values of vecs[first .. first + cnt) is >= q
+// meta->bad |= 1 when one of the n values of vecs[first .. first + cnt) is >= q (any cnt: a launch per 32768 vectors)
 int kze_scan(Ctx* c, const Fr* const* vecs, uint32_t first, uint32_t cnt, uint64_t n, KzeMeta* meta);
 
 struct KzeFoldArgs {
@@ -39,34 +39,22 @@ int kze_quotient(Ctx* c, uint32_t log_n, const Fr* fold, const Fr* inv, const Fr
 // (n points are enough); tw: kzd_twiddles_create's table for tw_log > log_n.  Returns with the stream synchronised.
 int kze_lagrange_points(Ctx* c, uint32_t log_n, const GlvScalar* tw, uint32_t tw_log, G1Affine* out);
 
-// kzg_domain.hip: what the evaluation-form calls need of a handle
-struct KzdView {
-  Ctx* c;
-  uint32_t log_n;
-  bool key_current;        // the context still holds the commit key the handle was built on
-  const GlvScalar* tw;     // w_(2n)^e, e < n
-  void** evals;            // the handle's slot for the state of kzg_evals.hip, released through kze_release
-  void** cells;            // the handle's slot for the state of kzg_cells.hip, released through kzc_release
-  uint64_t ws_cap;         // the cap on the point workspace of a call
-  void** recover;          // the handle's slot for the state of kzg_recover.hip, released through kzr_release
-  void** multi;            // the handle's slot for the state of kzg_multiproof.hip, released through kmp_release
-};
-KzdView kzd_view(plonk_kzg_domain* dom);
-void kze_release(void* evals);
-void kzr_release(void* recover);   // kzg_recover.hip
-void kmp_release(void* multi);     // kzg_multiproof.hip
+// every one of the n values (4 limbs each) of the `count` HOST vectors is a canonical residue
+bool kze_host_canonical(const void* const* vecs, uint64_t count, uint64_t n);
 
-// What kzg_multiproof.hip shares with the evaluation-form calls of the handle: the resident Lagrange points (built by whichever
-// call commits first; *built = 1 when this one did) and the commitment over them, sum_i s[i] [L_i(tau)] G as 48 compressed
-// bytes (returns with the stream synchronised; plonk_ctx_last_msm_points keeps reporting the caller's own last call).
-int kze_points_ready(const KzdView& v, uint32_t* built);
-int kze_commit_values(const KzdView& v, const Fr* s, uint8_t out48[48]);
+// What kzg_multiproof.hip shares with the evaluation-form calls of the handle (kzg_handle.hpp): the resident Lagrange points
+// (built by whichever call commits first; *built = 1 when this one did) and the commitment over them, sum_i s[i] [L_i(tau)] G
+// as 48 compressed bytes (returns with the stream synchronised; plonk_ctx_last_msm_points keeps reporting the caller's own
+// last call).
+struct KzgDomain;
+int kze_points_ready(KzgDomain* d, uint32_t* built);
+int kze_commit_values(KzgDomain* d, const Fr* s, uint8_t out48[48]);
 // the same for `count` resident vectors, out48[48 j] for s[j]: one after the other on a handle without tables, as ONE run of
 // grouped table launches on a handle that holds them (kzg_evals_core.hpp kze_tables_plan)
-int kze_commit_list(const KzdView& v, const Fr* const* s, uint64_t count, uint8_t* out48);
+int kze_commit_list(KzgDomain* d, const Fr* const* s, uint64_t count, uint8_t* out48);
 // a call that may use the handle's tables starts here: what plonk_kzg_evals_tables_last reports of "the last call" is
 // counted from this point on (kze_commit_values / kze_commit_list add to it)
-void kze_tables_call_begin(const KzdView& v);
+void kze_tables_call_begin(KzgDomain* d);
 
 // kze_finish_kernel: out48[48 i] = the compressed commitment of bits[MSM_BIT_SUMS i ...], i < count — the chain of
 // finish_bit_sums (rb row bits, bitpos: 2 W - S), the affine normalisation and G1Affine::to_bytes, one lane per commitment

@@ -33,7 +33,7 @@
 #include "hostg1.hpp"
 #include "kzg_core.hpp"
 #include "kzg_key.hpp"
-#include "kzg_domain.hpp"
+#include "kzg_handle.hpp"
 #include "kzg_evals.hpp"
 #include "kzg_multiproof.hpp"
 
@@ -227,19 +227,14 @@ __global__ void __launch_bounds__(KMP_LANES) kmp_weights_kernel(const Fr* __rest
 }
 
 // ---- launchers (kzg_multiproof.hpp) ------------------------------------------------------------------------------------------
-static int kmp_bad_args(const char* what) {
-  set_last_error(what, "invalid argument", __FILE__, __LINE__);
-  return PLONK_ERR_ARG;
-}
-
 int kmp_invd(Ctx* c, uint32_t log_n, Fr* invd, KzeMeta* meta) {
-  if (log_n < 1 || log_n > 32) return kmp_bad_args("kmp_invd");
+  if (log_n < 1 || log_n > 32) return kzg_bad_args("kmp_invd");
   PTRY(kze_denominators(c, log_n, Fr::one(), invd, meta));
   return poly_batch_inverse(c, invd, 1ull << log_n);
 }
 
 int kmp_gather(Ctx* c, const Fr* const* vecs, const uint32_t* vector_index, const uint32_t* point_index, uint64_t K, Fr* yk) {
-  if (!K || K > KMP_MAX_ITEMS) return kmp_bad_args("kmp_gather");
+  if (!K || K > KMP_MAX_ITEMS) return kzg_bad_args("kmp_gather");
   hipLaunchKernelGGL(kmp_gather_kernel, dim3((uint32_t)((K + 255) / 256)), dim3(256), 0, c->stream, vecs, vector_index, point_index,
                      (uint32_t)K, yk);
   HIP_TRY(hipGetLastError());
@@ -248,7 +243,7 @@ int kmp_gather(Ctx* c, const Fr* const* vecs, const uint32_t* vector_index, cons
 
 int kmp_groups(Ctx* c, uint32_t log_n, const Fr* rpow, const Fr* yk, const uint32_t* perm, const uint32_t* group_m,
                const uint32_t* group_off, uint64_t groups, Fr* ym, void* cw, Fr* negw) {
-  if (!groups || groups > KMP_MAX_ITEMS || log_n < 1 || log_n > 32) return kmp_bad_args("kmp_groups");
+  if (!groups || groups > KMP_MAX_ITEMS || log_n < 1 || log_n > 32) return kzg_bad_args("kmp_groups");
   hipLaunchKernelGGL(kmp_groups_kernel, dim3((uint32_t)groups), dim3(KMP_LANES), 0, c->stream, fr_domain_root(log_n).inv(),
                      Fr::from_u64(32), rpow, yk, perm, group_m, group_off, ym, cw, negw);
   HIP_TRY(hipGetLastError());
@@ -256,7 +251,7 @@ int kmp_groups(Ctx* c, uint32_t log_n, const Fr* rpow, const Fr* yk, const uint3
 }
 
 int kmp_aggregate(Ctx* c, const KmpAggArgs& a, uint64_t groups) {
-  if (!groups || groups > KMP_MAX_ITEMS || a.n != (1ull << a.log_n) || a.log_n < 1 || a.log_n > 32) return kmp_bad_args("kmp_aggregate");
+  if (!groups || groups > KMP_MAX_ITEMS || a.n != (1ull << a.log_n) || a.log_n < 1 || a.log_n > 32) return kzg_bad_args("kmp_aggregate");
   const uint32_t nwaves = kze_fold_waves(a.n), blocks = kze_fold_blocks(a.n);
   const Fr w = fr_domain_root(a.log_n), w_step = w.pow_u64(KMP_AGG_T);
   prof_begin(c, 12);   // slot 12: every aggregate and fix launch of the call
@@ -273,7 +268,7 @@ int kmp_aggregate(Ctx* c, const KmpAggArgs& a, uint64_t groups) {
 
 int kmp_weights(Ctx* c, uint32_t log_n, const Fr& t, const uint32_t* point_index, const Fr* rpow, const Fr* yk, const uint32_t* perm,
                 const uint32_t* off, uint64_t K, uint64_t M, Fr* wt, void* stw, Fr* y_out, uint32_t* sc, uint32_t* ids) {
-  if (!K || K > KMP_MAX_ITEMS || !M || M > KMP_MAX_VECTORS || log_n < 1 || log_n > 32) return kmp_bad_args("kmp_weights");
+  if (!K || K > KMP_MAX_ITEMS || !M || M > KMP_MAX_VECTORS || log_n < 1 || log_n > 32) return kzg_bad_args("kmp_weights");
   hipLaunchKernelGGL(kmp_weights_den_kernel, dim3((uint32_t)((K + 255) / 256)), dim3(256), 0, c->stream, fr_domain_root(log_n), t,
                      point_index, (uint32_t)K, wt);
   HIP_TRY(hipGetLastError());
@@ -285,8 +280,6 @@ int kmp_weights(Ctx* c, uint32_t log_n, const Fr& t, const uint32_t* point_index
 }
 
 // ---- the state a domain handle holds for plonk_kzg_multiproof_open ------------------------------------------------------------
-namespace {
-
 struct KmpBufs {
   enum { VECS, STAGE, VIDX, MIDX, PERM_M, GROUP_M, GROUP_OFF, PERM_V, OFF_V, YK, RPOW, RTW, YM, CW, NEGW, G, PARTIAL, WT, STW, YOUT, DEN,
          FOLD_PARTIAL, EVALS, Q, QPART, META, NBUF };   // grow-only
@@ -299,10 +292,9 @@ struct KzgMulti : KmpBufs, DevBufs<KmpBufs::NBUF> {
   ~KzgMulti() { (void)hipFree(invd); }
 };
 
-KzgMulti* kmp_state(const KzdView& v) {
-  if (!*v.multi) *v.multi = new KzgMulti();
-  return (KzgMulti*)*v.multi;
-}
+void kmp_release(KzgMulti* multi) { delete multi; }
+
+namespace {
 
 struct StreamDrain {   // an error leaves nothing of the call queued, and nothing reads the host vectors of the call after they are gone
   Ctx& c;
@@ -326,9 +318,9 @@ struct OpenCall {
   uint8_t* proof96;
 };
 
-int open_body(const char* api_fn, const KzdView& dv, KzgMulti* s, const OpenCall& a) {
-  Ctx& c = *dv.c;
-  const uint32_t L = dv.log_n;
+int open_body(const char* api_fn, KzgDomain* d, KzgMulti* s, const OpenCall& a) {
+  Ctx& c = *d->c;
+  const uint32_t L = d->log_n;
   const uint64_t n = 1ull << L, M = a.M, K = a.K;
   // the host side of the call: sorted before anything is queued
   std::vector<uint32_t> perm_m(K), group_m(K < n ? K : n), group_off((K < n ? K : n) + 1), scratch(n + 1), perm_v(K), off_v(M + 1);
@@ -368,8 +360,7 @@ int open_body(const char* api_fn, const KzdView& dv, KzgMulti* s, const OpenCall
   if (a.resident) {
     KzeMeta mh = {KZE_NONE, 0};
     HIP_TRY(hipMemcpyAsync(s->p[KzgMulti::META], &mh, sizeof mh, hipMemcpyHostToDevice, c.stream));
-    for (uint64_t first = 0; first < M; first += 32768)   // grid.y
-      PTRY(kze_scan(&c, vecs, (uint32_t)first, (uint32_t)(M - first < 32768 ? M - first : 32768), n, s->at<KzeMeta>(KzgMulti::META)));
+    PTRY(kze_scan(&c, vecs, 0, (uint32_t)M, n, s->at<KzeMeta>(KzgMulti::META)));
     HIP_TRY(hipMemcpyAsync(&mh, s->p[KzgMulti::META], sizeof mh, hipMemcpyDeviceToHost, c.stream));
     HIP_TRY(hipStreamSynchronize(c.stream));
     if (mh.bad) API_FAIL(PLONK_ERR_DATA, "a value is not a canonical residue");
@@ -392,12 +383,12 @@ int open_body(const char* api_fn, const KzdView& dv, KzgMulti* s, const OpenCall
   HIP_TRY(hipMemcpyAsync(yk.data(), s->p[KzgMulti::YK], sizeof(Fr) * K, hipMemcpyDeviceToHost, c.stream));
   HIP_TRY(hipStreamSynchronize(c.stream));
   // ---- the commitments and r ----
-  PTRY(kze_points_ready(dv, &info.built_points));
-  kze_tables_call_begin(dv);   // (a handle with tables: the M commitments are one run of grouped launches, D and pi one launch each)
+  PTRY(kze_points_ready(d, &info.built_points));
+  kze_tables_call_begin(d);   // (a handle with tables: the M commitments are one run of grouped launches, D and pi one launch each)
   if (a.commitments_in) {
     memcpy(cm.data(), a.commitments_in, 48 * M);
   } else {
-    PTRY(kze_commit_list(dv, table.data(), M, cm.data()));
+    PTRY(kze_commit_list(d, table.data(), M, cm.data()));
   }
   Transcript tr(a.label, a.label_len);
   Fr r = a.r, t = a.t;
@@ -451,7 +442,7 @@ int open_body(const char* api_fn, const KzdView& dv, KzgMulti* s, const OpenCall
   ag.partial = s->at<Fr>(KzgMulti::PARTIAL);
   PTRY(kmp_aggregate(&c, ag, groups));
   uint8_t proof[96];
-  PTRY(kze_commit_values(dv, ag.g, proof));
+  PTRY(kze_commit_values(d, ag.g, proof));
   // ---- t, h - g, the opening at t ----
   if (!a.has_override) {
     t = kmp_challenge_t(tr, proof);
@@ -483,7 +474,7 @@ int open_body(const char* api_fn, const KzdView& dv, KzgMulti* s, const OpenCall
   HIP_TRY(hipMemcpyAsync(&y, s->p[KzgMulti::YOUT], sizeof y, hipMemcpyDeviceToHost, c.stream));
   HIP_TRY(hipStreamSynchronize(c.stream));
   PTRY(kze_quotient(&c, L, ag.g, s->at<Fr>(KzgMulti::DEN), y, KZE_NONE, s->at<Fr>(KzgMulti::Q), s->at<Fr>(KzgMulti::QPART)));
-  PTRY(kze_commit_values(dv, s->at<Fr>(KzgMulti::Q), proof + 48));
+  PTRY(kze_commit_values(d, s->at<Fr>(KzgMulti::Q), proof + 48));
   // ---- the call's outputs ----
   memcpy(a.values, yk.data(), sizeof(Fr) * K);
   if (a.commitments_out) memcpy(a.commitments_out, cm.data(), 48 * M);
@@ -499,27 +490,18 @@ int open_impl(const char* api_fn, plonk_kzg_domain* dom, const void* const* vecs
               const uint64_t* challenges_override, uint64_t* values, uint8_t* commitments_out, uint8_t* proof96, bool resident) {
   if (!dom || !vecs || !vector_index || !point_index || !values || !proof96 || (label_len && !label))
     API_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
-  const KzdView dv = kzd_view(dom);
-  if (kmp_check_items(dv.log_n, nvectors, vector_index, point_index, count, !resident, false))
+  KzgDomain* d = dom->d;
+  if (kmp_check_items(d->log_n, nvectors, vector_index, point_index, count, !resident, false))
     API_FAIL(PLONK_ERR_ARG, "invalid argument: count must be in [1, 2^20], nvectors in [1, 65536], every index in range and (host form) nvectors * n <= 2^28");
   for (uint64_t j = 0; j < nvectors; ++j)
     if (!vecs[j]) API_FAIL(PLONK_ERR_ARG, "invalid argument: evals[j] is NULL");
   OpenCall a = {vecs, nvectors, commitments_in, vector_index, point_index, count, label, label_len, challenges_override != nullptr,
                 Fr::zero(), Fr::zero(), resident, values, commitments_out, proof96};
-  if (kmp_check_override(challenges_override, dv.log_n, &a.r, &a.t))
+  if (kmp_check_override(challenges_override, d->log_n, &a.r, &a.t))
     API_FAIL(PLONK_ERR_DATA, "the challenges override is not canonical, or its t lies in the domain");
-  if (!resident) {
-    Fr x;
-    for (uint64_t j = 0; j < nvectors; ++j)
-      for (uint64_t i = 0; i < (1ull << dv.log_n); ++i)
-        if (!kzg_fr_load((const uint64_t*)vecs[j] + 4 * i, &x)) API_FAIL(PLONK_ERR_DATA, "a value is not a canonical residue");
-  }
-  Ctx& c = *dv.c;
-  CTX_ENTER(c, api_fn);
-  HIP_TRY(hipSetDevice(c.device));
-  if (!dv.key_current) API_FAIL(PLONK_ERR_STATE, "the domain is bound to a commit key that was replaced on its context");
-  if (c.nccl_comm) API_FAIL(PLONK_ERR_STATE, "a context with a communicator holds only a range of the commit key");
-  return open_body(api_fn, dv, kmp_state(dv), a);
+  if (!resident && !kze_host_canonical(vecs, nvectors, 1ull << d->log_n)) API_FAIL(PLONK_ERR_DATA, "a value is not a canonical residue");
+  KZD_ENTER(d, api_fn, KZD_WORK);
+  return open_body(api_fn, d, kzd_state(d->multi), a);
 }
 
 // ---- plonk_kzg_multiproof_check: the workspace hangs off the key ----------------------------------------------------------------
@@ -527,10 +509,6 @@ struct KmcBufs {
   enum { COMP, PTS, KIND, SC, IDS, MIDX, PERM_V, OFF_V, YK, RPOW, WT, NBUF };   // grow-only
 };
 struct KzgMultiCheck : KmcBufs, DevBufs<KmcBufs::NBUF> {};
-
-double ms_between(std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
-  return std::chrono::duration<double, std::milli>(b - a).count();
-}
 
 struct CheckCall {
   uint32_t log_n;
@@ -630,7 +608,6 @@ int check_body(const char* api_fn, KzgKey* kk, const CheckCall& a, plonk_verify_
 
 }  // namespace
 
-void kmp_release(void* multi) { delete (KzgMulti*)multi; }
 void kmp_check_release(void* ws) { delete (KzgMultiCheck*)ws; }
 
 KzgKey::~KzgKey() {
@@ -670,14 +647,12 @@ int plonk_kzg_multiproof_last(plonk_kzg_domain* domain, plonk_kzg_multiproof_inf
   const char* const api_fn = __func__;
   return plonk::api_guard(api_fn, [&]() -> int {
   if (!domain || !out) API_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
-  const KzdView dv = kzd_view(domain);
-  Ctx& c = *dv.c;
-  CTX_ENTER(c, api_fn);
-  if (!dv.key_current) API_FAIL(PLONK_ERR_STATE, "the domain is bound to a commit key that was replaced on its context");
-  const KzgMulti* s = (const KzgMulti*)*dv.multi;
+  const KzgDomain* d = domain->d;
+  KZD_ENTER(d, api_fn, KZD_KEY);
+  const KzgMulti* s = d->multi;
   plonk_kzg_multiproof_info info = {};
-  info.log_n = dv.log_n;
-  info.msm_terms = 1ull << dv.log_n;
+  info.log_n = d->log_n;
+  info.msm_terms = 1ull << d->log_n;
   if (s) {
     if (s->last.log_n) info = s->last;
     info.device_bytes = s->invd_bytes + s->bytes();
@@ -716,9 +691,8 @@ int plonk_kzg_multiproof_check(plonk_kzg_key* key, uint32_t log_n, const uint8_t
 // KzgDomain._multi_last_challenges: r and t of the handle's last plonk_kzg_multiproof_open (Montgomery limbs).
 int plonk_test_kzg_multiproof_last_challenges(plonk_kzg_domain* domain, uint64_t out[8]) {
   if (!domain || !out) return PLONK_ERR_ARG;
-  const KzdView dv = kzd_view(domain);
-  std::lock_guard<std::mutex> lk(dv.c->mu);
-  const KzgMulti* s = (const KzgMulti*)*dv.multi;
+  std::lock_guard<std::mutex> lk(domain->d->c->mu);
+  const KzgMulti* s = domain->d->multi;
   if (!s) return PLONK_ERR_STATE;
   memcpy(out, s->last_r.l, 32);
   memcpy(out + 4, s->last_t.l, 32);

@@ -25,8 +25,7 @@
 #include "poly.hpp"
 #include "devmem.cuh"
 #include "kzg_core.hpp"
-#include "kzg_domain.hpp"
-#include "kzg_evals.hpp"
+#include "kzg_handle.hpp"
 #include "kzg_cells.hpp"
 #include "kzg_recover.hpp"
 
@@ -137,8 +136,6 @@ int kzr_tail(Ctx* c, const Fr* coeffs, uint32_t log_n, uint64_t max_len, uint32_
 }
 
 // ---- the state a handle holds for these calls ------------------------------------------------------------------------------
-namespace {
-
 struct KzrBufs {
   enum { A, IO, CL, TMP, PW, ZDOM, ZCOSET, SLOT, MISS, VECS, FLAGS, LEN, DESC, META, NBUF };   // grow-only
 };
@@ -146,10 +143,9 @@ struct KzgRecover : KzrBufs, DevBufs<KzrBufs::NBUF> {
   plonk_kzg_recover_info last = {};
 };
 
-KzgRecover* kzr_state(void** slot) {
-  if (!*slot) *slot = new KzgRecover();
-  return (KzgRecover*)*slot;
-}
+void kzr_release(KzgRecover* recover) { delete recover; }
+
+namespace {
 
 struct RecoverCall {
   uint32_t log_cell;
@@ -163,9 +159,9 @@ struct RecoverCall {
 };
 
 // steps 1 to 3 of the mathematics for polynomials [first, first + cnt): their coefficients in A
-int recover_chunk(const KzdView& v, KzgRecover* e, const RecoverCall& a, uint64_t first, uint32_t cnt) {
-  Ctx& c = *v.c;
-  const uint32_t L = v.log_n;
+int recover_chunk(const KzgDomain* d, KzgRecover* e, const RecoverCall& a, uint64_t first, uint32_t cnt) {
+  Ctx& c = *d->c;
+  const uint32_t L = d->log_n;
   const uint64_t n = 1ull << L, packed = a.available << a.log_cell;
   Fr* A = e->at<Fr>(KzgRecover::A);
   Fr* tmp = e->at<Fr>(KzgRecover::TMP);
@@ -198,12 +194,12 @@ int chunk_lengths(Ctx& c, KzgRecover* e, uint64_t n, uint32_t cnt, uint64_t* tri
   return PLONK_OK;
 }
 
-int recover_body(const char* api_fn, const KzdView& v, KzgRecover* e, const RecoverCall& a) {
-  Ctx& c = *v.c;
-  const uint32_t L = v.log_n, log_r = L - a.log_cell;
+int recover_body(const char* api_fn, KzgDomain* d, KzgRecover* e, const RecoverCall& a) {
+  Ctx& c = *d->c;
+  const uint32_t L = d->log_n, log_r = L - a.log_cell;
   const uint64_t n = 1ull << L, r = 1ull << log_r, count = a.count, packed = a.available << a.log_cell;
   const bool own_values = a.cells && !a.proofs48;   // with proofs the body of plonk_kzg_open_cells makes the cell values
-  const KzrPlan plan = kzr_plan(L, a.log_cell, count, a.available, v.ws_cap, a.cells || a.proofs48);
+  const KzrPlan plan = kzr_plan(L, a.log_cell, count, a.available, d->ws_cap, a.cells || a.proofs48);
   const uint64_t chunk = plan.chunk_polys;
   plonk_kzg_recover_info info = {};
   info.log_n = L;
@@ -250,7 +246,7 @@ int recover_body(const char* api_fn, const KzdView& v, KzgRecover* e, const Reco
   // ---- the verdict of every polynomial, before anything is written ----
   for (uint64_t first = 0; first < count; first += chunk) {
     const uint32_t cnt = (uint32_t)(count - first < chunk ? count - first : chunk);
-    PTRY(recover_chunk(v, e, a, first, cnt));
+    PTRY(recover_chunk(d, e, a, first, cnt));
     PTRY(kzr_tail(&c, e->at<Fr>(KzgRecover::A), L, a.max_len, cnt, e->at<int32_t>(KzgRecover::FLAGS) + first));
   }
   std::vector<int32_t> flags(count);
@@ -270,7 +266,7 @@ int recover_body(const char* api_fn, const KzdView& v, KzgRecover* e, const Reco
   Fr* A = e->at<Fr>(KzgRecover::A);
   for (uint64_t first = 0; first < count; first += chunk) {
     const uint32_t cnt = (uint32_t)(count - first < chunk ? count - first : chunk);
-    if (plan.passes > 1) PTRY(recover_chunk(v, e, a, first, cnt));   // (a single chunk still holds its coefficients)
+    if (plan.passes > 1) PTRY(recover_chunk(d, e, a, first, cnt));   // (a single chunk still holds its coefficients)
     if (a.coeffs) HIP_TRY(hipMemcpyAsync((uint8_t*)a.coeffs + sizeof(Fr) * n * first, A, sizeof(Fr) * n * cnt, hipMemcpyDefault, c.stream));
     if (own_values) {
       Fr* ev = e->at<Fr>(KzgRecover::IO);
@@ -283,13 +279,11 @@ int recover_body(const char* api_fn, const KzdView& v, KzgRecover* e, const Reco
     if (a.proofs48 || a.commitments48) PTRY(chunk_lengths(c, e, n, cnt, trimmed.data()));
     if (a.proofs48) {
       for (uint32_t b = 0; b < cnt; ++b) ptrs[b] = A + (uint64_t)b * n;
-      PTRY(kzc_open_resident(v, a.log_cell, ptrs.data(), trimmed.data(), cnt, a.cells ? (uint8_t*)a.cells + sizeof(Fr) * n * first : nullptr,
+      PTRY(kzc_open_resident(d, a.log_cell, ptrs.data(), trimmed.data(), cnt, a.cells ? (uint8_t*)a.cells + sizeof(Fr) * n * first : nullptr,
                              (uint8_t*)a.proofs48 + 48 * r * first, a.commitments48 ? (uint8_t*)a.commitments48 + 48 * first : nullptr,
                              &info.built_table));
     } else if (a.commitments48) {
-      comm.resize(48ull * cnt);
-      PTRY(kzd_commit(&c, A, n, trimmed.data(), cnt, comm.data()));
-      HIP_TRY(hipMemcpyAsync((uint8_t*)a.commitments48 + 48 * first, comm.data(), 48ull * cnt, hipMemcpyDefault, c.stream));
+      PTRY(kzd_commit(&c, A, n, trimmed.data(), cnt, comm, (uint8_t*)a.commitments48 + 48 * first));
     }
     HIP_TRY(hipStreamSynchronize(c.stream));   // the chunk's buffers are reused by the next one
   }
@@ -299,37 +293,24 @@ int recover_body(const char* api_fn, const KzdView& v, KzgRecover* e, const Reco
 
 int recover_impl(const char* api_fn, plonk_kzg_domain* dom, const RecoverCall& a) {
   if (!dom) API_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
-  const KzdView v = kzd_view(dom);
+  KzgDomain* d = dom->d;
   bool all_set = a.values != nullptr;
   for (uint64_t b = 0; all_set && b < a.count && a.count <= KZD_MAX_COUNT; ++b) all_set = a.values[b] != nullptr;
-  if (kzr_check_args(true, v.log_n, a.log_cell, a.count, a.cell_ids, a.available, a.values != nullptr, all_set, a.max_len,
+  if (kzr_check_args(true, d->log_n, a.log_cell, a.count, a.cell_ids, a.available, a.values != nullptr, all_set, a.max_len,
                      a.coeffs || a.cells || a.proofs48 || a.commitments48))
     API_FAIL(PLONK_ERR_ARG, "invalid argument: a NULL pointer, log_cell outside [1, log_n - 1], more than 2048 cells, count > 65536, "
                             "a cell index out of range or repeated, max_len outside [1, n], or no output at all");
-  Ctx& c = *v.c;
-  CTX_ENTER(c, api_fn);
-  HIP_TRY(hipSetDevice(c.device));
-  if (!kzd_view(dom).key_current) API_FAIL(PLONK_ERR_STATE, "the domain is bound to a commit key that was replaced on its context");
-  if (c.nccl_comm) API_FAIL(PLONK_ERR_STATE, "a context with a communicator holds only a range of the commit key");
+  KZD_ENTER(d, api_fn, KZD_WORK);
   if (!a.count) return PLONK_OK;
   if (kzr_check_degree(a.log_cell, a.available, a.max_len)) API_FAIL(PLONK_ERR_DEGREE, "max_len exceeds the values given: too few cells");
-  KzgRecover* e = kzr_state(v.recover);
+  KzgRecover* e = kzd_state(d->recover);
   // canonical values, as plonk_kzg_open_cells checks its coefficients: on the host, or by a scan of the resident arrays
   std::vector<uint64_t> lens(a.count, a.available << a.log_cell), trimmed(a.count);
-  if (a.resident) {
-    PTRY(e->need(KzgRecover::DESC, sizeof(KzdDesc) * a.count));
-    PTRY(e->need(KzgRecover::META, 16 * a.count));
-  }
-  PTRY(kzd_lengths(api_fn, &c, v.log_n, a.values, lens.data(), a.count, a.resident, e->at<KzdDesc>(KzgRecover::DESC),
-                   e->at<unsigned long long>(KzgRecover::META), trimmed.data()));
-  const int rc = recover_body(api_fn, kzd_view(dom), e, a);
-  if (rc != PLONK_OK) (void)hipStreamSynchronize(c.stream);   // an error leaves nothing of the call queued
-  return rc;
+  PTRY(kzd_lengths_on(api_fn, d->c, e, d->log_n, a.values, lens.data(), a.count, a.resident, trimmed.data()));
+  return kzd_drained(d->c, recover_body(api_fn, d, e, a));
 }
 
 }  // namespace
-
-void kzr_release(void* recover) { delete (KzgRecover*)recover; }
 
 }  // namespace plonk
 
@@ -361,14 +342,12 @@ int plonk_kzg_recover_last(plonk_kzg_domain* dom, plonk_kzg_recover_info* out) {
   const char* const api_fn = __func__;
   return plonk::api_guard(api_fn, [&]() -> int {
   if (!dom || !out) API_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
-  const KzdView v = kzd_view(dom);
-  Ctx& c = *v.c;
-  CTX_ENTER(c, api_fn);
-  if (!kzd_view(dom).key_current) API_FAIL(PLONK_ERR_STATE, "the domain is bound to a commit key that was replaced on its context");
-  const KzgRecover* e = (const KzgRecover*)*v.recover;
+  const KzgDomain* d = dom->d;
+  KZD_ENTER(d, api_fn, KZD_KEY);
+  const KzgRecover* e = d->recover;
   plonk_kzg_recover_info info = {};
   if (e) info = e->last;
-  info.log_n = v.log_n;
+  info.log_n = d->log_n;
   *out = info;
   return PLONK_OK;
   });

@@ -6,8 +6,6 @@
 // (positive).  Slots are loaded and read back through the doors of dev_kzg_domain.hip.  Test code only.
 #include <string.h>
 
-#include "kzg_domain.hpp"
-#include "kzg_evals.hpp"
 #include "kzg_cells.hpp"
 
 using namespace plonk;
@@ -67,9 +65,7 @@ int dkc_reduce(plonk_ctx* h, void* ws, uint64_t stride, uint32_t log_r, uint64_t
 // the slice count S of the handle's next plonk_kzg_open_cells calls (0 restores the plan's own choice)
 int dkc_set_slices(plonk_kzg_domain* dom, uint64_t slices) {
   if (!dom) return PLONK_ERR_ARG;
-  const KzdView v = kzd_view(dom);
-  std::lock_guard<std::mutex> lk(v.c->mu);
-  kzc_set_slices(v.cells, slices);
+  kzc_set_slices(dom, slices);
   return PLONK_OK;
 }
 
