@@ -858,6 +858,68 @@ int plonk_kzg_evals_tables_build(plonk_kzg_domain* domain);
 int plonk_kzg_evals_tables_drop(plonk_kzg_domain* domain);
 int plonk_kzg_evals_tables_last(plonk_kzg_domain* domain, plonk_kzg_evals_tables_info* out);
 
+/* ---- commitments of MANY SHORT vectors on a domain handle (opt-in window tables) ----------------------------
+ * Building or updating a vector-commitment tree means committing to very many short vectors (2^8 values: a tree node).  The
+ * MSM routes above pay a bucket sort and a reduction tail per commitment; for a short FIXED base neither is needed.  The
+ * handle is given window tables over its Lagrange points L_i = [L_i(tau)] G, n = 2^log_n <= 2^12: for a digit width c
+ * (window_bits) every value s < q is written in W(c) signed digits, s = sum_w d_w 2^(c w), d_w in [-2^(c-1), 2^(c-1)]
+ * (W = 128, 86, 64, 52, 43, 37, 32 for c = 2 .. 8: the smallest count for which no scalar below q carries out), and the
+ * tables hold every affine point [d 2^(c w)] L_i, d = 1 .. 2^(c-1): n x W x 2^(c-1) entries of 128 bytes (128 MiB for n = 2^8,
+ * c = 8).  One wave then owns a vector and adds its n x W table entries: mixed additions only, no doublings, no buckets.
+ *     commitments48[j] = sum_i values[j][i] L_i            the same 48 bytes plonk_kzg_commit_evals gives for that vector
+ *     update:   out_j = base_j + sum_(k in [offsets[j], offsets[j+1])) deltas[k] L_(index[k])
+ * plonk_kzg_many_tables_build: builds the Lagrange points if no call has yet, then the tables for window_bits = 2 .. 8; 0
+ *   picks the widest width whose tables fit what is left of the context's table budget.  The bytes count against that budget
+ *   and show in plonk_ctx_table_bytes while held, as for plonk_kzg_evals_tables_build; they are returned by
+ *   plonk_kzg_many_tables_drop and plonk_kzg_domain_destroy.  A second build with the width the handle holds is PLONK_OK with
+ *   built == 0; another width replaces the tables: the new ones are built beside the old, which a failed build keeps, so both
+ *   must fit the budget for that moment (PLONK_ERR_ARG otherwise: drop the old ones first).  A Lagrange point that is the identity (tau in the domain) gets entries of
+ *   128 zero bytes, which the accumulation skips.  PLONK_ERR_ARG for NULL, log_n > 12, window_bits outside {0, 2 .. 8}, and
+ *   for tables that do not fit what is left of the budget (window_bits == 0: no width fits); PLONK_ERR_STATE once the
+ *   context's key was reloaded, and on a context with a communicator.  A refused or failed build leaves the handle and the
+ *   budget as they were.
+ * plonk_kzg_many_tables_drop: frees them (PLONK_OK when the handle holds none; works after a key reload).
+ * plonk_kzg_commit_many: `values` holds count x n Montgomery Fr, vector after vector; count <= 2^24; count == 0 is PLONK_OK
+ *   and writes nothing.  The vectors are staged chunk by chunk through the two upload buffers of plonk_kzg_open, so count x n
+ *   is never resident.
+ * plonk_kzg_commit_many_dev: values_dev (16-byte aligned) and commitments48_dev (4-byte aligned) are DEVICE pointers on the
+ *   context's GPU, as for plonk_kzg_open_domain_dev: the values are read in place, the count x 48 bytes written there.
+ * plonk_kzg_update_many: the sparse form, count segments; index[k] < n; a repeated index inside a segment simply adds; an
+ *   empty segment returns its base re-encoded; base48 == NULL means the identity for every segment (a sparse commit).  The
+ *   identity (0xC0 00 ..) is a legal base.  count <= 2^24, offsets[count] <= 2^28, and one segment at most 2^16 terms (a
+ *   segment is one wave's work; longer sums are split by the caller and chained through base48).  All arrays are host memory.
+ * Errors of the three: PLONK_ERR_ARG for a NULL argument, a count, total or segment above its cap, offsets that do not start at 0 or
+ *   decrease, an index >= n, a misaligned device pointer; PLONK_ERR_DATA for a value or delta that is not a canonical residue;
+ *   PLONK_ERR_POINT for a base that does not decode or is not in the subgroup; PLONK_ERR_STATE when the handle holds no
+ *   many-vector tables (there is no fallback: use plonk_kzg_commit_evals), once the context's key was reloaded, and on a
+ *   context with a communicator.  Every check is made before anything of the call's result is queued or written: an error
+ *   leaves the outputs untouched.  The calls leave the context, its other tables, its provers, plonk_ctx_last_msm and
+ *   plonk_ctx_last_msm_points as they found them.
+ * plonk_kzg_many_last: the tables the handle holds and how the last of these calls ran: the tests assert it against the plan
+ *   computed on the host (plonk_amd/csrc/kzg_many_core.hpp). */
+typedef struct plonk_kzg_many_info {
+  uint32_t log_n;
+  uint32_t window_bits;       /* 0: the handle holds no many-vector tables */
+  uint32_t windows;           /* W(window_bits) */
+  uint32_t built;             /* 1: the last plonk_kzg_many_tables_build call built them (0: they were there) */
+  uint64_t table_bytes;       /* n x W x 2^(c-1) x 128, counted in plonk_ctx_table_bytes while held */
+  uint64_t count;             /* last call: vectors (segments) */
+  uint64_t terms;             /* values it added up: count x n, or offsets[count] */
+  uint64_t chunks;            /* chunks it ran in, under the handle's workspace cap */
+  uint64_t chunk_vectors;     /* vectors of a full chunk (sparse form: of the largest chunk) */
+  uint32_t slices;            /* partial sums per vector: > 1 when the call had too few vectors to fill the device */
+  uint32_t reserved;
+  uint64_t additions;         /* the bound terms x W on its mixed additions (zero digits are not counted on the device) */
+} plonk_kzg_many_info;
+int plonk_kzg_many_tables_build(plonk_kzg_domain* domain, uint32_t window_bits /* 2..8, 0 = automatic */);
+int plonk_kzg_many_tables_drop(plonk_kzg_domain* domain);
+int plonk_kzg_commit_many(plonk_kzg_domain* domain, const uint64_t* values /* count x n x 4, contiguous */, uint64_t count,
+                          uint8_t* commitments48 /* count x 48 */);
+int plonk_kzg_commit_many_dev(plonk_kzg_domain* domain, const void* values_dev, uint64_t count, void* commitments48_dev);
+int plonk_kzg_update_many(plonk_kzg_domain* domain, const uint8_t* base48 /* count x 48, or NULL */, const uint64_t* offsets /* count + 1 */,
+                          const uint32_t* index, const uint64_t* deltas /* offsets[count] x 4 */, uint64_t count, uint8_t* commitments48);
+int plonk_kzg_many_last(plonk_kzg_domain* domain, plonk_kzg_many_info* out);
+
 /* ---- KZG10 cell proofs: a polynomial opened on every coset of its domain --------------------------------
  * The n = 2^log_n evaluations of a polynomial cut into r = n / l cells of l = 2^log_cell values, each cell with ONE 48-byte
  * proof that opens all l of its values at once (Feist-Khovratovich section 3; data-availability sampling).  w is the generator

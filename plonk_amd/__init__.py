@@ -78,6 +78,8 @@ EXPORTS = [
     "plonk_kzg_commit_evals", "plonk_kzg_commit_evals_dev", "plonk_kzg_open_evals", "plonk_kzg_open_evals_dev",
     "plonk_kzg_evals_last",
     "plonk_kzg_evals_tables_build", "plonk_kzg_evals_tables_drop", "plonk_kzg_evals_tables_last",
+    "plonk_kzg_many_tables_build", "plonk_kzg_many_tables_drop", "plonk_kzg_commit_many", "plonk_kzg_commit_many_dev",
+    "plonk_kzg_update_many", "plonk_kzg_many_last",
     "plonk_kzg_open_cells", "plonk_kzg_open_cells_dev", "plonk_kzg_cell_points", "plonk_kzg_cells_last",
     "plonk_kzg_cell_verifier_create", "plonk_kzg_cell_verifier_destroy", "plonk_kzg_verify_cells", "plonk_kzg_verify_cells_each",
     "plonk_kzg_cell_verifier_last",
@@ -170,6 +172,14 @@ class _KzgEvalsTablesInfo(ctypes.Structure):
     _fields_ = [("log_n", ctypes.c_uint32), ("table_rows", ctypes.c_uint32), ("table_bytes", ctypes.c_uint64),
                 ("built", ctypes.c_uint32), ("bucket_bits", ctypes.c_uint32), ("msms", ctypes.c_uint64),
                 ("group_launches", ctypes.c_uint64), ("device_finished", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class _KzgManyInfo(ctypes.Structure):
+    """plonk_kzg_many_info (include/plonk_hip.h)"""
+    _fields_ = [("log_n", ctypes.c_uint32), ("window_bits", ctypes.c_uint32), ("windows", ctypes.c_uint32), ("built", ctypes.c_uint32),
+                ("table_bytes", ctypes.c_uint64), ("count", ctypes.c_uint64), ("terms", ctypes.c_uint64), ("chunks", ctypes.c_uint64),
+                ("chunk_vectors", ctypes.c_uint64), ("slices", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("additions", ctypes.c_uint64)]
 
 
 class _KzgCellsInfo(ctypes.Structure):
@@ -480,6 +490,12 @@ def load_library() -> ctypes.CDLL:
     lib.plonk_kzg_evals_tables_build.argtypes = [vp]
     lib.plonk_kzg_evals_tables_drop.argtypes = [vp]
     lib.plonk_kzg_evals_tables_last.argtypes = [vp, ctypes.POINTER(_KzgEvalsTablesInfo)]
+    lib.plonk_kzg_many_tables_build.argtypes = [vp, u32]
+    lib.plonk_kzg_many_tables_drop.argtypes = [vp]
+    lib.plonk_kzg_commit_many.argtypes = [vp, vp, u64, vp]
+    lib.plonk_kzg_commit_many_dev.argtypes = [vp, vp, u64, vp]
+    lib.plonk_kzg_update_many.argtypes = [vp, vp, vp, vp, vp, u64, vp]
+    lib.plonk_kzg_many_last.argtypes = [vp, ctypes.POINTER(_KzgManyInfo)]
     lib.plonk_kzg_open_cells.argtypes = [vp, u32, ctypes.POINTER(vp), ctypes.POINTER(u64), u64, vp, vp, vp]
     lib.plonk_kzg_open_cells_dev.argtypes = [vp, u32, ctypes.POINTER(vp), ctypes.POINTER(u64), u64, vp, vp, vp]
     lib.plonk_kzg_cell_points.argtypes = [vp, u32, vp, vp]
@@ -1910,6 +1926,62 @@ class KzgDomain:
     def drop_tables(self):
         self.ctx._check(self.ctx.lib.plonk_kzg_evals_tables_drop(self.handle))
 
+    # ---- opt-in window tables: commitments of MANY SHORT vectors, one wave per vector ----
+    def many_last(self) -> dict:
+        info = _KzgManyInfo()
+        self.ctx._check(self.ctx.lib.plonk_kzg_many_last(self.handle, ctypes.byref(info)))
+        return {k: getattr(info, k) for k, _ in info._fields_ if k != "reserved"}
+
+    def build_many_tables(self, window_bits: int = 0) -> dict:
+        """plonk_kzg_many_tables_build: n x W x 2^(c-1) x 128 bytes of the context's table budget until drop_many_tables /
+        close; window_bits 0 picks the widest width that fits"""
+        self.ctx._check(self.ctx.lib.plonk_kzg_many_tables_build(self.handle, window_bits))
+        return self.many_last()
+
+    def drop_many_tables(self):
+        self.ctx._check(self.ctx.lib.plonk_kzg_many_tables_drop(self.handle))
+
+    def commit_many(self, vectors) -> list:
+        """plonk_kzg_commit_many: vectors of n values (lists of ints, or ONE bytes object of count x n x 32 Montgomery bytes)
+        -> 48-byte commitments"""
+        if isinstance(vectors, (bytes, bytearray)):
+            raw = bytes(vectors)
+        else:
+            raw = b"".join(bytes(p) if isinstance(p, (bytes, bytearray)) else fr_to_bytes_mont(p) for p in vectors)
+        if len(raw) % (32 * self.n):
+            raise ValueError("a vector of values must hold exactly n field elements")
+        count = len(raw) // (32 * self.n)
+        cm = ctypes.create_string_buffer(48 * max(count, 1))
+        self.ctx._check(self.ctx.lib.plonk_kzg_commit_many(self.handle, raw, count, cm))
+        return [cm.raw[48 * j:48 * j + 48] for j in range(count)]
+
+    def commit_many_dev(self, ptr: int, count: int, out_ptr: int):
+        """plonk_kzg_commit_many_dev: count x n values resident at `ptr`; the count x 48 bytes are written to the device
+        pointer `out_ptr`"""
+        self.ctx._check(self.ctx.lib.plonk_kzg_commit_many_dev(self.handle, ptr, count, out_ptr))
+
+    def update_many(self, updates, base=None) -> list:
+        """plonk_kzg_update_many: updates[j] = [(index, delta), ...]; base: one 48-byte commitment per segment, or None for
+        the identity -> base_j + sum delta L_index as 48 bytes each"""
+        updates = [list(u) for u in updates]
+        count = len(updates)
+        offs, idx, deltas = [0], [], []
+        for u in updates:
+            idx.extend(i for i, _ in u)
+            deltas.extend(x for _, x in u)
+            offs.append(len(idx))
+        bin_ = None
+        if base is not None:
+            bin_ = b"".join(bytes(b) for b in base)
+            if len(bin_) != 48 * count:
+                raise ValueError("one 48-byte base per segment")
+        oarr = (ctypes.c_uint64 * (count + 1))(*offs)
+        iarr = (ctypes.c_uint32 * max(len(idx), 1))(*idx)
+        cm = ctypes.create_string_buffer(48 * max(count, 1))
+        self.ctx._check(self.ctx.lib.plonk_kzg_update_many(self.handle, bin_, oarr, iarr, fr_to_bytes_mont(deltas) if deltas else b"\0" * 32,
+                                                            count, cm))
+        return [cm.raw[48 * j:48 * j + 48] for j in range(count)]
+
     # ---- multiproofs: many (vector, domain point) openings, one 96-byte proof ----
     def _open_multi(self, fn, ptrs, items, label, commitments, challenges):
         items = list(items)
@@ -2080,6 +2152,7 @@ class KzgDomain:
         if getattr(self, "handle", None):
             if getattr(self.ctx, "handle", None):
                 self.ctx.lib.plonk_kzg_evals_tables_drop(self.handle)   # the table budget first, then the handle
+                self.ctx.lib.plonk_kzg_many_tables_drop(self.handle)
                 self.ctx.lib.plonk_kzg_domain_destroy(self.handle)
             self.handle = None
 

@@ -683,6 +683,7 @@ int evals_impl(const char* api_fn, plonk_kzg_domain* dom, const void* const* vec
 }  // namespace
 
 int kze_points_ready(KzgDomain* d, uint32_t* built) { return lagrange_ready(d, kzd_state(d->evals), built); }
+const G1Affine* kze_points(KzgDomain* d) { return kzd_state(d->evals)->lag; }
 int kze_commit_values(KzgDomain* d, const Fr* s, uint8_t out48[48]) {
   return commit_values(d->c, kzd_state(d->evals), s, 1ull << d->log_n, out48);
 }

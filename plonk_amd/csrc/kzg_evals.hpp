@@ -48,6 +48,7 @@ bool kze_host_canonical(const void* const* vecs, uint64_t count, uint64_t n);
 // last call).
 struct KzgDomain;
 int kze_points_ready(KzgDomain* d, uint32_t* built);
+const G1Affine* kze_points(KzgDomain* d);   // the n resident points once kze_points_ready returned PLONK_OK (kzg_many.hip builds its window tables over them)
 int kze_commit_values(KzgDomain* d, const Fr* s, uint8_t out48[48]);
 // the same for `count` resident vectors, out48[48 j] for s[j]: one after the other on a handle without tables, as ONE run of
 // grouped table launches on a handle that holds them (kzg_evals_core.hpp kze_tables_plan)

@@ -1,5 +1,6 @@
 // The plonk_kzg_domain handle (kzg_domain.hip creates and destroys it) and the way in of every call on it: shared by the
-// files whose calls hang off the handle (kzg_domain.hip, kzg_evals.hip, kzg_cells.hip, kzg_recover.hip, kzg_multiproof.hip).
+// files whose calls hang off the handle (kzg_domain.hip, kzg_evals.hip, kzg_cells.hip, kzg_recover.hip, kzg_multiproof.hip,
+// kzg_many.hip).
 // DESIGN.md section 21 has the layout.
 #pragma once
 #include <mutex>
@@ -21,10 +22,12 @@ struct KzgEvals;     // kzg_evals.hip: the Lagrange points, the opt-in tables an
 struct KzgCells;     // kzg_cells.hip: the A^(u) tables and the workspace of the cell proofs
 struct KzgRecover;   // kzg_recover.hip: the workspace of the cell recovery
 struct KzgMulti;     // kzg_multiproof.hip: the invd table and the workspace of plonk_kzg_multiproof_open
+struct KzgMany;      // kzg_many.hip: the opt-in window tables and the workspace of the many-vector commitments
 void kze_release(KzgEvals* evals);
 void kzc_release(KzgCells* cells);
 void kzr_release(KzgRecover* recover);
 void kmp_release(KzgMulti* multi);
+void kzm_release(KzgMany* many);
 
 struct KzdBufs {
   enum { WS, F, G, EVALS, TMP, OUT48, DESC, META, NBUF };   // grow-only buffers of the open calls
@@ -42,7 +45,9 @@ struct KzgDomain : KzdBufs, DevBufs<KzdBufs::NBUF> {
   KzgCells* cells = nullptr;
   KzgRecover* recover = nullptr;
   KzgMulti* multi = nullptr;
-  ~KzgDomain() {   // in this order: the multiproof state, the recovery state, the cell state, the evaluation-form state, the fixed buffers; the base frees the grow-only ones last
+  KzgMany* many = nullptr;
+  ~KzgDomain() {   // in this order: the many-vector state (it reads the Lagrange points of the evaluation-form state), the multiproof state, the recovery state, the cell state, the evaluation-form state, the fixed buffers; the base frees the grow-only ones last
+    kzm_release(many);
     kmp_release(multi);
     kzr_release(recover);
     kzc_release(cells);
