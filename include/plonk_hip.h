@@ -920,6 +920,78 @@ int plonk_kzg_update_many(plonk_kzg_domain* domain, const uint8_t* base48 /* cou
                           const uint32_t* index, const uint64_t* deltas /* offsets[count] x 4 */, uint64_t count, uint8_t* commitments48);
 int plonk_kzg_many_last(plonk_kzg_domain* domain, plonk_kzg_many_info* out);
 
+/* ---- KZG10 vector-commitment trees: build, update, prove on the device --------------------------------------
+ * A dense n-ary tree of KZG commitments over a domain handle that holds many-vector tables, n = 2^log_n <= 2^12, depth D >= 1,
+ * D x log_n <= 26.  Level l (0 = the root) has n^l nodes; the tree keeps ALL levels resident:
+ *     vals[l]    one flat array of n^(l+1) Montgomery Fr; vals[D-1] holds the N = n^D leaves
+ *     C[l][k]  = sum_i vals[l][k n + i] L_i              the 48 bytes plonk_kzg_commit_evals gives for that vector
+ *     vals[l][j] = h(C[l+1][j])   for l < D-1            the flat index of a child is its slot in the parent level
+ *     h(c48)   = Transcript::new("kzg10-tree-v1"); append_message("node", c48); challenge_scalar("node-scalar")
+ *   (Merlin, a 64-byte wide reduction; the identity 0xC0 00 .. is hashed like any other 48 bytes).  Per node the tree also keeps
+ *   the 48 bytes and the decoded affine point with its identity flag, so an update never decodes or subgroup-checks a node.
+ *   These bytes are data, not tables: they are not counted against the table budget; plonk_kzg_tree_last reports them.
+ * plonk_kzg_tree_create: PLONK_ERR_ARG for NULL, depth == 0, log_n > 12 or depth x log_n > 26; PLONK_ERR_STATE on a context
+ *   with a communicator or once its key was reloaded, as for every call below that takes the tree.  The tree is EMPTY.  A tree
+ *   is destroyed before its domain.
+ * plonk_kzg_tree_build (leaves: N x 4 limbs, host) / _build_dev (leaves_dev: 16-byte aligned device pointer): the host form
+ *   stages the leaves through the two upload buffers of plonk_kzg_open into vals[D-1], the _dev form copies them there.  Then
+ *   per level, bottom up, on the stream with no host round trip: the accumulation of plonk_kzg_commit_many (chunked under the
+ *   handle's workspace cap), a finish kernel (point, flag, 48 bytes) and the map h into the level above.  PLONK_ERR_ARG for a
+ *   NULL or misaligned pointer, PLONK_ERR_DATA for a leaf >= q, PLONK_ERR_STATE when the domain holds no many-vector tables
+ *   (their window width may differ from the last build's).  A failed or refused build leaves the tree EMPTY: every call but
+ *   build, destroy and plonk_kzg_tree_last (built == 0) then returns PLONK_ERR_STATE.
+ * plonk_kzg_tree_root / _nodes: 48 bytes per node; PLONK_ERR_ARG for a level >= D or first + count beyond the level.
+ * plonk_kzg_tree_update: leaf leaf_index[k] becomes values[k], k < count.  Every check comes before anything is changed, in
+ *   this order: PLONK_ERR_ARG (NULL, count == 0 or > 2^20, an index >= N, a REPEATED index), PLONK_ERR_DATA (a value >= q),
+ *   PLONK_ERR_STATE (an empty tree, no many-vector tables).  The touched nodes of all levels, their segments and child indices
+ *   are computed once on the host and uploaded once; then per level, bottom up: delta = new - old with the store of the new
+ *   value, the sparse accumulation of plonk_kzg_update_many over (child index, delta), the finish kernel with the stored point
+ *   as base, the map, and the delta of the parent's value.  Afterwards every stored byte equals a build from the new leaves.
+ * plonk_kzg_tree_proof_nodes: host only: the number of path commitments a proof of these leaves carries.
+ * plonk_kzg_tree_prove: with T_D the sorted distinct leaf indices and T_l = { j / n : j in T_(l+1) }, the multiproof's vectors
+ *   are the nodes of T_0 (the root), T_1, .., T_(D-1), each ascending; its items are, per level l in that order, the flat
+ *   indices of T_(l+1) as (node j / n, point j mod n); path48 holds the commitments of T_1 .. T_(D-1) in that order — the
+ *   items of level l < D-1 are one to one with the path commitments of level l + 1 and their values are h of those.
+ *   values[k] is the leaf leaf_index[k] (the caller's order).  The vectors are read where the tree holds them; the transcript
+ *   of plonk_kzg_multiproof_open is used unchanged under the caller's label, and so are its Lagrange-basis tables.
+ *   PLONK_ERR_ARG for NULL, count == 0, a repeated or out-of-range index, more than 65536 distinct nodes or 2^20 items;
+ *   PLONK_ERR_DATA / PLONK_ERR_STATE as plonk_kzg_multiproof_open_dev.  An error leaves the outputs untouched.
+ * plonk_kzg_tree_check: needs no tree and no domain.  Rebuilds the items from the indices, computes the inner values with h
+ *   on the host and calls plonk_kzg_multiproof_check on root48 || path48: PLONK_ERR_ARG also for `nodes` other than what the
+ *   indices imply; otherwise PLONK_ERR_ARG, _DATA, _POINT, PLONK_OK or PLONK_ERR_VERIFY as that call.
+ * plonk_kzg_tree_last: the tree and how its last build / update / prove ran; the tests assert it against the plan computed
+ *   on the host (plonk_amd/csrc/kzg_tree_core.hpp).
+ * The tree calls leave the context, its tables and budget, plonk_ctx_last_msm and plonk_kzg_many_last as they found them;
+ * plonk_kzg_tree_prove runs the MSMs plonk_kzg_multiproof_open documents. */
+typedef struct plonk_kzg_tree plonk_kzg_tree;
+typedef struct plonk_kzg_tree_info {
+  uint32_t log_n, depth;
+  uint32_t built;             /* 0: the tree is EMPTY */
+  uint32_t kind;              /* the last call that ran: 0 none, 1 build, 2 update, 3 prove */
+  uint64_t leaves;            /* N = n^depth */
+  uint64_t device_bytes;      /* the values, bytes, points and flags of all levels, and the tree's workspace */
+  uint64_t touched_nodes;     /* nodes it committed (build: all; update: |T_0| + .. + |T_(D-1)|) or opened (prove) */
+  uint64_t sparse_terms;      /* update: |T_1| + .. + |T_D| */
+  uint64_t chunks;            /* accumulation launches of a build or an update */
+  uint64_t items, vectors;    /* prove: K and M of the multiproof */
+} plonk_kzg_tree_info;
+int plonk_kzg_tree_create(plonk_kzg_domain* domain, uint32_t depth, plonk_kzg_tree** out);
+void plonk_kzg_tree_destroy(plonk_kzg_tree* tree);
+int plonk_kzg_tree_build(plonk_kzg_tree* tree, const uint64_t* leaves /* N x 4 */);
+int plonk_kzg_tree_build_dev(plonk_kzg_tree* tree, const void* leaves_dev);
+int plonk_kzg_tree_root(plonk_kzg_tree* tree, uint8_t out48[48]);
+int plonk_kzg_tree_nodes(plonk_kzg_tree* tree, uint32_t level, uint64_t first, uint64_t count, uint8_t* out48 /* count x 48 */);
+int plonk_kzg_tree_update(plonk_kzg_tree* tree, const uint64_t* leaf_index, const uint64_t* values /* count x 4 */, uint64_t count);
+int plonk_kzg_tree_proof_nodes(uint32_t log_n, uint32_t depth, const uint64_t* leaf_index, uint64_t count, uint64_t* nodes);
+int plonk_kzg_tree_prove(plonk_kzg_tree* tree, const uint64_t* leaf_index, uint64_t count, const uint8_t* label, uint64_t label_len,
+                         const uint64_t* challenges_override /* 8 limbs or NULL */, uint64_t* values /* count x 4 out */,
+                         uint8_t* path48 /* nodes x 48 out */, uint8_t proof96[96]);
+int plonk_kzg_tree_check(plonk_kzg_key* key, uint32_t log_n, uint32_t depth, const uint8_t root48[48], const uint64_t* leaf_index,
+                         const uint64_t* values /* count x 4 */, uint64_t count, const uint8_t* path48, uint64_t nodes,
+                         const uint8_t proof96[96], const uint8_t* label, uint64_t label_len, const uint64_t* challenges_override,
+                         plonk_verify_info* info /* may be NULL */);
+int plonk_kzg_tree_last(plonk_kzg_tree* tree, plonk_kzg_tree_info* out);
+
 /* ---- KZG10 cell proofs: a polynomial opened on every coset of its domain --------------------------------
  * The n = 2^log_n evaluations of a polynomial cut into r = n / l cells of l = 2^log_cell values, each cell with ONE 48-byte
  * proof that opens all l of its values at once (Feist-Khovratovich section 3; data-availability sampling).  w is the generator

@@ -80,6 +80,9 @@ EXPORTS = [
     "plonk_kzg_evals_tables_build", "plonk_kzg_evals_tables_drop", "plonk_kzg_evals_tables_last",
     "plonk_kzg_many_tables_build", "plonk_kzg_many_tables_drop", "plonk_kzg_commit_many", "plonk_kzg_commit_many_dev",
     "plonk_kzg_update_many", "plonk_kzg_many_last",
+    "plonk_kzg_tree_create", "plonk_kzg_tree_destroy", "plonk_kzg_tree_build", "plonk_kzg_tree_build_dev", "plonk_kzg_tree_root",
+    "plonk_kzg_tree_nodes", "plonk_kzg_tree_update", "plonk_kzg_tree_proof_nodes", "plonk_kzg_tree_prove", "plonk_kzg_tree_check",
+    "plonk_kzg_tree_last",
     "plonk_kzg_open_cells", "plonk_kzg_open_cells_dev", "plonk_kzg_cell_points", "plonk_kzg_cells_last",
     "plonk_kzg_cell_verifier_create", "plonk_kzg_cell_verifier_destroy", "plonk_kzg_verify_cells", "plonk_kzg_verify_cells_each",
     "plonk_kzg_cell_verifier_last",
@@ -180,6 +183,12 @@ class _KzgManyInfo(ctypes.Structure):
                 ("table_bytes", ctypes.c_uint64), ("count", ctypes.c_uint64), ("terms", ctypes.c_uint64), ("chunks", ctypes.c_uint64),
                 ("chunk_vectors", ctypes.c_uint64), ("slices", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
                 ("additions", ctypes.c_uint64)]
+
+
+class _KzgTreeInfo(ctypes.Structure):
+    _fields_ = [("log_n", ctypes.c_uint32), ("depth", ctypes.c_uint32), ("built", ctypes.c_uint32), ("kind", ctypes.c_uint32),
+                ("leaves", ctypes.c_uint64), ("device_bytes", ctypes.c_uint64), ("touched_nodes", ctypes.c_uint64),
+                ("sparse_terms", ctypes.c_uint64), ("chunks", ctypes.c_uint64), ("items", ctypes.c_uint64), ("vectors", ctypes.c_uint64)]
 
 
 class _KzgCellsInfo(ctypes.Structure):
@@ -496,6 +505,18 @@ def load_library() -> ctypes.CDLL:
     lib.plonk_kzg_commit_many_dev.argtypes = [vp, vp, u64, vp]
     lib.plonk_kzg_update_many.argtypes = [vp, vp, vp, vp, vp, u64, vp]
     lib.plonk_kzg_many_last.argtypes = [vp, ctypes.POINTER(_KzgManyInfo)]
+    lib.plonk_kzg_tree_create.argtypes = [vp, u32, ctypes.POINTER(vp)]
+    lib.plonk_kzg_tree_destroy.argtypes = [vp]
+    lib.plonk_kzg_tree_destroy.restype = None
+    lib.plonk_kzg_tree_build.argtypes = [vp, vp]
+    lib.plonk_kzg_tree_build_dev.argtypes = [vp, vp]
+    lib.plonk_kzg_tree_root.argtypes = [vp, vp]
+    lib.plonk_kzg_tree_nodes.argtypes = [vp, u32, u64, u64, vp]
+    lib.plonk_kzg_tree_update.argtypes = [vp, vp, vp, u64]
+    lib.plonk_kzg_tree_proof_nodes.argtypes = [u32, u32, vp, u64, ctypes.POINTER(u64)]
+    lib.plonk_kzg_tree_prove.argtypes = [vp, vp, u64, vp, u64, vp, vp, vp, vp]
+    lib.plonk_kzg_tree_check.argtypes = [vp, u32, u32, vp, vp, vp, u64, vp, u64, vp, vp, u64, vp, vp]
+    lib.plonk_kzg_tree_last.argtypes = [vp, ctypes.POINTER(_KzgTreeInfo)]
     lib.plonk_kzg_open_cells.argtypes = [vp, u32, ctypes.POINTER(vp), ctypes.POINTER(u64), u64, vp, vp, vp]
     lib.plonk_kzg_open_cells_dev.argtypes = [vp, u32, ctypes.POINTER(vp), ctypes.POINTER(u64), u64, vp, vp, vp]
     lib.plonk_kzg_cell_points.argtypes = [vp, u32, vp, vp]
@@ -1686,6 +1707,33 @@ class KzgKey:
             self.ctx._check(rc)
         return rc == PLONK_OK
 
+    def check_tree_code(self, log_n: int, depth: int, root: bytes, leaf_index, values, path, proof: bytes, label: bytes = b"",
+                        challenges=None, nodes: "int | None" = None):
+        """(return code of plonk_kzg_tree_check, plonk_verify_info as a dict).  values: one int per leaf index, or 32 Montgomery
+        bytes; path: the 48-byte path commitments KzgTree.prove returned; nodes: their count as told to the library (default:
+        len(path))"""
+        leaf_index, values, path = list(leaf_index), list(values), [bytes(c) for c in path]
+        if len(bytes(root)) != 48 or any(len(c) != 48 for c in path) or len(bytes(proof)) != 96:
+            raise ValueError("commitments are 48-byte compressed G1 points, a multiproof is 96 bytes")
+        if len(values) != len(leaf_index):
+            raise ValueError("one value per leaf index")
+        idx = (ctypes.c_uint64 * max(len(leaf_index), 1))(*leaf_index)
+        vals = b"".join(bytes(v) if isinstance(v, (bytes, bytearray)) else fr_to_bytes_mont([v]) for v in values) or b"\0"
+        info = _VerifyInfo()
+        rc = self.ctx.lib.plonk_kzg_tree_check(self.handle, log_n, depth, bytes(root), idx, vals, len(leaf_index), b"".join(path) or None,
+                                               len(path) if nodes is None else nodes, bytes(proof), label, len(label),
+                                               _multi_challenges(challenges), ctypes.byref(info))
+        return rc, {k: getattr(info, k) for k, _ in info._fields_}
+
+    def check_tree(self, log_n: int, depth: int, root: bytes, leaf_index, values, path, proof: bytes, label: bytes = b"",
+                   challenges=None) -> bool:
+        """plonk_kzg_tree_check: True when the proof of KzgTree.prove shows these leaves under `root`, False when it does not
+        (PLONK_ERR_VERIFY); malformed input raises.  Needs no tree and no domain."""
+        rc, _ = self.check_tree_code(log_n, depth, root, leaf_index, values, path, proof, label, challenges)
+        if rc not in (PLONK_OK, -12):
+            self.ctx._check(rc)
+        return rc == PLONK_OK
+
     def _pairing_each_values(self, a, b):
         """TEST HOOK: per check the final-exponentiated Fp12 value of e(-a, x_h) e(b, h) as 12 integers (tower order), from
         the device pairing kernel.  Not part of the C API."""
@@ -2150,10 +2198,100 @@ class KzgDomain:
 
     def close(self):
         if getattr(self, "handle", None):
+            for t in list(getattr(self, "_trees", ())):   # they hold a pointer to the native handle
+                t.close()
             if getattr(self.ctx, "handle", None):
                 self.ctx.lib.plonk_kzg_evals_tables_drop(self.handle)   # the table budget first, then the handle
                 self.ctx.lib.plonk_kzg_many_tables_drop(self.handle)
                 self.ctx.lib.plonk_kzg_domain_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class KzgTree:
+    """plonk_kzg_tree: a dense n-ary KZG vector-commitment tree of `depth` levels over `domain` (n = 2^log_n values per node,
+    N = n^depth leaves), every level resident on the device (include/plonk_hip.h).  The domain must hold many-vector tables
+    (KzgDomain.build_many_tables) for `build` and `update`.  Closed before its domain: KzgDomain.close does it."""
+
+    def __init__(self, domain: "KzgDomain", depth: int):
+        self.domain, self.ctx, self.depth, self.log_n = domain, domain.ctx, depth, domain.log_n
+        self.leaves = 1 << (domain.log_n * max(depth, 0)) if 0 <= domain.log_n * max(depth, 0) <= 26 else 0
+        h = ctypes.c_void_p()
+        self.ctx._check(self.ctx.lib.plonk_kzg_tree_create(domain.handle, depth, ctypes.byref(h)))
+        self.handle = h
+        if not hasattr(domain, "_trees"):
+            domain._trees = weakref.WeakSet()
+        domain._trees.add(self)
+
+    def build(self, leaves):
+        """plonk_kzg_tree_build: the N leaves as ints, or N x 32 Montgomery bytes"""
+        raw = bytes(leaves) if isinstance(leaves, (bytes, bytearray)) else fr_to_bytes_mont(leaves)
+        if len(raw) != 32 * self.leaves:
+            raise ValueError("a tree is built from exactly n^depth leaves")
+        self.ctx._check(self.ctx.lib.plonk_kzg_tree_build(self.handle, raw))
+
+    def build_dev(self, ptr: int):
+        """plonk_kzg_tree_build_dev: the N leaves resident at the device pointer `ptr`"""
+        self.ctx._check(self.ctx.lib.plonk_kzg_tree_build_dev(self.handle, ptr))
+
+    def root(self) -> bytes:
+        out = ctypes.create_string_buffer(48)
+        self.ctx._check(self.ctx.lib.plonk_kzg_tree_root(self.handle, out))
+        return out.raw
+
+    def nodes(self, level: int, first: int = 0, count: "int | None" = None) -> list:
+        """plonk_kzg_tree_nodes: the 48-byte commitments of `count` nodes of `level` from `first` on (default: the rest)"""
+        if count is None:
+            count = (1 << (self.log_n * level)) - first
+        out = ctypes.create_string_buffer(48 * max(count, 1))
+        self.ctx._check(self.ctx.lib.plonk_kzg_tree_nodes(self.handle, level, first, count, out))
+        return [out.raw[48 * j:48 * j + 48] for j in range(count)]
+
+    def update(self, leaf_index, values):
+        """plonk_kzg_tree_update: leaf leaf_index[k] becomes values[k] (ints, or 32 Montgomery bytes each)"""
+        leaf_index, values = list(leaf_index), list(values)
+        if len(leaf_index) != len(values):
+            raise ValueError("one value per leaf index")
+        idx = (ctypes.c_uint64 * max(len(leaf_index), 1))(*leaf_index)
+        vals = b"".join(bytes(v) if isinstance(v, (bytes, bytearray)) else fr_to_bytes_mont([v]) for v in values) or b"\0" * 32
+        self.ctx._check(self.ctx.lib.plonk_kzg_tree_update(self.handle, idx, vals, len(leaf_index)))
+
+    def proof_nodes(self, leaf_index) -> int:
+        leaf_index = list(leaf_index)
+        idx = (ctypes.c_uint64 * max(len(leaf_index), 1))(*leaf_index)
+        out = ctypes.c_uint64()
+        self.ctx._check(self.ctx.lib.plonk_kzg_tree_proof_nodes(self.log_n, self.depth, idx, len(leaf_index), ctypes.byref(out)))
+        return out.value
+
+    def prove(self, leaf_index, label: bytes = b"", challenges=None):
+        """plonk_kzg_tree_prove -> (values, path, proof): the leaves in the order of leaf_index, the path commitments (48 bytes
+        each, levels 1 .. depth-1, ascending within a level) and the 96-byte multiproof"""
+        leaf_index = list(leaf_index)
+        count = len(leaf_index)
+        idx = (ctypes.c_uint64 * max(count, 1))(*leaf_index)
+        nodes = ctypes.c_uint64()
+        self.ctx._check(self.ctx.lib.plonk_kzg_tree_proof_nodes(self.log_n, self.depth, idx, count, ctypes.byref(nodes)))
+        vals = ctypes.create_string_buffer(32 * max(count, 1))
+        path = ctypes.create_string_buffer(48 * max(nodes.value, 1))
+        proof = ctypes.create_string_buffer(96)
+        self.ctx._check(self.ctx.lib.plonk_kzg_tree_prove(self.handle, idx, count, label, len(label), _multi_challenges(challenges), vals, path,
+                                                          proof))
+        return (fr_from_bytes_mont(vals.raw[:32 * count]), [path.raw[48 * j:48 * j + 48] for j in range(nodes.value)], proof.raw)
+
+    def last(self) -> dict:
+        info = _KzgTreeInfo()
+        self.ctx._check(self.ctx.lib.plonk_kzg_tree_last(self.handle, ctypes.byref(info)))
+        return {k: getattr(info, k) for k, _ in info._fields_}
+
+    def close(self):
+        if getattr(self, "handle", None):
+            if getattr(self.domain, "handle", None) and getattr(self.ctx, "handle", None):
+                self.ctx.lib.plonk_kzg_tree_destroy(self.handle)
             self.handle = None
 
     def __del__(self):

@@ -277,6 +277,12 @@ struct KzgMany : KzmBufs, DevBufs<KzmBufs::NBUF> {
 
 void kzm_release(KzgMany* many) { delete many; }
 void kzm_test_force_slices(KzgDomain* d, uint32_t slices) { kzd_state(d->many)->force_slices = slices; }
+bool kzm_handle_tables(const KzgDomain* d, KzmTables* out) {
+  const KzgMany* m = d->many;
+  if (!m || !m->table) return false;
+  *out = KzmTables{m->table, d->log_n, m->window_bits, m->windows};
+  return true;
+}
 
 namespace {
 

@@ -29,8 +29,11 @@ int kzm_accumulate_sparse(Ctx* c, const KzmTables& t, const uint64_t* offsets, c
 // VDEC_IDENTITY, decode_points); out48 is 4-byte aligned
 int kzm_compress(Ctx* c, const G1RSlot* partial, uint32_t slices, const G1Affine* base, const int32_t* kind, uint64_t count, uint8_t* out48);
 
-// TEST HOOK (tests/csrc/dev_kzg_many.hip): the slices of the dense calls on the handle from now on (0: the plan's own rule)
 struct KzgDomain;
+// the window tables the handle holds (false: it holds none) — kzg_tree.hip runs the launchers above over them; the caller holds
+// the context's mutex
+bool kzm_handle_tables(const KzgDomain* d, KzmTables* out);
+// TEST HOOK (tests/csrc/dev_kzg_many.hip): the slices of the dense calls on the handle from now on (0: the plan's own rule)
 void kzm_test_force_slices(KzgDomain* d, uint32_t slices);
 
 }  // namespace plonk

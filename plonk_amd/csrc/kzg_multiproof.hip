@@ -608,6 +608,20 @@ int check_body(const char* api_fn, KzgKey* kk, const CheckCall& a, plonk_verify_
 
 }  // namespace
 
+int kmp_open_entered(const char* api_fn, KzgDomain* d, const void* const* vecs_dev, uint64_t nvectors, const uint8_t* commitments_in,
+                     const uint32_t* vector_index, const uint32_t* point_index, uint64_t count, const uint8_t* label, uint64_t label_len,
+                     const uint64_t* challenges_override, uint64_t* values, uint8_t* proof96) {
+  if (!vecs_dev || !commitments_in || !vector_index || !point_index || !values || !proof96 || (label_len && !label))
+    API_FAIL(PLONK_ERR_ARG, "invalid argument: a required pointer is NULL");
+  if (kmp_check_items(d->log_n, nvectors, vector_index, point_index, count, false, false))
+    API_FAIL(PLONK_ERR_ARG, "invalid argument: count must be in [1, 2^20], nvectors in [1, 65536] and every index in range");
+  OpenCall a = {vecs_dev, nvectors, commitments_in, vector_index, point_index, count, label, label_len, challenges_override != nullptr,
+                Fr::zero(), Fr::zero(), true, values, nullptr, proof96};
+  if (kmp_check_override(challenges_override, d->log_n, &a.r, &a.t))
+    API_FAIL(PLONK_ERR_DATA, "the challenges override is not canonical, or its t lies in the domain");
+  return open_body(api_fn, d, kzd_state(d->multi), a);
+}
+
 void kmp_check_release(void* ws) { delete (KzgMultiCheck*)ws; }
 
 KzgKey::~KzgKey() {

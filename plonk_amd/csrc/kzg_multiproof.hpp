@@ -48,6 +48,13 @@ int kmp_aggregate(Ctx* c, const KmpAggArgs& a, uint64_t groups);
 int kmp_weights(Ctx* c, uint32_t log_n, const Fr& t, const uint32_t* point_index, const Fr* rpow, const Fr* yk, const uint32_t* perm,
                 const uint32_t* off, uint64_t K, uint64_t M, Fr* wt, void* stw, Fr* y_out, uint32_t* sc, uint32_t* ids);
 
+// plonk_kzg_multiproof_open_dev (given commitments, no commitments_out) for a caller that is inside the handle already —
+// kzg_tree.hip, which holds the context's mutex and has made the KZD_WORK checks: the argument checks, then the same body
+struct KzgDomain;
+int kmp_open_entered(const char* api_fn, KzgDomain* d, const void* const* vecs_dev, uint64_t nvectors, const uint8_t* commitments_in,
+                     const uint32_t* vector_index, const uint32_t* point_index, uint64_t count, const uint8_t* label, uint64_t label_len,
+                     const uint64_t* challenges_override, uint64_t* values, uint8_t* proof96);
+
 void kmp_check_release(void* ws);   // the workspace plonk_kzg_multiproof_check hangs off its key
 
 }  // namespace plonk

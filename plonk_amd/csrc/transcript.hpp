@@ -89,6 +89,10 @@ class Strobe128 {
   HD void meta_ad(const uint8_t* d, size_t n, bool more) { begin_op(FLAG_M | FLAG_A, more); absorb(d, n); }
   HD void ad(const uint8_t* d, size_t n, bool more) { begin_op(FLAG_A, more); absorb(d, n); }
   HD void prf(uint8_t* out, size_t n, bool more) { begin_op(FLAG_I | FLAG_A | FLAG_C, more); squeeze(out, n); }
+  // read-only: for a caller that carries a constant prefix to a kernel as data (kzg_tree_core.hpp: kzt_map_seed)
+  HD const uint8_t* raw_state() const { return st_; }
+  HD uint8_t raw_pos() const { return pos_; }
+  HD uint8_t raw_pos_begin() const { return pos_begin_; }
 
  private:
   static constexpr uint8_t R = 166;
@@ -185,6 +189,7 @@ class Transcript {
     append_message("dom-sep", (const uint8_t*)"circuit_size", 12);
     append_u64("n", n);
   }
+  HD const Strobe128& strobe() const { return s_; }
 
  private:
   Strobe128 s_;
